@@ -14,9 +14,17 @@ stream of batches (``CaptionPipeline``: batch i + 1's encoder on its own HIP str
 waited for one step later) -- every step still encodes, decodes and exchanges exactly one batch and all K are complete when the
 region closes; the one-batch-at-a-time rate of rounds 1-4 is measured in the same run and reported as ``value_sequential``.  Workloads (BASELINE.json configs): ``c2`` = CaptioningLSTM
 (default, configs[1]); ``c3`` = CaptioningTransformer 6-layer/8-head; ``c5`` = the 300-template fp16 beam-10 sweep.
-The default run reports c2 as the contract line and attaches a c3 measurement under ``"c3"``.
+The default run reports c2 as the contract line; with ``--full`` it also attaches a c3 measurement under ``"c3"``.
 
-What the line carries besides the contract fields:
+A plain run (no ``--full``) does only what the headline needs: it sets up, runs ``--warmup`` untimed steps, times exactly ``--steps``
+steps one batch at a time (``value`` / ``ms_per_step``), writes the last timed step's outputs when ``--dump-outputs DIR`` is given and
+prints the result line.  ``--full`` adds every other leg below (and the pipelined / hipGraph / host-inclusive rates, the other
+precisions, the CPU baselines and the c3 leg of the default workload), as rounds 1-6 ran them.
+
+``--dump-outputs DIR``: the gathered token ids and caption lengths of the headline's last timed step (C5: the sweep's; score-*: the
+perplexities) as ``DIR/<name>.npy`` (integers as float64, exact); the inputs are seeded, so two builds compare output for output.
+
+What the line carries besides the contract fields (``--full``):
   roofline           ONE kernel template at ONE shape -- the launch key (entry[role]{MxNxK}) with the largest share of the
                      step -- timed with HIP events recorded inside the library on the launch stream, every launch of it,
                      inside the timed region; priced against MFMA peak or HBM bandwidth by its arithmetic intensity
@@ -56,6 +64,8 @@ PEAK_16_TFLOPS = 2500.0  # dense bf16 / fp16 MFMA peak
 PMC_ROUND = next((r for r in ("r6", "r5") if os.path.exists(os.path.join(ROOT, "profiles", r, "pmc_hbm_traffic.json"))), "r6")
 PMC_FILE = os.path.join(ROOT, "profiles", PMC_ROUND, "pmc_hbm_traffic.json")
 TORCH_DTYPE = {"bf16": torch.bfloat16, "f16": torch.float16, "f32": torch.float32}
+
+DUMP_CAP_BYTES = 60 << 20  # --dump-outputs: at most 64 MB in all, with room for the .npy headers
 
 _SD_CACHE = {}
 RANK_TIMES = []         # wall time of the last timed region on every rank (seconds), filled by timed_region
@@ -377,9 +387,9 @@ def timed_steps(model, images, rank, n_local, n_total, steps, barrier, watch=Non
         # that the instrumentation stays below ~0.2 ms per step (an unbiased sample of the same launches)
         with hip.profile(watch=watch, stride=stride) as prof:
             dt, out = timed_region(step, steps, world, images.device, drain=drain)
-        return dt, out[1], prof.summary()
+        return dt, out, prof.summary()
     dt, out = timed_region(step, steps, world, images.device, drain=drain)
-    return dt, out[1], {}
+    return dt, out, {}
 
 
 def synth_images_u8(n, seed=0):
@@ -420,6 +430,12 @@ def host_inclusive(model, n_local, steps):
     return out
 
 
+def last_outputs(out):
+    """The gathered ``(tokens, lengths)`` a timed region's last step returned, copied to the host as soon as the region closes (a
+    hipGraph replay hands out its static output buffers, which the next replay overwrites)."""
+    return {"tokens": out[0].cpu(), "lengths": out[1].cpu()}
+
+
 def run_workload(workload, args, rank, world, dev, steps, warmup, with_cpu, dtype="bf16", main_line=True):
     import torch.distributed as dist
     from deephumor_amd import hip
@@ -436,6 +452,20 @@ def run_workload(workload, args, rank, world, dev, steps, warmup, with_cpu, dtyp
 
     graph = args.graph
     stride = 1
+    if not args.full:
+        # the plain run: the headline's region alone (one batch at a time, no events inside it), after --warmup untimed steps
+        # (at least one: code-object loading, allocator growth and a hipGraph capture stay out of the region)
+        with torch.no_grad():
+            for w in range(max(1, warmup)):
+                one_step(model, images, rank * n_local, n_total, seed=w, graph=graph)
+            dt, out, _ = timed_steps(model, images, rank, n_local, n_total, steps, barrier, graph=graph)
+        seq = {"value": n_total * steps / dt, "unit": "captions/s", "ms_per_step": dt / steps * 1e3}
+        rt = list(RANK_TIMES)
+        return {"value": seq["value"], "ms_per_step": seq["ms_per_step"], "mean_caption_len": float(out[1].float().mean()),
+                "schedule": "sequential: one batch at a time" + (" (hipGraph replay)" if graph else ""), "sequential": seq,
+                "per_rank_ms_per_step": {"min": min(rt) / steps * 1e3, "max": max(rt) / steps * 1e3, "ranks": len(rt),
+                                         "skew_ms": (max(rt) - min(rt)) / steps * 1e3},
+                "outputs": last_outputs(out)}
     with torch.no_grad():
         # untimed: a cold pass (code-object loading, allocator growth), then one fully instrumented pass (HIP events around
         # every launch made through the library) for the per-kernel breakdown and the choice of the roofline kernel
@@ -455,14 +485,17 @@ def run_workload(workload, args, rank, world, dev, steps, warmup, with_cpu, dtyp
             # the same K steps one batch at a time first (rounds 1-4's headline; kept as value_sequential) -- the roofline kernel's
             # launches are event-timed in THIS region, where the kernel has the chip to itself (in the pipelined region it shares the
             # CUs with the next batch's encoder: its elapsed time there says nothing about the kernel) -- then the production schedule
-            ts, _, summary = timed_steps(model, images, rank, n_local, n_total, steps, barrier, watch=watch, stride=stride)
+            ts, out, summary = timed_steps(model, images, rank, n_local, n_total, steps, barrier, watch=watch, stride=stride)
+            outputs = last_outputs(out)
             seq = {"value": n_total * steps / ts, "unit": "captions/s", "ms_per_step": ts / steps * 1e3}
             seq_rank_times = list(RANK_TIMES)             # every rank's wall time of THIS region (the one `value` comes from)
-            dt, lens, _ = timed_steps(model, images, rank, n_local, n_total, steps, barrier, pipelined=True)
+            dt, (_, lens), _ = timed_steps(model, images, rank, n_local, n_total, steps, barrier, pipelined=True)
         elif watch:
-            dt, lens, summary = timed_steps(model, images, rank, n_local, n_total, steps, barrier, watch=watch, stride=stride)
+            dt, out, summary = timed_steps(model, images, rank, n_local, n_total, steps, barrier, watch=watch, stride=stride)
+            outputs, lens = last_outputs(out), out[1]
         else:
-            dt, lens, summary = timed_steps(model, images, rank, n_local, n_total, steps, barrier, graph=graph)
+            dt, out, summary = timed_steps(model, images, rank, n_local, n_total, steps, barrier, graph=graph)
+            outputs, lens = last_outputs(out), out[1]
     # `value` is ONE BATCH AT A TIME (rounds 1-4's definition: a step = one pass of the hot path over one batch, nothing of the next
     # batch under it) -- the region the roofline kernel is event-timed in; the production schedule's rate (the same K batches as one
     # pipelined stream, round 5's `value`) is reported next to it as `pipelined` / value_pipelined
@@ -472,7 +505,7 @@ def run_workload(workload, args, rank, world, dev, steps, warmup, with_cpu, dtyp
     if seq is None:
         seq, pipe = {"value": n_total * steps / dt, "unit": "captions/s", "ms_per_step": dt / steps * 1e3}, None
     res = {"value": seq["value"], "ms_per_step": seq["ms_per_step"],
-           "mean_caption_len": float(lens.float().mean()) if lens is not None else None}
+           "mean_caption_len": float(lens.float().mean()) if lens is not None else None, "outputs": outputs}
     res["schedule"] = "sequential: one batch at a time" + (" (hipGraph replay)" if graph else "")
     res["sequential"] = seq
     if pipe is not None:
@@ -632,12 +665,13 @@ def run_c5(args, rank, world, dev, dtype):
         return gather_captions(toks, lens, n_total)
 
     with torch.no_grad():
-        sweep(0)
+        for w in range(max(1, args.warmup)):
+            sweep(w)
         reps = max(1, args.steps)
         dt, (toks, lens) = timed_region(lambda s: sweep(100 + s), reps, world, dev)
     return {"workload": workload_name("c5"), "value": n_total * reps / dt, "unit": "captions/s", "sweeps": reps,
-            "ms_per_sweep": dt / reps * 1e3, "templates": n_total, "gathered": int(toks.shape[0]), "dtype": dtype,
-            "mean_caption_len": float(lens.float().mean())}
+            "ms_per_sweep": dt / reps * 1e3, "ms_per_step": dt / reps * 1e3, "steps": reps, "warmup": args.warmup,
+            "templates": n_total, "gathered": int(toks.shape[0]), "dtype": dtype, "mean_caption_len": float(lens.float().mean()), "outputs": last_outputs((toks, lens))}
 
 
 def run_shard(args, dev, dtype):
@@ -688,7 +722,7 @@ def run_shard(args, dev, dtype):
                 step(-1 - w)
             with hip.profile() as prof:
                 step(0)
-            dt, _ = timed_region(step, steps, 1, dev)
+            dt, out = timed_region(step, steps, 1, dev)
         bd = prof.summary()
         by_entry = {}
         for k, v in bd.items():
@@ -697,12 +731,12 @@ def run_shard(args, dev, dtype):
             e[0] += v["calls"]; e[1] += v["ms"]
         launches = sum(v["calls"] for v in bd.values())
         return dt / steps, {"launches_per_step": launches,
-                            "event_timed_ms_per_step": {k: [c, round(ms, 3)] for k, (c, ms) in sorted(by_entry.items(), key=lambda kv: -kv[1][1])}}
+                            "event_timed_ms_per_step": {k: [c, round(ms, 3)] for k, (c, ms) in sorted(by_entry.items(), key=lambda kv: -kv[1][1])}}, out
 
-    t_shard, bd_shard = timed(lo, hi, args.steps, args.warmup)
+    t_shard, bd_shard, payload = timed(lo, hi, args.steps, args.warmup)
     full_n = n_total if wl == "c5" else args.batch            # C2 / C3 are weak scaling: the 1-GPU workload IS one shard
     if wl == "c5" and not args.shard_only:
-        t_full, bd_full = timed(0, n_total, max(2, args.steps // 2), 1)
+        t_full, bd_full, _ = timed(0, n_total, max(2, args.steps // 2), 1)
     else:
         t_full, bd_full = t_shard, None
     res = {"workload": workload_name(wl), "dtype": dtype,
@@ -719,6 +753,7 @@ def run_shard(args, dev, dtype):
     if bd_full is not None:
         res["one_gpu"]["breakdown"] = bd_full
     res["options"] = {k: v[0] for k, v in hip.options().items()}
+    res["outputs"] = {"payload": payload.cpu()}          # the shard's [cap, T + 1] ids + lengths as exchanged in its last timed step
     return res
 
 
@@ -747,19 +782,26 @@ def run_score(args, rank, world, dev, dtype, kind):
         return score_sharded(lambda lo, hi: score_captions(model, images, tpl[lo:hi], caps[lo:hi], lengths_d[lo:hi], batch_size=args.score_batch), n_total)
 
     from deephumor_amd import hip
-    pp = run()
-    with hip.profile() as prof0:                          # untimed instrumented pass: which launch key dominates the pass
-        run()
-    breakdown = prof0.summary()
-    dominant = max(breakdown, key=lambda k: breakdown[k]["ms"])
+    for _ in range(max(1, args.warmup)):
+        pp = run()
     reps = max(1, args.steps)
-    stride = max(1, breakdown[dominant]["calls"] // 32)
-    with hip.profile(watch={dominant}, stride=stride) as prof:       # events around the dominant key's launches inside the timed region
+    if not args.full:                                     # the timed passes alone (no instrumented pass, no events, no CPU leg)
         dt, pp = timed_region(lambda s: run(), reps, world, dev)
-    summary = prof.summary()
+    else:
+        with hip.profile() as prof0:                      # untimed instrumented pass: which launch key dominates the pass
+            run()
+        breakdown = prof0.summary()
+        dominant = max(breakdown, key=lambda k: breakdown[k]["ms"])
+        stride = max(1, breakdown[dominant]["calls"] // 32)
+        with hip.profile(watch={dominant}, stride=stride) as prof:   # events around the dominant key's launches inside the timed region
+            dt, pp = timed_region(lambda s: run(), reps, world, dev)
+        summary = prof.summary()
     res = {"workload": f"teacher-forced scoring, {kind_of(kind)}, 300 templates x 30 captions x 32 tokens, V={V_WORD}",
            "value": n_total * reps / dt, "unit": "captions scored/s", "passes": reps, "ms_per_pass": dt / reps * 1e3,
-           "captions": n_total, "mean_perplexity": float(pp.float().mean()), "dtype": dtype}
+           "ms_per_step": dt / reps * 1e3, "steps": reps, "warmup": args.warmup,
+           "captions": n_total, "mean_perplexity": float(pp.float().mean()), "dtype": dtype, "outputs": {"perplexity": pp.cpu()}}
+    if not args.full:
+        return res
     res["roofline"] = price(dominant, (summary if dominant in summary else breakdown)[dominant], dtype)
     res["roofline"]["measured"] = f"timed region, every {stride}th launch" if dominant in summary else "instrumented pass"
     by_entry = {}
@@ -821,6 +863,31 @@ def git_head():
             return f.read().strip() or None
     except OSError:
         return None
+
+
+def dump_outputs(out_dir, outputs):
+    """``--dump-outputs DIR``: one ``DIR/<name>.npy`` per array the timed path returned in its last step -- integers as float64
+    (exact), floating-point values as float32 -- so that two builds can be compared output for output on the same seeded inputs.
+    Above DUMP_CAP_BYTES in all, every array with rows keeps the same fraction of them, a fixed, seeded sample (the same rows for
+    arrays of the same row count), with the kept row indices in ``DIR/<name>_rows.npy``; 0-d arrays are kept whole."""
+    import numpy as np
+    arrays = {k: v.numpy().astype(np.float64 if not v.is_floating_point() or v.dtype == torch.float64 else np.float32)
+              for k, v in outputs.items()}
+    if sum(a.nbytes for a in arrays.values()) > DUMP_CAP_BYTES:
+        whole = sum(a.nbytes for a in arrays.values() if a.ndim == 0)
+        per_all_rows = sum(a.nbytes + 8 * a.shape[0] for a in arrays.values() if a.ndim)   # (a row's index costs 8 bytes)
+        frac = (DUMP_CAP_BYTES - whole) / per_all_rows
+        sampled = {}
+        for k, a in arrays.items():
+            if a.ndim == 0:
+                sampled[k] = a
+                continue
+            rows = np.sort(np.random.default_rng(0).choice(a.shape[0], size=int(a.shape[0] * frac), replace=False))
+            sampled[k], sampled[f"{k}_rows"] = a[rows], rows.astype(np.float64)
+        arrays = sampled
+    os.makedirs(out_dir, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(out_dir, f"{k}.npy"), a)
 
 
 def free_port():
@@ -895,7 +962,7 @@ def stub_workload(args, rank, world, dev):
             "shard": [lo, hi], "shard_sizes": [shard_range(n_total, r, world)[1] - shard_range(n_total, r, world)[0] for r in range(world)]
             if args.workload == "c5" else [args.batch] * world,
             "gathered": int(toks.shape[0]), "gather_in_global_order": bool(torch.equal(toks, want)),
-            "mean_caption_len": float(lens.float().mean())}
+            "mean_caption_len": float(lens.float().mean()), "outputs": last_outputs((toks, lens))}
 
 
 def main(argv=None):
@@ -906,8 +973,12 @@ def main(argv=None):
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--batch", type=int, default=256, help="images per GPU (BASELINE configs: 256)")
     ap.add_argument("--workload", choices=["c2", "c3", "both", "c5", "score-c2", "score-c3"], default="both")
-    ap.add_argument("--no-cpu", action="store_true", help="skip the CPU baseline / fp32 parity legs")
-    ap.add_argument("--quick", action="store_true", help="only the timed steps and the roofline (no host-inclusive / CPU legs)")
+    ap.add_argument("--full", action="store_true", help="every leg besides the headline: pipelined / hipGraph / host-inclusive rates, roofline "
+                    "and per-kernel tables, the other precisions and their parity checks, the CPU baselines, the c3 leg of --workload both")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed path returned in its last step as DIR/<name>.npy (float64 / float32)")
+    ap.add_argument("--no-cpu", action="store_true", help="with --full: skip the CPU baseline / fp32 parity legs")
+    ap.add_argument("--quick", action="store_true", help="with --full: only the timed steps and the roofline (no host-inclusive / CPU legs)")
     ap.add_argument("--score-batch", type=int, default=1024, help="captions per teacher-forced batch (score-* workloads)")
     ap.add_argument("--graph", action="store_true", help="replay the step from a captured hipGraph (the in-library event "
                     "profiler of the roofline line needs real launches, so the roofline then comes from the instrumented pass)")
@@ -924,10 +995,14 @@ def main(argv=None):
                          "current batch's decode (deephumor_amd.pipeline.CaptionPipeline); sequential: one batch at a time (the rounds 1-4 headline)")
     ap.add_argument("--stub", action="store_true", help="CPU/gloo control-flow test of the multi-rank path (model stubbed; not a measurement)")
     args = ap.parse_args(argv)
+    if (args.quick or args.no_cpu) and not args.full:
+        ap.error("--quick and --no-cpu select among the --full legs; a plain run has none to skip: add --full or drop them")
     if args.dtype is None:
         args.dtype = "f16" if args.workload == "c5" else "bf16"
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
+        if args.dump_outputs:                             # (the ranks run from the repository root)
+            argv += ["--dump-outputs", os.path.abspath(args.dump_outputs)]
         return launch_ranks(args, argv)                   # before anything touches a GPU
     rank = int(os.environ.get("RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -957,7 +1032,9 @@ def main(argv=None):
             dist.init_process_group("nccl", rank=rank, world_size=world, device_id=dev)
         n_ranks_seen = dist.get_world_size()
 
-    def finish(line):
+    def finish(line, outputs):
+        if rank == 0 and args.dump_outputs:
+            dump_outputs(args.dump_outputs, outputs)
         line["n_ranks_seen"] = n_ranks_seen          # what the process group itself reports (RCCL saw N ranks)
         line["ranks_launched_by"] = launched_by
         if single_pg:
@@ -976,34 +1053,39 @@ def main(argv=None):
 
     if args.stub:
         res = stub_workload(args, rank, world, dev)
+        outputs = res.pop("outputs")
         c5 = args.workload == "c5"
         return finish(dict(res, metric="captions/sec (224x224, 32-tok, beam=10, 300-template sweep)" if c5 else "captions/sec (224x224, 32-tok, beam=5)",
                            unit="captions/s", n_gpus=world, steps=args.steps, warmup=args.warmup, higher_is_better=True,
                            scaling="strong" if c5 else "weak", vs_baseline=None, dtype="none", data="stub",
-                           config={"workload": "STUB: control flow only, no model, CPU/gloo" + (" (C5 partitioning: 300 templates, uneven shards)" if c5 else "")}))
+                           config={"workload": "STUB: control flow only, no model, CPU/gloo" + (" (C5 partitioning: 300 templates, uneven shards)" if c5 else "")}),
+                      outputs)
 
     if args.shard_of:
         if world != 1 or not 0 <= args.shard_rank < args.shard_of or args.workload.startswith("score-"):
             print("bench.py: --shard-of needs --gpus 1, 0 <= --shard-rank < --shard-of and a decode workload", file=sys.stderr)
             return 2
         res = run_shard(args, dev, args.dtype)
+        outputs = res.pop("outputs")
         wl = {"both": "c2"}.get(args.workload, args.workload)
         return finish(dict(res, metric="captions/sec of ONE rank's shard on one GPU + projected whole-job rate (see projection.label)",
                            value=res["shard"]["images"] / (res["shard"]["shard_ms"] / 1e3), unit="captions/s", n_gpus=1, steps=args.steps,
                            warmup=args.warmup, ms_per_step=res["shard"]["shard_ms"], higher_is_better=True, scaling=res["projection"]["scaling"],
                            vs_baseline=None, data="synthetic",
                            config={"workload": workload_name(wl), "shard_of": args.shard_of, "shard_rank": args.shard_rank,
-                                   "vocab": V_WORD, "max_len": MAX_LEN, "top_k": TOP_K, "commit": git_head()}))
+                                   "vocab": V_WORD, "max_len": MAX_LEN, "top_k": TOP_K, "commit": git_head()}), outputs)
     if args.workload.startswith("score-"):
         res = run_score(args, rank, world, dev, args.dtype, args.workload.split("-")[1])
+        outputs = res.pop("outputs")
         return finish(dict(res, metric="captions scored/sec (teacher-forced perplexity, 32 tokens)", n_gpus=world,
-                           higher_is_better=True, scaling="strong", vs_baseline=None, data="synthetic"))
+                           higher_is_better=True, scaling="strong", vs_baseline=None, data="synthetic"), outputs)
     if args.workload == "c5":
         res = run_c5(args, rank, world, dev, args.dtype)
+        outputs = res.pop("outputs")
         return finish(dict(res, metric="captions/sec (224x224, 32-tok, beam=10, 300-template sweep)", n_gpus=world,
                            higher_is_better=True, scaling="strong", vs_baseline=None, data="synthetic",
                            config={"workload": workload_name("c5"), "beam_size": 10, "top_k": TOP_K, "vocab": V_WORD,
-                                   "parallelism": f"templates sharded x{world} (uneven shards), one padded all_gather of ids"}))
+                                   "parallelism": f"templates sharded x{world} (uneven shards), one padded all_gather of ids"}), outputs)
     main_wl = "c2" if args.workload in ("c2", "both") else "c3"
     with_cpu = (world == 1) and not args.no_cpu and not args.quick
     res = run_workload(main_wl, args, rank, world, dev, args.steps, args.warmup, with_cpu, args.dtype)
@@ -1018,7 +1100,7 @@ def main(argv=None):
                    "weights": "synthetic name-keyed (seed 1234)", "encoder_in_timed_region": True,
                    "inputs": "device-resident fp32 NCHW images (host-inclusive rates under host_inclusive)",
                    "hipgraph": bool(args.graph), "commit": git_head()},
-        "roofline": res["roofline"], "cpu_baseline": res.get("cpu_baseline"),
+        **({"roofline": res["roofline"], "cpu_baseline": res.get("cpu_baseline")} if args.full else {}),
         # which rate `value` is: the bench contract's (inputs already resident in HBM when the timed region starts; a PCIe-inclusive rate
         # is never `value`).  SURVEY 8(d) / BASELINE.md section 3 define the metric host images -> host ids: that one is
         # `value_host_inclusive` (pipelined, decoded uint8 images in pinned memory) with its ratio to `value` next to it
@@ -1027,7 +1109,9 @@ def main(argv=None):
                      "stream (round 5's `value`): value_pipelined; host -> host (SURVEY 8(d)): value_host_inclusive.  speedup_vs_cpu = value / "
                      "cpu_baseline.value.  Top-level workload = BASELINE.json configs[1] (C2, the configuration the metric is quoted on that fits "
                      "one GPU -- the bench contract's rule); C3, the Transformer configuration north_star's roofline target names, is the nested "
-                     "`c3` object with the same keys",
+                     "`c3` object with the same keys" if args.full else
+                     "device-resident fp32 NCHW images -> token ids on the device (bench contract), ONE BATCH AT A TIME (= value_sequential); "
+                     "top-level workload = BASELINE.json configs[1] (C2); the pipelined, hipGraph, host-inclusive, CPU and c3 figures: --full",
     }
     line["config"]["schedule"] = res.get("schedule")
     line["value_sequential"] = res["sequential"]["value"]
@@ -1035,8 +1119,9 @@ def main(argv=None):
         line["value_pipelined"] = res["pipelined"]["value"]
         line["ms_per_step_pipelined"] = res["pipelined"]["ms_per_step"]
         line["pipelined_schedule"] = res["pipelined"]["schedule"]
-    line["whole_step"] = res["whole_step"]
-    line["whole_step_mfma_frac"] = res["whole_step"]["mfma_frac"]
+    if "whole_step" in res:
+        line["whole_step"] = res["whole_step"]
+        line["whole_step_mfma_frac"] = res["whole_step"]["mfma_frac"]
     for k in ("greedy_token_match_vs_cpu_ref", f"greedy_token_match_{args.dtype}_vs_cpu_ref", "precision_vs_fp32_hip", "speedup_vs_cpu", "pipelined_device_resident",
               "mean_caption_len", "fp32_parity_path", "parity_grade_path", "f16_path", "bf16_path", "host_inclusive", "hipgraph_replay", "kernel_breakdown_ms_per_step", "kernel_breakdown_note",
               "encoder_layers", "roofline_self_attention", "roofline_cross_attention", "roofline_decoder_attention_combined"):
@@ -1068,11 +1153,12 @@ def main(argv=None):
         line["value_host_inclusive_over_value"] = hi["u8_hwc"]["pipelined"]["value"] / res["value"]
         line["value_host_inclusive_def"] = ("uint8 HWC 224x224 images in pinned host memory -> token ids in pinned host memory, pipelined "
                                             "(CaptionPipeline + u8_preprocess); the fp32 NCHW form is under host_inclusive.f32_nchw")
-    if args.workload == "both":
+    if args.workload == "both" and args.full:
         r3 = run_workload("c3", args, rank, world, dev, max(3, args.steps // 2), 1, with_cpu, args.dtype, main_line=False)
         r3.pop("encoder_layers", None)
+        r3.pop("outputs")
         line["c3"] = dict(r3, workload=workload_name("c3") + ", same batch/beam settings", unit="captions/s")
-    return finish(line)
+    return finish(line, res["outputs"])
 
 
 if __name__ == "__main__":

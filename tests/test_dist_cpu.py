@@ -236,6 +236,49 @@ def test_bench_rejects_mismatched_world_size(monkeypatch, capfd):
     assert "WORLD_SIZE=4" in capfd.readouterr().err
 
 
+@pytest.mark.parametrize("flag", ["--quick", "--no-cpu"])
+def test_bench_refuses_full_only_flags_without_full(flag, capfd):
+    """--quick / --no-cpu choose among the --full legs: without --full they are refused, not silently ignored."""
+    import sys
+    sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+    import bench
+    with pytest.raises(SystemExit) as e:
+        bench.main(["--gpus", "1", "--stub", flag])
+    assert e.value.code == 2 and "--full" in capfd.readouterr().err
+
+
+def test_bench_dump_outputs_are_the_last_timed_step(monkeypatch, capfd, tmp_path):
+    """``--dump-outputs DIR`` through two launched ranks (model stubbed): the gathered ids and lengths of the LAST timed step, as float64,
+    written once; above the size cap every array keeps the same fraction of its rows, a seeded sample listed in <name>_rows.npy."""
+    import json
+    import sys
+    import numpy as np
+    sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+    import bench
+    for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT", "DH_BENCH_LAUNCHED_BY"):
+        monkeypatch.delenv(k, raising=False)
+    monkeypatch.chdir(tmp_path)
+    assert bench.main(["--gpus", "2", "--steps", "4", "--warmup", "1", "--batch", "5", "--stub", "--dump-outputs", "out"]) == 0
+    assert json.loads(capfd.readouterr().out.strip().splitlines()[-1])["steps_run"] == [0, 1, 2, 3]
+    toks, lens = np.load(tmp_path / "out" / "tokens.npy"), np.load(tmp_path / "out" / "lengths.npy")
+    idx = np.arange(10)
+    assert toks.dtype == lens.dtype == np.float64 and sorted(os.listdir(tmp_path / "out")) == ["lengths.npy", "tokens.npy"]
+    assert np.array_equal(toks, (idx[:, None] * 10 + np.arange(bench.MAX_LEN)[None, :] + 3) % 97)
+    assert np.array_equal(lens, idx % bench.MAX_LEN + 1)
+
+    monkeypatch.setattr(bench, "DUMP_CAP_BYTES", 4096)
+    big = {"tokens": torch.arange(200 * 32).view(200, 32), "scores": torch.rand(200, dtype=torch.float16),
+           "wide": torch.rand(50, 64, dtype=torch.float64), "total": torch.tensor(7)}
+    bench.dump_outputs(str(tmp_path / "big"), big)
+    got = {f[:-4]: np.load(tmp_path / "big" / f) for f in os.listdir(tmp_path / "big")}
+    assert sorted(got) == ["scores", "scores_rows", "tokens", "tokens_rows", "total", "wide", "wide_rows"]
+    assert sum(a.nbytes for a in got.values()) <= 4096 and got["scores"].dtype == np.float32 and got["total"] == 7
+    assert np.array_equal(got["tokens_rows"], got["scores_rows"]) and 0 < len(got["tokens_rows"]) < 200 and 0 < len(got["wide_rows"]) < 50
+    for k in ("tokens", "scores", "wide"):
+        rows = got[f"{k}_rows"].astype(np.int64)
+        assert np.array_equal(got[k], big[k].numpy().astype(got[k].dtype)[rows]), k
+
+
 def _single_worker(rank, world, port, ret):
     os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
     dist.init_process_group("gloo", rank=0, world_size=1, timeout=datetime.timedelta(seconds=120))

@@ -54,13 +54,29 @@ def test_sharded_generate_through_one_rank_rccl():
     assert res == {"backend": "nccl", "ids": True, "rows": True, "timed_out": 3, "dt_ok": True, "rank_times": True}
 
 
-def test_bench_rccl_single_line():
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--rccl-single", "--quick", "--workload", "c2", "--batch", "32",
-                        "--steps", "2", "--warmup", "1"], capture_output=True, text=True, timeout=900, cwd=ROOT)
+def _bench_rccl_single(*extra):
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--rccl-single", "--workload", "c2", "--batch", "32",
+                        "--steps", "2", "--warmup", "1", *extra], capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert p.returncode == 0, p.stderr[-2000:]
     line = json.loads([l for l in p.stdout.splitlines() if l.strip()][-1])      # the LAST stdout line (RCCL's banner must not follow it)
     assert line["n_ranks_seen"] == 1 and "rccl_single_rank" in line and line["value"] > 0
     assert line["per_rank_ms_per_step"]["ranks"] == 1 and line["per_rank_ms_per_step"]["max"] == pytest.approx(line["ms_per_step"])
+    return line
+
+
+def test_bench_rccl_single_line(tmp_path):
+    """The whole --full line through a one-rank RCCL group (instrumented pass, event-timed sequential region, pipelined region with
+    asynchronous all_gathers, hipGraph replay), then the plain run through the same group: both write the last timed step's gathered
+    ids and lengths (--dump-outputs), and with the same seeds they are the same."""
+    import numpy as np
+    line = _bench_rccl_single("--full", "--quick", "--dump-outputs", str(tmp_path / "full"))
+    assert "roofline" in line and "value_pipelined" in line and "value_hipgraph_replay" in line
+    toks, lens = np.load(tmp_path / "full" / "tokens.npy"), np.load(tmp_path / "full" / "lengths.npy")
+    assert toks.shape == (32, 32) and lens.shape == (32,) and lens.mean() == pytest.approx(line["mean_caption_len"])
+    assert ((toks >= 0) & (toks < 36541)).all() and ((lens >= 1) & (lens <= 32)).all()
+    plain = _bench_rccl_single("--dump-outputs", str(tmp_path / "plain"))
+    assert "roofline" not in plain and "value_pipelined" not in plain
+    assert np.array_equal(np.load(tmp_path / "plain" / "tokens.npy"), toks) and np.array_equal(np.load(tmp_path / "plain" / "lengths.npy"), lens)
 
 
 GRAPH_CHILD = r"""
