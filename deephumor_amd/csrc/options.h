@@ -22,7 +22,8 @@ enum DhOption {
     DH_OPT_DEFERRED_LN,              // deferred-LayerNorm decode chain (0: LayerNorm launches between the GEMMs)
     DH_OPT_PACKED_CROSS,             // matrix-core cross-attention on packed K / V^T tiles (0: the LDS kernel)
     DH_OPT_ENCODER_GENERIC,          // 0: every specialised encoder kernel; 1: round-3 set (no streaming 1x1 / stage-1,2,4 tails / conv1 fusions);
-                                     // 2: everything through the implicit-GEMM tile kernel (the reference point of the bit-identity A/B tests)
+                                     // 2: every bottleneck convolution through the implicit-GEMM tile kernel (the reference point of the
+                                     // bit-identity A/B tests); 3: also the implicit-GEMM stem (another summation order: not bit-equal)
     DH_OPT_DIST_ALWAYS,              // a one-rank process group still runs its collectives (bench.py --rccl-single, tests)
     DH_OPT_DECODE_STREAMS,           // HIP streams a batch's decode is interleaved over (1)
     DH_OPT_COUNT

@@ -6,7 +6,7 @@ parameter containers -- the arithmetic runs in ``libdeephumor_hip.so`` (``deephu
 batched over images.  Inference only: like the reference's ``generate`` callers
 (deephumor_demo.ipynb:1134-1141) the model must be in ``eval()`` mode.
 """
-import os
+from collections import namedtuple
 
 import torch
 from torch import nn
@@ -106,6 +106,117 @@ class _Planned:
         return self._plan_cache[1]
 
 
+# One bottleneck of the 16-bit trunk's schedule: the kernel of each convolution, by its ``hip`` function's name -- conv1 None when the
+# previous launch computed it; a fused tail is named as both conv2 and conv3; conv3 of a stage's first block includes the downsample
+# (the dual GEMM) -- and whether this launch also computes the next bottleneck's conv1 (``fuse``).
+Step = namedtuple("Step", "conv1 conv2 conv3 fuse")
+
+TILE = "conv2d_nhwc_bn_act"          # the implicit-GEMM tile kernel: every convolution's reference point
+
+
+def _schedule(bottlenecks, shape, packed, level):
+    """The kernels of the 16-bit trunk for images of ``shape`` (``packed``: [N, H, W, 8], else [N, 3, H, W]) at option
+    ``encoder_generic`` = ``level``: ``(stem kernel, [Step per bottleneck])``.  It reads shapes only -- the weights' channel counts and
+    strides, the input size -- and the host-side ``hip.*_supported`` predicates, so it runs without a GPU.  Every specialised kernel's
+    condition is here, once; level >= 1 switches off the register-streamed kernels (conv1x1_wreg, conv1x1_dual_wreg, conv3x3_s4, the
+    stage-1 / 2 tails) and every conv1 fusion, >= 2 also the stage-3 tail, the ring tail and conv3x3_direct (each of them bit-identical
+    to the tile kernel), >= 3 also the one-launch stems (another summation order: close, not bit-equal)."""
+    n, h, w = (shape[0], shape[1], shape[2]) if packed else (shape[0], shape[2], shape[3])
+    ho, wo = (h - 1) // 2 + 1, (w - 1) // 2 + 1                  # the stem convolution (7 x 7, stride 2, pad 3)
+    if level >= 3 or ho % 2 or wo % 2:
+        stem = TILE                                              # + maxpool3x3s2_nhwc
+    elif h >= 2 and w >= 2:
+        stem = "stem_conv7_bn_relu_maxpool"
+    else:
+        stem = "conv2d_nhwc_bn_relu_maxpool"
+    h, w = (ho - 1) // 2 + 1, (wo - 1) // 2 + 1                   # the max-pool (3 x 3, stride 2, pad 1)
+    steps = []
+    for i, b in enumerate(bottlenecks):
+        nxt = bottlenecks[i + 1] if i + 1 < len(bottlenecks) else None
+        n1 = nxt.conv1.weight.shape[0] if nxt is not None and nxt.downsample is None else 0      # a conv1 this block's launch may fuse
+        cin, c, s = b.conv1.weight.shape[1], b.conv2.weight.shape[0], b.conv2.stride[0]
+        ho, wo = (h - 1) // s + 1, (w - 1) // s + 1
+        if steps and steps[-1].fuse:
+            conv1 = None
+        else:
+            conv1 = "conv1x1_wreg_nhwc" if level < 1 and hip.conv1x1_wreg_supported(n * h * w, cin, c) else TILE
+        if b.downsample is None and level < 1 and n1 and hip.bottleneck_tail_s1_supported(h, w, c, n1):
+            # stage 1 (56 x 56 x 64): 4-row strips, weights register-streamed, and the next block's conv1 on the output tile while it is
+            # in LDS -- the 411 MB tensor is not read back for it (conv_s1.hip; without the fusion the ring tail is the faster one)
+            steps.append(Step(conv1, "bottleneck_tail_s1_nhwc", "bottleneck_tail_s1_nhwc", True))
+        elif b.downsample is None and level < 2 and hip.bottleneck_tail_s3_supported(h, w, c):
+            # stage 3 (14 x 14 x 256): one image per workgroup, patch-resident 3x3 + 1x1 expansion, weights register-streamed
+            steps.append(Step(conv1, "bottleneck_tail_s3_nhwc", "bottleneck_tail_s3_nhwc", False))
+        elif b.downsample is None and level < 1 and hip.bottleneck_tail_s2_supported(h, w, c):
+            # stage 2 (28 x 28 x 128), three workgroups per CU (conv_s2.hip); + the next block's conv1 (512 -> 128) on the output
+            # chunks in LDS: 170 us against 135 + 55 us
+            steps.append(Step(conv1, "bottleneck_tail_s2_nhwc", "bottleneck_tail_s2_nhwc", n1 > 0))
+        elif b.downsample is None and level < 2 and hip.conv3x3_direct_supported(h, w, c, c):
+            # the ring tail: conv2 + bn2 + relu + conv3 + bn3 + residual + relu in one launch, the conv2 output tile stays in LDS
+            steps.append(Step(conv1, "bottleneck_tail_nhwc", "bottleneck_tail_nhwc", False))
+        else:
+            if b.downsample is None and level < 1 and hip.conv3x3_s4_supported(h, w, c):
+                conv2 = "conv3x3_s4_nhwc"        # stage 4: two images x half of the channels per workgroup, weights register-streamed
+            elif s == 1 and level < 2 and hip.conv3x3_direct_supported(h, w, c, c):
+                conv2 = "conv3x3_direct_nhwc"    # patch-resident direct convolution (stages 1-2)
+            else:
+                conv2 = TILE
+            fuse = False
+            if b.downsample is not None:
+                # conv3 + downsample as one GEMM (the dual); stage 1's also runs the next block's conv1 (its 256 outputs are in the workgroup)
+                k, cout = b.conv3.weight.shape[1] + b.downsample[0].weight.shape[1], b.conv3.weight.shape[0]
+                if level < 1 and hip.conv1x1_dual_wreg_supported((n, ho, wo, c), (n, h, w, cin), cout):
+                    conv3, fuse = "conv1x1_dual_wreg_nhwc", (k, cout, n1) == (128, 256, 64)
+                else:
+                    conv3 = "conv1x1_dual_nhwc"
+            elif level < 1 and c == 512 and hip.conv1x1_wreg_supported(n * h * w, c, b.conv3.weight.shape[0]):
+                conv3 = "conv1x1_wreg_nhwc"          # stage 4's conv3 + residual (the kernel's residual form takes Cin = 512)
+            else:
+                conv3 = TILE
+            steps.append(Step(conv1, conv2, conv3, fuse))
+        h, w = ho, wo
+    return stem, steps
+
+
+def _conv_launch(name, c):
+    """f(x, residual=None): convolution ``c`` of a plan on the kernel ``name``."""
+    if name == "conv1x1_wreg_nhwc":
+        # weights stationary in registers, pixels streamed (csrc/conv1x1_wreg.hip)
+        return lambda x, r=None: hip.conv1x1_wreg_nhwc(x, c["pk"], c["w"].shape[0], c["scale"], c["shift"], relu=c["relu"], residual=r)
+    if name == "conv3x3_s4_nhwc":
+        return lambda x, r=None: hip.conv3x3_s4_nhwc(x, c["pk"], c["scale"], c["shift"])
+    if name == "conv3x3_direct_nhwc":
+        return lambda x, r=None: hip.conv3x3_direct_nhwc(x, c["w"], c["scale"], c["shift"])
+    assert name == TILE, name
+    return lambda x, r=None: hip.conv2d_nhwc_bn_act(x, c["w"], c["scale"], c["shift"], residual=r, relu=c["relu"], stride=c["stride"],
+                                                    pad=c["pad"])
+
+
+def _block_launch(blk, n1, step):
+    """step(x, y1_ready) -> (x, y1_for_next_block): bottleneck ``blk`` of a plan on the kernels of ``step`` (``n1``: the next block's
+    conv1 when ``step.fuse``)."""
+    c1, c2, c3, d = blk["c1"], blk["c2"], blk["c3"], blk["dual"]
+    conv1 = (lambda x, ready: ready) if step.conv1 is None else (lambda x, ready, f=_conv_launch(step.conv1, c1): f(x))
+    nxt = dict(w1p=n1["pk"], scale1=n1["scale"], shift1=n1["shift"], n1=n1["w"].shape[0]) if step.fuse else {}
+    done = (lambda r: r) if step.fuse else (lambda r: (r, None))                # the fused launches return (out, y1_next)
+    if step.conv2 == "bottleneck_tail_nhwc":
+        return lambda x, ready: (hip.bottleneck_tail_nhwc(conv1(x, ready), c2["w"], c2["scale"], c2["shift"], c3["w"], c3["scale"],
+                                                          c3["shift"], x), None)
+    if step.conv2 in ("bottleneck_tail_s1_nhwc", "bottleneck_tail_s2_nhwc", "bottleneck_tail_s3_nhwc"):      # weights register-streamed
+        tail = getattr(hip, step.conv2)
+        return lambda x, ready: done(tail(conv1(x, ready), c2["pk"], c2["scale"], c2["shift"], c3["pk"], c3["scale"], c3["shift"], x,
+                                          **nxt))
+    conv2 = _conv_launch(step.conv2, c2)
+    if step.conv3 == "conv1x1_dual_wreg_nhwc":
+        end = lambda y, x: done(hip.conv1x1_dual_wreg_nhwc(y, x, d["pk"], d["w"].shape[0], d["shift"], d["stride"], relu=True, **nxt))
+    elif step.conv3 == "conv1x1_dual_nhwc":
+        end = lambda y, x: (hip.conv1x1_dual_nhwc(y, x, d["w"], d["shift"], d["stride"], relu=True), None)
+    else:
+        conv3 = _conv_launch(step.conv3, c3)
+        end = lambda y, x: (conv3(y, x), None)                                 # + the identity residual
+    return lambda x, ready: end(conv2(conv1(x, ready)), x)
+
+
 class ImageEncoder(_Planned, nn.Module):
     """ResNet-50 image encoder (reference encoders.py:7-70).
 
@@ -165,87 +276,43 @@ class ImageEncoder(_Planned, nn.Module):
 
         blocks = []
         stem = conv(self.resnet[0], self.resnet[1], True, stem=True)
-        c1 = self.resnet[0]
-        if bf16 and tuple(c1.weight.shape) == (64, 3, 7, 7) and c1.stride[0] == 2 and c1.padding[0] == 3:
-            stem["wpk"] = hip.pack_stem_weight(c1.weight, wdt)      # the direct-convolution stem kernel's weight layout
-        for stage in list(self.resnet)[4:]:
-            for blk in stage:
-                ent = dict(
-                    down=conv(blk.downsample[0], blk.downsample[1], False) if blk.downsample is not None else None,
-                    c1=conv(blk.conv1, blk.bn1, True), c2=conv(blk.conv2, blk.bn2, True),
-                    c3=conv(blk.conv3, blk.bn3, True, residual=True), dual=None)
-                c1w = ent["c1"]["w"]
-                if (bf16 and c1w.is_cuda and tuple(c1w.shape[1:3]) == (1, 1) and ent["c1"]["stride"] == 1 and c1w.shape[3] in (256, 512, 1024)
-                        and c1w.shape[0] % 128 == 0):
-                    ent["c1"]["wpk1"] = hip.pack_mfma_fragments(c1w.reshape(c1w.shape[0], c1w.shape[3]).contiguous())
-                if bf16 and ent["down"] is not None:
-                    # first block of a stage on the bf16 path: relu(bn3(conv3(y)) + bn_d(downsample(x))) as ONE GEMM over
-                    # [y | x at the strided pixels] with the BatchNorm scales folded into the weights -- the identity
-                    # tensor (411 MB in stage 1 at 256 images) is neither written nor read back
-                    c3, dn = ent["c3"], ent["down"]
-                    cout = c3["w"].shape[0]
-                    w_cat = torch.cat([c3["w"].float().view(cout, -1) * c3["scale"][:, None],
-                                       dn["w"].float().view(cout, -1) * dn["scale"][:, None]], 1)
-                    if c3["w"].shape[-1] % 64 == 0 and dn["w"].shape[-1] % 64 == 0:
-                        ent["dual"] = dict(w=w_cat.to(wdt).contiguous(), shift=(c3["shift"] + dn["shift"]).contiguous(),
-                                           stride=dn["stride"])
-                        if w_cat.is_cuda and w_cat.shape[1] in (128, 384, 768) and cout % 256 == 0:
-                            ent["dual"]["wpk"] = hip.pack_mfma_fragments(ent["dual"]["w"])
-                if (bf16 and ent["down"] is None and ent["c2"]["stride"] == 1 and ent["c2"]["w"].shape[1] == 3
-                        and ent["c3"]["w"].shape[0] == 4 * ent["c2"]["w"].shape[0] and ent["c2"]["w"].shape[0] == ent["c2"]["w"].shape[3]
-                        and hip.bottleneck_tail_s3_supported(14, 14, ent["c2"]["w"].shape[0])):
-                    # stage-3 blocks: the fused tail streams the weights from L2 into registers in MFMA fragment order
-                    ent["w2p"] = hip.pack_mfma_fragments(ent["c2"]["w"])
-                    ent["w3p"] = hip.pack_mfma_fragments(ent["c3"]["w"].reshape(ent["c3"]["w"].shape[0], -1).contiguous())
-                elif (bf16 and ent["c2"]["w"].is_cuda and ent["down"] is None and ent["c2"]["stride"] == 1 and ent["c2"]["w"].shape[1] == 3
-                        and ent["c3"]["w"].shape[0] == 4 * ent["c2"]["w"].shape[0] and ent["c2"]["w"].shape[0] == ent["c2"]["w"].shape[3]
-                        and hip.bottleneck_tail_s1_supported(56, 56, ent["c2"]["w"].shape[0])):
-                    # stage-1 blocks: 4-row strips (conv_s1.hip); this block's conv1 in fragment order too, for the previous tail to run it
-                    ent["w2p1"] = hip.pack_mfma_fragments(ent["c2"]["w"])
-                    ent["w3p1"] = hip.pack_mfma_fragments(ent["c3"]["w"].reshape(ent["c3"]["w"].shape[0], -1).contiguous())
-                    if (tuple(c1w.shape[1:3]) == (1, 1) and ent["c1"]["stride"] == 1 and ent["c1"]["relu"]
-                            and hip.bottleneck_tail_s1_supported(56, 56, ent["c2"]["w"].shape[0], c1w.shape[0]) and c1w.shape[3] == 4 * ent["c2"]["w"].shape[0]):
-                        ent["c1"]["wpkf"] = hip.pack_mfma_fragments(c1w.reshape(c1w.shape[0], c1w.shape[3]).contiguous())
-                elif (bf16 and ent["c2"]["w"].is_cuda and ent["down"] is None and ent["c2"]["stride"] == 1 and ent["c2"]["w"].shape[1] == 3
-                        and ent["c3"]["w"].shape[0] == 4 * ent["c2"]["w"].shape[0] and ent["c2"]["w"].shape[0] == ent["c2"]["w"].shape[3]
-                        and hip.bottleneck_tail_s2_supported(28, 28, ent["c2"]["w"].shape[0])):
-                    # stage-2 blocks: the same structure on 4-row strips, three workgroups per CU (conv_s2.hip)
-                    ent["w2p2"] = hip.pack_mfma_fragments(ent["c2"]["w"])
-                    ent["w3p2"] = hip.pack_mfma_fragments(ent["c3"]["w"].reshape(ent["c3"]["w"].shape[0], -1).contiguous())
-                    if (tuple(c1w.shape[1:3]) == (1, 1) and ent["c1"]["stride"] == 1 and ent["c1"]["relu"] and tuple(c1w.shape[::3]) == (128, 512)):
-                        ent["c1"]["wpkf"] = hip.pack_mfma_fragments(c1w.reshape(128, 512).contiguous())     # for the previous tail to run it
-                c3w = ent["c3"]["w"]
-                if (bf16 and c3w.is_cuda and ent["down"] is None and tuple(c3w.shape[1:]) == (1, 1, 512) and c3w.shape[0] % 128 == 0
-                        and c3w.shape[0] // 128 in (1, 2, 4, 8, 16)):
-                    ent["c3"]["wpk1"] = hip.pack_mfma_fragments(c3w.reshape(c3w.shape[0], 512).contiguous())      # stage-4 conv3 + residual
-                c2w = ent["c2"]["w"]
-                if (bf16 and c2w.is_cuda and ent["c2"]["stride"] == 1 and ent["c2"]["pad"] == 1 and tuple(c2w.shape[1:3]) == (3, 3)
-                        and hip.conv3x3_s4_supported(7, 7, c2w.shape[0]) and c2w.shape[3] == c2w.shape[0]):
-                    # stage-4 conv2 (stride 1): two images x half of the channels per workgroup, weights register-streamed (conv_s4.hip)
-                    ent["c2"]["wpk4"] = hip.pack_mfma_fragments(c2w)
-                blocks.append(ent)
+        if bf16:
+            stem["wpk"] = hip.pack_stem_weight(self.resnet[0].weight, wdt)      # the direct-convolution stem kernel's weight layout
+        for blk in self._bottlenecks():
+            ent = dict(
+                down=conv(blk.downsample[0], blk.downsample[1], False) if blk.downsample is not None else None,
+                c1=conv(blk.conv1, blk.bn1, True), c2=conv(blk.conv2, blk.bn2, True),
+                c3=conv(blk.conv3, blk.bn3, True, residual=True), dual=None)
+            if bf16 and ent["down"] is not None:
+                # first block of a stage on the 16-bit path: relu(bn3(conv3(y)) + bn_d(downsample(x))) as ONE GEMM over
+                # [y | x at the strided pixels] with the BatchNorm scales folded into the weights -- the identity
+                # tensor (411 MB in stage 1 at 256 images) is neither written nor read back
+                c3, dn = ent["c3"], ent["down"]
+                cout = c3["w"].shape[0]
+                w_cat = torch.cat([c3["w"].float().view(cout, -1) * c3["scale"][:, None],
+                                   dn["w"].float().view(cout, -1) * dn["scale"][:, None]], 1)
+                ent["dual"] = dict(w=w_cat.to(wdt).contiguous(), shift=(c3["shift"] + dn["shift"]).contiguous(), stride=dn["stride"])
+            if bf16:
+                # ``pk``: the weights in MFMA fragment order, which the register-streamed kernels read -- one copy per weight, chosen by
+                # channel shapes alone (the same at every image size; ``_schedule`` picks the kernels): conv1 with 256 - 1,024 input
+                # channels (conv1x1_wreg; the conv1 a tail or dual launch runs for the block before), conv2 / conv3 of the blocks
+                # without downsample (the fused tails, conv3x3_s4, conv3 + residual on conv1x1_wreg), the dual GEMM's folded weight
+                # up to K = 768 (conv1x1_dual_wreg).  Stage 4's wider layers (Cin 2,048, K = 1,536) stay unpacked.
+                packed = [ent["c1"]] if 256 <= ent["c1"]["w"].shape[3] <= 1024 else []
+                if ent["down"] is None:
+                    packed += [ent["c2"], ent["c3"]]
+                elif ent["dual"]["w"].shape[1] <= 768:
+                    packed.append(ent["dual"])
+                for c in packed:
+                    c["pk"] = hip.pack_mfma_fragments(c["w"].reshape(c["w"].shape[0], -1).contiguous())
+            blocks.append(ent)
         s, b = _bn_affine(self.bn)
         return dict(stem=stem, blocks=blocks, bn_scale=s, bn_shift=b, bf16=bf16, dtype=wdt, split=split,
                     lin_w=self.linear.weight.detach(), lin_b=self.linear.bias.detach().float().contiguous(),
                     lin_wx=hip.split_f32x(self.linear.weight.detach().contiguous()) if split else None)
 
-    @staticmethod
-    def _conv(x, c, residual=None, nhwc=False):
-        if (nhwc and "wpk1" in c and (residual is None or x.shape[3] == 512)
-                and hip.conv1x1_wreg_supported(x.shape[0] * x.shape[1] * x.shape[2], x.shape[3], c["w"].shape[0])
-                and hip.option("encoder_generic") < 1):
-            # conv1 of the K >= 256 bottlenecks, conv3 + residual of stage 4: weights stationary in registers, pixels streamed
-            # (csrc/conv1x1_wreg.hip; bit-identical)
-            return hip.conv1x1_wreg_nhwc(x, c["wpk1"], c["w"].shape[0], c["scale"], c["shift"], relu=c["relu"], residual=residual)
-        if (nhwc and residual is None and "wpk4" in c and c["relu"] and hip.conv3x3_s4_supported(x.shape[1], x.shape[2], x.shape[3])
-                and hip.option("encoder_generic") < 1):
-            return hip.conv3x3_s4_nhwc(x, c["wpk4"], c["scale"], c["shift"])
-        if (nhwc and residual is None and c["relu"] and c["stride"] == 1 and c["pad"] == 1 and c["w"].shape[1] == 3
-                and hip.conv3x3_direct_supported(x.shape[1], x.shape[2], x.shape[3], c["w"].shape[0])
-                and hip.option("encoder_generic") < 2):
-            return hip.conv3x3_direct_nhwc(x, c["w"], c["scale"], c["shift"])      # patch-resident direct convolution (stages 1-2)
-        fn = hip.conv2d_nhwc_bn_act if nhwc else hip.conv2d_bn_act
-        return fn(x, c["w"], c["scale"], c["shift"], residual=residual, relu=c["relu"], stride=c["stride"], pad=c["pad"])
+    def _bottlenecks(self):
+        return [blk for stage in list(self.resnet)[4:] for blk in stage]
 
     TRUNK_MAX_IMAGES = 384
 
@@ -272,12 +339,22 @@ class ImageEncoder(_Planned, nn.Module):
             x = cv(y, blk["c3"], residual=idt)
         return x
 
+    @staticmethod
+    def _features_f32(images, plan):
+        """The parity path: NCHW fp32 tensors, every convolution on the vector ALUs -> [N, 2048, H/32, W/32]."""
+        def cv(x, c, residual=None):
+            return hip.conv2d_bn_act(x, c["w"], c["scale"], c["shift"], residual=residual, relu=c["relu"], stride=c["stride"], pad=c["pad"])
+        x = hip.maxpool3x3s2(cv(images.contiguous(), plan["stem"]))
+        for blk in plan["blocks"]:
+            y = cv(cv(x, blk["c1"]), blk["c2"])
+            x = cv(y, blk["c3"], residual=x if blk["down"] is None else cv(x, blk["down"]))
+        return x
+
     def features(self, images):
         """Trunk output (encoders.py:56): ``[N, 2048, H/32, W/32]`` fp32 on the parity path,
         channels-last ``[N, H/32, W/32, 2048]`` bf16 on the bf16 path."""
         plan = self._get_plan()
         nhwc = plan["bf16"]
-        st = plan["stem"]
         # what torch's conv2d would refuse (the kernels take the layout on trust: a 1- or 4-channel tensor read as 3 channels is foreign
         # memory or garbage, not an error -- round 5 probe)
         if images.dim() != 4:
@@ -292,120 +369,47 @@ class ImageEncoder(_Planned, nn.Module):
                                 "tensor of experiments.inference.preprocess_images")
         if plan["split"]:
             return self._features_split(images, plan)
-        if nhwc and images.shape[0] > self.TRUNK_MAX_IMAGES:
+        if not nhwc:
+            return self._features_f32(images, plan)
+        if images.shape[0] > self.TRUNK_MAX_IMAGES:
             #  the streaming / register-streamed 16-bit kernels index pixels with 32-bit magic divisions and are tuned for
             # <= 256 images per launch (the stage-1 dual kernel stops applying near 436 images): larger batches go through the trunk
             # in chunks of 256 -- every image's arithmetic is independent of its batch, so the features are the same bit for bit
             return torch.cat([self.features(images[i:i + 256]) for i in range(0, images.shape[0], 256)], 0)
-        if nhwc:
-            prepacked = images.dim() == 4 and images.shape[-1] == 8 and images.dtype == plan["dtype"]
-            h_in, w_in = (images.shape[1], images.shape[2]) if prepacked else (images.shape[2], images.shape[3])
-            direct = ("wpk" in st and h_in >= 2 and w_in >= 2 and ((h_in - 1) // 2 + 1) % 2 == 0 and ((w_in - 1) // 2 + 1) % 2 == 0
-                      and (prepacked or images.shape[1] == 3) and hip.option("encoder_generic") < 3)
-            if direct:
-                # conv1 + bn1 + relu + maxpool as ONE direct-convolution launch that reads the caller's tensor as it is (fp32 NCHW
-                # or the preprocessing kernels' packed 16-bit layout): no packing launch, no im2col traffic, no un-pooled activation
-                src = images.contiguous() if prepacked else images.float().contiguous()
-                x = hip.stem_conv7_bn_relu_maxpool(src, st["wpk"], st["scale"], st["shift"])
-                return self._trunk(x, plan)
-            if prepacked:
-                packed = images.contiguous()              # already normalised + packed (experiments.inference.preprocess_images)
-            else:
-                packed = hip.pack_nchw_to_nhwc8(images.float().contiguous(), out_dtype=plan["dtype"])
-            ks, cout = st["w"].shape[1], st["w"].shape[0]
-            ho = (packed.shape[1] + 2 * st["pad"] - ks) // st["stride"] + 1
-            wo = (packed.shape[2] + 2 * st["pad"] - ks) // st["stride"] + 1
-            if ho % 2 == 0 and wo % 2 == 0 and cout <= 64 and hip.option("encoder_generic") < 3:
-                # conv1 + bn1 + relu + maxpool in one launch: the un-pooled 112 x 112 x 64 activation never exists
-                x = hip.conv2d_nhwc_bn_relu_maxpool(packed, st["w"], st["scale"], st["shift"], st["stride"], st["pad"])
-            else:
-                x = hip.maxpool3x3s2_nhwc(self._conv(packed, st, nhwc=True))
-        else:
-            x = hip.maxpool3x3s2(self._conv(images.contiguous(), st))
-        return self._trunk(x, plan)
-
-    def _trunk(self, x, plan):
-        """layer1..layer4 on the pooled stem output: the kernel of every bottleneck is chosen ONCE per (plan, input shape) -- a table of
-        steps kept with the plan (``_trunk_table``) -- and a forward is a walk over that table."""
-        key = (tuple(x.shape), hip.options_epoch)
+        key = (tuple(images.shape), packed_in, hip.options_epoch)
         table = plan.setdefault("_trunk_tables", {}).get(key)
         if table is None:
-            table = plan["_trunk_tables"][key] = self._trunk_table(plan, tuple(x.shape))
-        ready = None                                      # the NEXT block's conv1 output when the previous tail launch computed it
+            table = plan["_trunk_tables"][key] = self._trunk_table(plan, tuple(images.shape), packed_in)
+        x, ready = images, None                           # ready: the NEXT block's conv1 output when the previous launch computed it
         for step in table:
             x, ready = step(x, ready)
         return x
 
-    def _trunk_table(self, plan, shape):
-        """[step(x, y1_ready) -> (x, y1_for_next_block)] for an input of ``shape`` ([N, H, W, C] on the 16-bit paths, NCHW in fp32).
-        Option ``encoder_generic``: 0 = every specialised kernel; >= 1 without round 4's (streaming 1x1, stage-1 / 2 / 4 tails, conv1 fusions);
-        >= 2 also without the patch-resident 3x3 / fused tails of rounds 2-3: every convolution through the implicit-GEMM tile kernel (all
-        of them bit-identical to it: tests/test_bf16_gpu.py)."""
-        nhwc, blocks, lvl = plan["bf16"], plan["blocks"], hip.option("encoder_generic")
-        conv = self._conv
-        table = []
-        h, w = (shape[1], shape[2]) if nhwc else (shape[2], shape[3])
-        for bi, blk in enumerate(blocks):
-            c1, c2, c3 = blk["c1"], blk["c2"], blk["c3"]
-            nxt = blocks[bi + 1] if bi + 1 < len(blocks) else None
-            cmid = c2["w"].shape[0]
-            first = lambda x, ready, c1=c1: ready if ready is not None else conv(x, c1, nhwc=True)
-            if (nhwc and lvl < 1 and "w2p1" in blk and nxt is not None and "wpkf" in nxt["c1"] and "w2p1" in nxt
-                    and hip.bottleneck_tail_s1_supported(h, w, cmid, nxt["c1"]["w"].shape[0])):
-                # stage 1 (56 x 56 x 64), next block's conv1 256 -> 64: 4-row strips, weights register-streamed, and that conv1 in the
-                # same launch on the output tile while it is in LDS -- the 411 MB tensor is not read back for it (conv_s1.hip).
-                # (Without the fusion the ring kernel below is the faster tail in the encoder: 195 against 214 us.)
-                n1 = nxt["c1"]
-                table.append(lambda x, ready, blk=blk, c2=c2, c3=c3, n1=n1, first=first: hip.bottleneck_tail_s1_nhwc(
-                    first(x, ready), blk["w2p1"], c2["scale"], c2["shift"], blk["w3p1"], c3["scale"], c3["shift"], x,
-                    n1["wpkf"], n1["scale"], n1["shift"], n1["w"].shape[0]))
-            elif nhwc and lvl < 2 and "w2p" in blk and hip.bottleneck_tail_s3_supported(h, w, cmid):
-                # stage 3 (14 x 14 x 256): one image per workgroup, patch-resident 3x3 + 1x1 expansion, weights register-streamed
-                table.append(lambda x, ready, blk=blk, c2=c2, c3=c3, first=first: (hip.bottleneck_tail_s3_nhwc(
-                    first(x, ready), blk["w2p"], c2["scale"], c2["shift"], blk["w3p"], c3["scale"], c3["shift"], x), None))
-            elif nhwc and lvl < 1 and "w2p2" in blk and hip.bottleneck_tail_s2_supported(h, w, cmid):
-                if nxt is not None and "wpkf" in nxt["c1"] and "w2p2" in nxt:
-                    # + the next block's conv1 (512 -> 128) on the output chunks in LDS: 170 us against 135 + 55 us
-                    n1 = nxt["c1"]
-                    table.append(lambda x, ready, blk=blk, c2=c2, c3=c3, n1=n1, first=first: hip.bottleneck_tail_s2_nhwc(
-                        first(x, ready), blk["w2p2"], c2["scale"], c2["shift"], blk["w3p2"], c3["scale"], c3["shift"], x,
-                        n1["wpkf"], n1["scale"], n1["shift"], 128))
-                else:
-                    table.append(lambda x, ready, blk=blk, c2=c2, c3=c3, first=first: (hip.bottleneck_tail_s2_nhwc(
-                        first(x, ready), blk["w2p2"], c2["scale"], c2["shift"], blk["w3p2"], c3["scale"], c3["shift"], x), None))
-            elif (nhwc and lvl < 2 and blk["dual"] is None and blk["down"] is None and c2["stride"] == 1 and c2["w"].shape[1] == 3
-                    and hip.conv3x3_direct_supported(h, w, c2["w"].shape[3], cmid) and c3["w"].shape[0] == 4 * cmid):
-                # conv2 + bn2 + relu + conv3 + bn3 + residual + relu in one launch: the conv2 output tile stays in LDS
-                table.append(lambda x, ready, c2=c2, c3=c3, first=first: (hip.bottleneck_tail_nhwc(
-                    first(x, ready), c2["w"], c2["scale"], c2["shift"], c3["w"], c3["scale"], c3["shift"], x), None))
+    def _trunk_table(self, plan, shape, packed):
+        """The 16-bit trunk for images of ``shape`` (``packed``: the [N, H, W, 8] layout) as [step(x, y1_ready) -> (x, y1_for_next_block)]:
+        the stem, then one step per bottleneck, each running the kernels ``_schedule`` picks at the current ``encoder_generic`` level
+        (0 = every specialised kernel; 1 = round 3's set; 2 = every bottleneck convolution through the implicit-GEMM tile kernel -- all
+        three bit-identical; 3 = also the implicit-GEMM stem).  Built once per (shape, options epoch) and kept with the plan: it only
+        binds the plan's tensors, so building it launches nothing (it may happen inside a hipGraph capture)."""
+        stem, steps = _schedule(self._bottlenecks(), shape, packed, hip.option("encoder_generic"))
+        st, blocks = plan["stem"], plan["blocks"]
+        if stem == "stem_conv7_bn_relu_maxpool":
+            # conv1 + bn1 + relu + maxpool as ONE direct-convolution launch that reads the caller's tensor as it is (fp32 NCHW
+            # or the preprocessing kernels' packed 16-bit layout): no packing launch, no im2col traffic, no un-pooled activation
+            table = [lambda x, _: (hip.stem_conv7_bn_relu_maxpool(x.contiguous() if packed else x.float().contiguous(), st["wpk"], st["scale"],
+                                                                  st["shift"]), None)]
+        else:
+            # a packed input is already normalised + packed (experiments.inference.preprocess_images)
+            pack = (lambda x: x.contiguous()) if packed else (lambda x: hip.pack_nchw_to_nhwc8(x.float().contiguous(), out_dtype=plan["dtype"]))
+            if stem == "conv2d_nhwc_bn_relu_maxpool":
+                # conv1 + bn1 + relu + maxpool in one launch: the un-pooled 112 x 112 x 64 activation never exists
+                table = [lambda x, _: (hip.conv2d_nhwc_bn_relu_maxpool(pack(x), st["w"], st["scale"], st["shift"], st["stride"], st["pad"]), None)]
             else:
-                table.append(self._generic_block(blk, nxt, nhwc, lvl))
-            if blk["down"] is not None:
-                st = blk["down"]["stride"]
-                h, w = (h - 1) // st + 1, (w - 1) // st + 1
+                conv = _conv_launch(stem, st)
+                table = [lambda x, _: (hip.maxpool3x3s2_nhwc(conv(pack(x))), None)]
+        for i, (blk, step) in enumerate(zip(blocks, steps)):
+            table.append(_block_launch(blk, blocks[i + 1]["c1"] if step.fuse else None, step))
         return table
-
-    def _generic_block(self, blk, nxt, nhwc, lvl):
-        """conv1 -> conv2 -> (conv3 + downsample as ONE GEMM | downsample, conv3 + residual): the first block of every stage, and every
-        block when the specialised tails do not apply."""
-        conv = self._conv
-
-        def step(x, ready):
-            y1 = ready if ready is not None else conv(x, blk["c1"], nhwc=nhwc)
-            y = conv(y1, blk["c2"], nhwc=nhwc)
-            d = blk["dual"]
-            if d is not None:
-                if "wpk" in d and lvl < 1 and hip.conv1x1_dual_wreg_supported(y.shape, x.shape, d["w"].shape[0]):
-                    if nxt is not None and "wpkf" in nxt["c1"] and d["w"].shape == (256, 128) and nxt["c1"]["w"].shape[0] == 64:
-                        # layer1.0's ending + layer1.1's conv1 in one launch (the block's 256 output channels are in the workgroup)
-                        n1 = nxt["c1"]
-                        return hip.conv1x1_dual_wreg_nhwc(y, x, d["wpk"], 256, d["shift"], d["stride"], relu=True, w1p=n1["wpkf"],
-                                                          scale1=n1["scale"], shift1=n1["shift"], n1=64)
-                    return hip.conv1x1_dual_wreg_nhwc(y, x, d["wpk"], d["w"].shape[0], d["shift"], d["stride"], relu=True), None
-                return hip.conv1x1_dual_nhwc(y, x, d["w"], d["shift"], d["stride"], relu=True), None
-            idt = x if blk["down"] is None else conv(x, blk["down"], nhwc=nhwc)
-            return conv(y, blk["c3"], residual=idt, nhwc=nhwc), None
-        return step
 
     @f32x_guarded
     def forward(self, images):
