@@ -1,21 +1,39 @@
 #!/usr/bin/env bash
-# A deliberately degraded library for the "the gates turn red" check: the register-stationary LSTM step rounds its
-# accumulators to bf16 after every 32-k MFMA step (= a kernel that accumulates in 16 bits).  Built next to the product library;
+# A deliberately degraded library for the "the gates turn red" check.  Built next to the product library;
 # tests select it with DEEPHUMOR_HIP_LIB.
+#   tools/build_degraded_lib.sh [MODE]
+#   lstm          (default) the register-stationary LSTM step rounds its accumulators to bf16 after every 32-k MFMA step
+#                 (= a kernel that accumulates in 16 bits) -> scratch/degraded/libdegraded.so
+#   prefill_tail  the teacher-forced self-attention (attn_self_prefill_kernel) ignores every key j >= 32: the top iteration of
+#                 the fp32 form, the top three of the 16-bit form -> scratch/degraded/libdegraded_prefill_tail.so
 set -e
+MODE=${1:-lstm}
 R=$(cd "$(dirname "$0")/.." && pwd)
 D=$R/scratch/degraded
+case $MODE in
+  lstm) LIB=$D/libdegraded.so ;;
+  prefill_tail) LIB=$D/libdegraded_prefill_tail.so ;;
+  *) echo "unknown mode '$MODE' (lstm | prefill_tail)" >&2; exit 2 ;;
+esac
+rm -rf $D/csrc $D/obj
 mkdir -p $D/csrc $D/obj
 cp $R/deephumor_amd/csrc/* $D/csrc/
-python3 - "$D/csrc/lstm_wreg.hip" <<'PY'
+python3 - "$MODE" "$D/csrc" <<'PY'
 import sys
-p = sys.argv[1]
+mode, d = sys.argv[1:3]
+if mode == "lstm":
+    # 16-bit ACCUMULATION: the accumulator is rounded to bf16 after every 32-k MFMA step
+    p = d + "/lstm_wreg.hip"
+    old = "        acc[i] = Op16<OT>::mfma(wf[f], fa[t % (PF + 1)], acc[i]);"
+    new = ("        acc[i] = Op16<OT>::mfma(wf[f], fa[t % (PF + 1)], acc[i]);\n"
+           "        for (int e_ = 0; e_ < 4; ++e_) acc[i][e_] = bf16_to_f32(f32_to_bf16(acc[i][e_]));")
+else:
+    # keys 32 and later of a position's history get no weight (left out of the softmax and of the value sum)
+    p = d + "/attention.hip"
+    old = "        live[it] = j < L;\n        masked[it] = live[it] && j >= 1 && tokens && aux[it] == pad_index;"
+    new = "        live[it] = j < L && j < 32;\n        masked[it] = live[it] && j >= 1 && tokens && aux[it] == pad_index;"
 s = open(p).read()
-# 16-bit ACCUMULATION: the accumulator is rounded to bf16 after every 32-k MFMA step
-old = "        acc[i] = Op16<OT>::mfma(wf[f], fa[t % (PF + 1)], acc[i]);"
-new = ("        acc[i] = Op16<OT>::mfma(wf[f], fa[t % (PF + 1)], acc[i]);\n"
-       "        for (int e_ = 0; e_ < 4; ++e_) acc[i][e_] = bf16_to_f32(f32_to_bf16(acc[i][e_]));")
-assert old in s
+assert s.count(old) == 1, (mode, p)
 open(p, "w").write(s.replace(old, new))
 PY
 sed -i 's#"../../include/deephumor_hip.h"#"'$R'/include/deephumor_hip.h"#' $D/csrc/common.h
@@ -26,5 +44,5 @@ for f in $D/csrc/*.hip; do
   objs="$objs $o"
 done
 wait
-hipcc --offload-arch=gfx950 -shared -fPIC -o $D/libdegraded.so $objs
-echo built $D/libdegraded.so
+hipcc --offload-arch=gfx950 -shared -fPIC -o $LIB $objs
+echo built $LIB

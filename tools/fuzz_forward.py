@@ -6,6 +6,8 @@ Per trial, random decoder (as tools/fuzz_generate.py), random batch, ragged leng
     multiples of 8 so the 16-bit kernels accept them);
   * ``generate_batch`` of the whole batch vs one call per row with ``img0 = row`` under the same Philox seed (bit-equal ids), on fp32
     and on bf16.
+``--long``: transformer decoders only, head dim 64, captions of 24-56 tokens (most near 40 or 56) with one row free of <pad>,
+so that the prefill attention (40 keys in fp32, 56 in 16 bits) runs its top iterations with live keys.
 TEST INFRASTRUCTURE (imports the oracle).
 
     python tools/fuzz_forward.py --trials 200 --seed 1 > gpurun_out/fuzz_fwd.jsonl
@@ -27,16 +29,20 @@ from oracle import ref_path as R                                                
 
 
 def one_trial(rng, idx):
-    kind = rng.choice(["lstm", "tfm", "tfm_self"])
+    kind = rng.choice(["tfm", "tfm_self"] if LONG else ["lstm", "tfm", "tfm_self"])
     v = rng.choice([rng.randint(5, 70), rng.randint(71, 700), rng.randint(701, 4000)])
     bs = rng.randint(1, 9)
     cap_len = rng.randint(1, 30)
     if BIG:                                               # the product's widths and many rows: the large-batch kernel variants
         bs, cap_len = rng.randint(150, 1400), rng.randint(1, 10)
         v = rng.choice([rng.randint(71, 3000), rng.randint(3001, 9000)])
+    if LONG:                                              # the top iteration of the prefill attention: 40 keys in fp32, 56 in 16 bits
+        cap_len = rng.choice([rng.randint(31, 39), rng.randint(47, 55), rng.randint(24, 56)])
     g = torch.Generator().manual_seed(2000 + idx)
     cap = torch.randint(4, max(v, 5), (bs, cap_len), generator=g).clamp_(max=v - 1)
     lengths = torch.tensor([rng.randint(1, cap_len + 1) for _ in range(bs)])
+    if LONG:
+        lengths[0] = cap_len + 1                          # one row without <pad>: the top history keys are live
     for b in range(bs):                                   # <pad> beyond each caption, as the reference's collate produces
         cap[b, max(int(lengths[b]) - 1, 0):] = 0
     cfg = dict(kind=kind, V=v, bs=bs, cap_len=cap_len, lengths=lengths.tolist())
@@ -54,11 +60,15 @@ def one_trial(rng, idx):
         nl, pf = rng.randint(1, 3), 8 * rng.randint(1, 64)
         if BIG:
             heads, hid, nl, pf = 8, 512, rng.randint(1, 2), rng.choice([2048, 1024])
+        if LONG:                                          # head dim 64: the register-resident prefill attention
+            hid = 64 * heads
         cfg.update(hid=hid, heads=heads, layers=nl, pf=pf)
         cls = TransformerDecoder if kind == "tfm" else SelfAttentionTransformerDecoder
         make = lambda: cls(v, hid_dim=hid, n_layers=nl, n_heads=heads, pf_dim=pf, dropout=0.0, pad_index=0, max_len=64)
         first = torch.randn(bs, hid, generator=g)
         s_len = rng.choice([49, 49, rng.randint(1, 60)])
+        if LONG:                                          # the caption, not the encoder length, sets the sequence length
+            s_len = rng.randint(1, cap_len + 1)
         enc = torch.randn(bs, s_len, hid, generator=g) if kind == "tfm" else None
         if enc is not None:
             # keep |x| away from the fp16 underflow threshold (6e-8): the reference reads a row with ANY exactly-zero element as
@@ -126,17 +136,20 @@ def one_trial(rng, idx):
 
 
 BIG = False
+LONG = False
 
 
 def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--big", action="store_true", help="the product's widths (512) and 150-1400 rows: the large-batch kernel variants")
+    ap.add_argument("--long", action="store_true", help="transformer decoders with head dim 64 and captions of 24-56 tokens: the "
+                    "teacher-forced forward reaches the top iterations of the prefill attention with live keys")
     ap.add_argument("--trials", type=int, default=100)
     ap.add_argument("--seed", type=int, default=1)
     ap.add_argument("--first", type=int, default=0)
     args = ap.parse_args(argv)
-    global BIG
-    BIG = args.big
+    global BIG, LONG
+    BIG, LONG = args.big, args.long
     bad = 0
     worst = {"fp32_max_abs": 0.0, "bf16_max_abs_over_std": 0.0, "f16_max_abs_over_std": 0.0}
     for i in range(args.first, args.first + args.trials):
