@@ -109,7 +109,7 @@ __global__ __launch_bounds__(1024) void attn_decode_kernel(AttnParams<T> p) {
                 kp = p.knew + (size_t)rc * p.ldnew + h * dh;
             }
             ph[j] = phys;
-            masked = (j >= 1) && (p.tokens[(size_t)rl * p.tok_ld + j - 1] == p.pad_index);
+            masked = (j >= 1) && p.tokens && (p.tokens[(size_t)rl * p.tok_ld + j - 1] == p.pad_index);
         }
         float e = -1e8f;
         if (!masked) {
@@ -201,7 +201,7 @@ __global__ __launch_bounds__(1024) void attn_decode_fast_kernel(AttnParams<T> p)
                 } else {
                     kp = p.knew + (size_t)rc * p.ldnew + h * DH;
                 }
-                masked = (j >= 1) && (p.tokens[(size_t)rl * p.tok_ld + j - 1] == p.pad_index);
+                masked = (j >= 1) && p.tokens && (p.tokens[(size_t)rl * p.tok_ld + j - 1] == p.pad_index);
             }
             float kk[8];
             load8(kp + dc * 8, kk);

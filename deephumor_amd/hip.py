@@ -689,9 +689,10 @@ def add_layernorm(x, y, gamma, beta, out=None, eps=1e-5):
 
 def attn_self_decode(qkv, kcache, vcache, src, tokens, out, n_img, rows_per_img, row_mult, rows_total, t, d,
                      n_heads, scale, pad_index):
+    """``tokens=None`` (no pad masking; needs ``pad_index < 0`` beyond ``t = 0``) passes a null pointer."""
     _dev(qkv, kcache, vcache, src, tokens, out)
     _launch("dh_attn_self_decode", _ptr(qkv), _ptr(kcache), _ptr(vcache), _ptr(src), src.stride(0),
-                                      _ptr(tokens), tokens.stride(0), _ptr(out), n_img, rows_per_img, row_mult,
+                                      _ptr(tokens), 0 if tokens is None else tokens.stride(0), _ptr(out), n_img, rows_per_img, row_mult,
                                       rows_total, t, d, n_heads, float(scale), pad_index, _dt(qkv), _stream())
     return out
 

@@ -305,8 +305,9 @@ def test_forward_prefill_equals_position_by_position(kind, bf16, images):
 @pytest.mark.parametrize("kind", ["CaptioningTransformerBase", "CaptioningTransformer"])
 def test_long_caption_uses_the_long_history_kernels(kind, images):
     """max_len = 64 (> the 40 / 56 keys the register-resident attention kernels hold): greedy ids of the fp32 path
-    still equal the CPU oracle's, and the bf16 path runs a longer caption still (100).  (The oracle re-runs the whole sequence per
-    token: 64 positions cost a third of what 100 did.)"""
+    still equal the CPU oracle's.  The bf16 path only RUNS a longer caption still (100): its shape and lengths are asserted, not its
+    numbers -- the 16-bit arithmetic of the long-history kernels is held to fp64 in tests/test_attn_decode_gpu.py.  (The oracle
+    re-runs the whole sequence per token: 64 positions cost a third of what 100 did.)"""
     import sys
     import os
     sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))

@@ -17,11 +17,9 @@ import torch
 
 pytestmark = pytest.mark.gpu
 
+from attn_ref import BF16, DT_IDS, DTYPES, F16, F32, Gate as _Gate, attn_ref, rnd  # noqa: E402
 from helpers import synthetic_sd, synth_images  # noqa: E402
 
-F32, BF16, F16 = torch.float32, torch.bfloat16, torch.float16
-DTYPES = [F32, BF16, F16]
-DT_IDS = ["f32", "bf16", "f16"]
 LIMIT = {F32: 40, BF16: 56, F16: 56}           # _prefill_ok / dh_attn_self_prefill: 5 or 7 iterations of 8 keys
 # 1.25 x the worst 16-bit error measured on an MI355X over each test's cases (ulps at max(|want|, 2^-6)); Gate.check prints it.
 # The matrix-core cross-attention rounds the softmax weights to the operand type before its P V product (attn_items.h
@@ -33,7 +31,12 @@ ULP_GATE = {
     "cross_prefill_packed": {BF16: 1.25 * 30.21, F16: 1.25 * 31.56},
     "attn_masked": {BF16: 1.25 * 0.5002, F16: 1.25 * 0.5180},
 }
-ULP_FLOOR = 2.0 ** -6
+
+
+def Gate(name, dt):
+    """attn_ref.Gate against this file's ULP_GATE: fp32 cases assert ``atol = 2e-5`` as they come, 16-bit cases record the
+    error in ulps (at max(|want|, 2^-6)); ``check`` asserts the worst against the gate and prints it."""
+    return _Gate(name, dt, ULP_GATE)
 
 
 @pytest.fixture(scope="module")
@@ -42,53 +45,6 @@ def hip():
     h.load()
     assert torch.cuda.is_available()
     return h
-
-
-def rnd(*shape, seed=0):
-    return torch.randn(*shape, generator=torch.Generator().manual_seed(seed + 7 * sum(shape)))
-
-
-def ulp(x, dt):
-    """Spacing of ``dt`` at |x| (x fp64), at least the type's smallest subnormal step."""
-    mant, sub = {BF16: (7, 2.0 ** -133), F16: (10, 2.0 ** -24)}[dt]
-    _, e = torch.frexp(x.abs())
-    step = torch.ldexp(torch.ones_like(x), e - 1 - mant).clamp(min=sub)
-    return torch.where(x == 0, torch.full_like(x, sub), step)
-
-
-def err_ulps(got, want, dt):
-    want = want.double()
-    return float(((got.double().cpu() - want).abs() / ulp(want.abs().clamp(min=ULP_FLOOR), dt)).max())
-
-
-class Gate:
-    """Accumulates one test's cases: fp32 cases assert ``atol = 2e-5`` as they come, 16-bit cases record the error in ulps;
-    ``check`` asserts the worst against the gate and prints it (the numbers behind ``ULP_GATE``)."""
-
-    def __init__(self, name, dt):
-        self.name, self.dt, self.worst, self.where = name, dt, 0.0, None
-
-    def add(self, got, want, what):
-        if self.dt == F32:
-            np.testing.assert_allclose(got.cpu().double().numpy(), want.double().numpy(), atol=2e-5, rtol=0, err_msg=str(what))
-            return
-        e = err_ulps(got, want, self.dt)
-        if e > self.worst:
-            self.worst, self.where = e, what
-
-    def check(self):
-        if self.dt == F32:
-            return
-        print(f"[{self.name}] {self.dt}: worst {self.worst:.4f} ulp at {self.where}")
-        assert self.worst <= ULP_GATE[self.name][self.dt], (self.name, self.dt, self.worst, self.where)
-
-
-def attn_ref(q, k, v, masked, scale):
-    """q [B, H, Tq, dh], k / v [B, H, Tk, dh], masked bool broadcastable to [B, H, Tq, Tk] -> [B, H, Tq, dh], in fp64."""
-    energy = torch.einsum("bhtd,bhsd->bhts", q.double(), k.double()) / scale
-    if masked is not None:
-        energy = energy.masked_fill(masked, -1e8)
-    return torch.einsum("bhts,bhsd->bhtd", torch.softmax(energy, -1), v.double())
 
 
 # ---- 1. attn_self_prefill: every history length --------------------------------------------------------------------------
