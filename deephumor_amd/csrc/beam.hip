@@ -90,10 +90,23 @@ __device__ __forceinline__ void pick_store(int32_t* pi, float* pv, size_t at, in
 // and hand on a finite dummy pick, so that nothing downstream indexes with garbage
 __device__ __forceinline__ bool dh_softmax_nonfinite(float m, float s) { return !(s >= 1.0f) || !(fabsf(m) < INFINITY); }
 
+// Prompted launches (the *_prompted entry points; PR = true instantiations): every image of the batch brings its own prompt length
+// first_pos[img] and `step` is the launch's absolute position, so the image is in one of three phases --
+//   step <  first_pos[img]  forced: the position's token is the prompt's; nothing is drawn, the row's logits are not read;
+//   step == first_pos[img]  first : the image's logical row img * beam is its single source row (rnn_models.py:73-103,
+//                                   transformers.py:517-545) -- it draws with row index 0, exactly as the dense first step does;
+//   step >  first_pos[img]  normal: today's step.
+// One workgroup owns one row, so the test is workgroup-uniform and the idle rows leave before the first barrier.
+__device__ __forceinline__ bool prompt_row_idle(const int32_t* __restrict__ first_pos, int rc, int rows_per_img, int step) {
+    const int fp = first_pos[rc / rows_per_img];
+    return step < fp || (step == fp && rc % rows_per_img != 0);
+}
+
+template <bool PR>
 __global__ __launch_bounds__(256) void beam_row_sample_kernel(
     const float* __restrict__ logits, int ldl, int V, int rows_per_img, int beam, int top_k,
     float temperature, int unk, const float* __restrict__ noise, uint64_t seed, const uint64_t* __restrict__ seed_ptr, int img0, int step,
-    int32_t* __restrict__ pick_idx, float* __restrict__ pick_val, int32_t* __restrict__ err) {
+    int32_t* __restrict__ pick_idx, float* __restrict__ pick_val, int32_t* __restrict__ err, const int32_t* __restrict__ first_pos) {
     __shared__ int hist[4][256];
     __shared__ uint32_t s_prefix;
     __shared__ int s_k, s_cnt, wtot[4];
@@ -103,6 +116,7 @@ __global__ __launch_bounds__(256) void beam_row_sample_kernel(
     __shared__ int picks[DH_BEAM_MAX_BEAMS];
 
     const int rc = blockIdx.x, tid = threadIdx.x, wave = tid >> 6;
+    if constexpr (PR) { if (prompt_row_idle(first_pos, rc, rows_per_img, step)) return; }
     const float* row = logits + (size_t)rc * ldl;
 
     // ---- k-th largest by MSB-first radix select on the order-preserving key --------------------
@@ -430,11 +444,11 @@ __device__ __forceinline__ void row_tail(const RowLds& L, int rc, int ldl, int r
 #undef s_thr
 }
 
-template <int EPT, int NT, int WPE>
+template <int EPT, int NT, int WPE, bool PR>
 __global__ __launch_bounds__(NT, WPE) void beam_row_sample_fast_kernel(
     const float* __restrict__ logits, int ldl, int V, int rows_per_img, int beam, int top_k,
     float temperature, int unk, const float* __restrict__ noise, uint64_t seed, const uint64_t* __restrict__ seed_ptr, int img0, int step,
-    int32_t* __restrict__ pick_idx, float* __restrict__ pick_val, int32_t* __restrict__ err) {
+    int32_t* __restrict__ pick_idx, float* __restrict__ pick_val, int32_t* __restrict__ err, const int32_t* __restrict__ first_pos) {
     __shared__ uint32_t lmax[NT];
     __shared__ int hist[4 * 256];
     __shared__ uint32_t s_prefix;
@@ -446,6 +460,7 @@ __global__ __launch_bounds__(NT, WPE) void beam_row_sample_fast_kernel(
     __shared__ uint32_t s_thr;
 
     const int rc = blockIdx.x, tid = threadIdx.x;
+    if constexpr (PR) { if (prompt_row_idle(first_pos, rc, rows_per_img, step)) return; }
     const float* row = logits + (size_t)rc * ldl;
     float v[EPT];
     uint32_t best = 0u;                          // key 0 < key of every real float
@@ -497,6 +512,7 @@ struct SelectParams {
     int32_t* parent; int32_t* hparent; uint8_t* done; int32_t* end_step;
     int beam, first, first_sets_ended, write_pos, t, step_index, eos, img0;
     float temperature; const float* noise; uint64_t seed; const uint64_t* seed_ptr;
+    const int32_t* first_pos = nullptr;                 // dh_beam_select_prompted: [n_img] prompt lengths, `first` is then per image
 };
 
 // LDS scratch of one image's candidate draw, carved by the caller (beam_select_kernel's own arrays)
@@ -509,12 +525,29 @@ struct SelLds {
 // The candidate draw + in-place rewrite of one image's beam state, executed by ONE wave (lane = 0..63); LDS hand-overs are
 // wave-local (wave_lds_sync).  MB = the largest beam
 // count the instantiation takes (register arrays of the beams' flags / scores): 16 for the usual settings, 64 for beam_size > 16.
-template <int MB>
+// PR (dh_beam_select_prompted): the image's phase comes from p.first_pos[img] against p.step_index instead of the launch-wide p.first
+// (see prompt_row_idle); its first step reads the picks of its logical row img * beam, where the prompted samplers leave them.
+template <int MB, bool PR = false>
 __device__ __forceinline__ void beam_select_image(const SelectParams& p, const int img, const int lane, const SelLds& L) {
     int32_t* stage = L.stage;
     int* ctok = L.ctok; int* cpar = L.cpar; int* keep = L.keep; float* cval = L.cval; float* q = L.q; uint8_t* cend = L.cend;
 #define s_n (*L.s_n)
     const int B = p.beam, base = img * B;
+    int first = p.first;
+    if constexpr (PR) {
+        const int fp = p.first_pos[img];
+        if (p.step_index < fp) {
+            // forced: the token column keeps the prompt's token, scores / ended / done stay 0, nothing is drawn.  Every beam row keeps
+            // pointing at the image's base row -- the one row with real history behind it -- for the KV cache and the LSTM state
+            for (int b = lane; b < B; b += 64) {
+                p.parent[base + b] = base; p.hparent[base + b] = base;
+                if (p.src) p.src[(size_t)(base + b) * p.src_ld + p.t] = base;
+            }
+            return;
+        }
+        first = p.step_index == fp;
+    }
+    const size_t pk_first = PR ? (size_t)base * B : (size_t)img * B;
     // Stand-alone kernel (L.pki set): EVERYTHING the image needs -- its token rows, ancestor rows and all its picks -- is requested
     // up front by LDS-DMA, next to the loads of done / ended / vals: ONE memory round trip instead of four dependent ones (done ->
     // ended -> picks -> token rows), which were most of this 8 us kernel.
@@ -526,8 +559,8 @@ __device__ __forceinline__ void beam_select_image(const SelectParams& p, const i
         if (p.src)
             for (int b = 0; b < B; ++b)
                 for (int j = lane; j < p.t; j += 64) dh_lds_dma4(p.src + (size_t)(base + b) * p.src_ld + j, srcbuf0 + b * p.t + (j - lane));
-        const int npk = p.first ? B : B * B;
-        const size_t pk0 = p.first ? (size_t)img * B : (size_t)base * B;
+        const int npk = first ? B : B * B;
+        const size_t pk0 = first ? pk_first : (size_t)base * B;
         for (int i = lane; i < npk; i += 64) {
             dh_lds_dma4(p.pick_idx + pk0 + i, L.pki + (i - lane));
             dh_lds_dma4(p.pick_val + pk0 + i, L.pkv + (i - lane));
@@ -545,10 +578,10 @@ __device__ __forceinline__ void beam_select_image(const SelectParams& p, const i
 
     // candidate list in the reference's order: beam b contributes 1 candidate if it has ended, else B.
     // Every lane derives the (short) offset table itself; candidates are then filled in parallel.
-    if (p.first) {
+    if (first) {
         for (int j = lane; j < B; j += 64) {
-            const int tok = pre ? L.pki[j] : p.pick_idx[(size_t)img * B + j];
-            ctok[j] = tok; cval[j] = pre ? L.pkv[j] : p.pick_val[(size_t)img * B + j]; cpar[j] = 0;
+            const int tok = pre ? L.pki[j] : p.pick_idx[pk_first + j];
+            ctok[j] = tok; cval[j] = pre ? L.pkv[j] : p.pick_val[pk_first + j]; cpar[j] = 0;
             cend[j] = (uint8_t)(p.first_sets_ended && tok == p.eos);
             keep[j] = j;
         }
@@ -578,7 +611,7 @@ __device__ __forceinline__ void beam_select_image(const SelectParams& p, const i
     }
     wave_lds_sync();
     const int n = s_n;
-    if (!p.first) {
+    if (!first) {
         // draw `beam` candidates without replacement from softmax(cand_val / T)
         float m = -INFINITY;
         for (int c = lane; c < n; c += 64) m = fmaxf(m, cval[c] / p.temperature);
@@ -630,7 +663,7 @@ __device__ __forceinline__ void beam_select_image(const SelectParams& p, const i
         all_ended &= cend[c];
     }
     // the reference only tests all_ended() inside the token loop (rnn_models.py:131), never after the first draw
-    if (lane == 0 && all_ended && !p.first) { p.done[img] = 1; p.end_step[img] = p.step_index; }
+    if (lane == 0 && all_ended && !first) { p.done[img] = 1; p.end_step[img] = p.step_index; }
 #undef s_n
 }
 
@@ -639,12 +672,12 @@ __device__ __forceinline__ void beam_select_image(const SelectParams& p, const i
 // consecutive columns of each row.  The k-th largest GROUP maximum is a lower bound of the row's k-th largest
 // value (k groups hold a value >= it), and only groups whose maximum reaches that bound can contain one of the
 // top-k values: about top_k of the ~570 groups.  So this kernel reads ~9 % of the row instead of all of it.
-template <int NT>
+template <int NT, bool PR>
 __global__ __launch_bounds__(NT) void beam_row_sample_groups_kernel(
     const float* __restrict__ logits, int ldl, int V, const float* __restrict__ gmax, int gm_ld, int n_groups,
     int gcols, int rows_per_img, int beam, int top_k, float temperature, int unk, const float* __restrict__ noise,
     uint64_t seed, const uint64_t* __restrict__ seed_ptr, int img0, int step, int32_t* __restrict__ pick_idx, float* __restrict__ pick_val,
-    int32_t* __restrict__ err) {
+    int32_t* __restrict__ err, const int32_t* __restrict__ first_pos) {
     constexpr int MAXG = 1024, GPT = MAXG / NT;       // group keys per thread, kept in registers
     __shared__ int glist[MAXG];
     __shared__ int hist[4][256];
@@ -657,6 +690,7 @@ __global__ __launch_bounds__(NT) void beam_row_sample_groups_kernel(
     __shared__ float red[NT];
     __shared__ int picks[DH_BEAM_MAX_BEAMS];
     const int rc = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    if constexpr (PR) { if (prompt_row_idle(first_pos, rc, rows_per_img, step)) return; }
     const float* row = logits + (size_t)rc * ldl;
     uint32_t gk[GPT];
 #pragma unroll
@@ -711,19 +745,67 @@ __global__ __launch_bounds__(NT) void beam_row_sample_groups_kernel(
     row_tail<NT>(L, rc, ldl, rows_per_img, beam, top_k, temperature, unk, noise, seed, seed_ptr, img0, step, pick_idx, pick_val, err);
 }
 
+// The launches of the three row-sampler entry points and of their *_prompted twins (PR: with first_pos, see prompt_row_idle)
+template <bool PR>
+static int row_sample_groups_launch(const float* logits, int ldl, int V, const float* group_max, int gm_ld,
+                                    int n_groups, int group_cols, int rows, int rows_per_img, int beam,
+                                    int top_k, float temperature, int unk_index, const float* noise,
+                                    uint64_t seed, const uint64_t* seed_ptr, int img0, int step, const int32_t* first_pos,
+                                    int32_t* pick_idx, float* pick_val, int32_t* err, void* stream) {
+    DH_REQUIRE(logits && group_max && pick_idx && pick_val && err && rows > 0 && rows_per_img > 0 && V > 0 && ldl >= V);
+    DH_REQUIRE(beam >= 1 && beam <= DH_BEAM_MAX_BEAMS && beam <= top_k && top_k <= V && temperature > 0.f);
+    DH_REQUIRE(n_groups > 0 && n_groups <= 1024 && top_k <= n_groups && gm_ld >= n_groups && group_cols > 0 && group_cols <= 64 &&
+               (long long)n_groups * group_cols >= V);
+    DH_REQUIRE(!PR || (first_pos && rows_per_img == beam && rows % beam == 0));
+    DhProfScope prof("dh_beam_row_sample", 0.0, 0.0, stream);
+    hipLaunchKernelGGL((beam_row_sample_groups_kernel<256, PR>), dim3(rows), dim3(256), 0, (hipStream_t)stream, logits, ldl, V,
+                       group_max, gm_ld, n_groups, group_cols, rows_per_img, beam, top_k, temperature, unk_index, noise,
+                       seed, seed_ptr, img0, step, pick_idx, pick_val, err, first_pos);
+    DH_LAUNCH_CHECK();
+}
+
 extern "C" int dh_beam_row_sample_groups(const float* logits, int ldl, int V, const float* group_max, int gm_ld,
                                          int n_groups, int group_cols, int rows, int rows_per_img, int beam,
                                          int top_k, float temperature, int unk_index, const float* noise,
                                          uint64_t seed, const uint64_t* __restrict__ seed_ptr, int img0, int step, int32_t* pick_idx, float* pick_val,
                                          int32_t* err, void* stream) {
-    DH_REQUIRE(logits && group_max && pick_idx && pick_val && err && rows > 0 && rows_per_img > 0 && V > 0 && ldl >= V);
+    return row_sample_groups_launch<false>(logits, ldl, V, group_max, gm_ld, n_groups, group_cols, rows, rows_per_img, beam, top_k, temperature,
+                                           unk_index, noise, seed, seed_ptr, img0, step, nullptr, pick_idx, pick_val, err, stream);
+}
+
+extern "C" int dh_beam_row_sample_groups_prompted(const float* logits, int ldl, int V, const float* group_max, int gm_ld,
+                                                  int n_groups, int group_cols, int rows, int rows_per_img, int beam,
+                                                  int top_k, float temperature, int unk_index, const float* noise,
+                                                  uint64_t seed, const uint64_t* seed_ptr, int img0, int step, const int32_t* first_pos,
+                                                  int32_t* pick_idx, float* pick_val, int32_t* err, void* stream) {
+    return row_sample_groups_launch<true>(logits, ldl, V, group_max, gm_ld, n_groups, group_cols, rows, rows_per_img, beam, top_k, temperature,
+                                          unk_index, noise, seed, seed_ptr, img0, step, first_pos, pick_idx, pick_val, err, stream);
+}
+
+// exact: the general kernel only (4-pass radix select over the whole row; any top_k, any V; a row with more survivors than
+// DH_BEAM_MAX_SURVIVORS is drawn over the row itself instead of flagging DH_BEAM_ERR_OVERFLOW): the fall-back the host takes when a batch
+// flagged that overflow in the pre-filtered kernels.
+template <bool PR>
+static int row_sample_launch(const float* logits, int ldl, int V, int rows, int rows_per_img, int beam,
+                             int top_k, float temperature, int unk_index, const float* noise,
+                             uint64_t seed, const uint64_t* seed_ptr, int img0, int step, const int32_t* first_pos, int32_t* pick_idx,
+                             float* pick_val, int32_t* err, bool exact, void* stream) {
+    DH_REQUIRE(logits && pick_idx && pick_val && err && rows > 0 && rows_per_img > 0 && V > 0 && ldl >= V);
     DH_REQUIRE(beam >= 1 && beam <= DH_BEAM_MAX_BEAMS && beam <= top_k && top_k <= V && temperature > 0.f);
-    DH_REQUIRE(n_groups > 0 && n_groups <= 1024 && top_k <= n_groups && gm_ld >= n_groups && group_cols > 0 && group_cols <= 64 &&
-               (long long)n_groups * group_cols >= V);
+    DH_REQUIRE(!PR || (first_pos && rows_per_img == beam && rows % beam == 0));
     DhProfScope prof("dh_beam_row_sample", 0.0, 0.0, stream);
-    hipLaunchKernelGGL((beam_row_sample_groups_kernel<256>), dim3(rows), dim3(256), 0, (hipStream_t)stream, logits, ldl, V,
-                       group_max, gm_ld, n_groups, group_cols, rows_per_img, beam, top_k, temperature, unk_index, noise,
-                       seed, seed_ptr, img0, step, pick_idx, pick_val, err);
+#define DH_FAST(EPT, NT, WPE) hipLaunchKernelGGL((beam_row_sample_fast_kernel<EPT, NT, WPE, PR>), dim3(rows), dim3(NT), 0, \
+        (hipStream_t)stream, logits, ldl, V, rows_per_img, beam, top_k, temperature, unk_index, noise, seed, seed_ptr, img0, \
+        step, pick_idx, pick_val, err, first_pos)
+    if (!exact && top_k <= 256 && V <= 512 * 8) DH_FAST(8, 512, 4);
+    else if (!exact && top_k <= 256 && V <= 1024 * 16) DH_FAST(16, 1024, 8);
+    else if (!exact && top_k <= 256 && V <= 1024 * 36) DH_FAST(36, 1024, 8);
+    else if (!exact && top_k <= 256 && V <= 1024 * 64) DH_FAST(64, 1024, 4);
+    else
+        hipLaunchKernelGGL(beam_row_sample_kernel<PR>, dim3(rows), dim3(256), 0, (hipStream_t)stream, logits, ldl, V,
+                           rows_per_img, beam, top_k, temperature, unk_index, noise, seed, seed_ptr, img0, step, pick_idx,
+                           pick_val, err, first_pos);
+#undef DH_FAST
     DH_LAUNCH_CHECK();
 }
 
@@ -731,43 +813,37 @@ extern "C" int dh_beam_row_sample(const float* logits, int ldl, int V, int rows,
                                   int top_k, float temperature, int unk_index, const float* noise,
                                   uint64_t seed, const uint64_t* __restrict__ seed_ptr, int img0, int step, int32_t* pick_idx, float* pick_val,
                                   int32_t* err, void* stream) {
-    DH_REQUIRE(logits && pick_idx && pick_val && err && rows > 0 && rows_per_img > 0 && V > 0 && ldl >= V);
-    DH_REQUIRE(beam >= 1 && beam <= DH_BEAM_MAX_BEAMS && beam <= top_k && top_k <= V && temperature > 0.f);
-    DhProfScope prof("dh_beam_row_sample", 0.0, 0.0, stream);
-#define DH_FAST(EPT, NT, WPE) hipLaunchKernelGGL((beam_row_sample_fast_kernel<EPT, NT, WPE>), dim3(rows), dim3(NT), 0, \
-        (hipStream_t)stream, logits, ldl, V, rows_per_img, beam, top_k, temperature, unk_index, noise, seed, seed_ptr, img0, \
-        step, pick_idx, pick_val, err)
-    if (top_k <= 256 && V <= 512 * 8) DH_FAST(8, 512, 4);
-    else if (top_k <= 256 && V <= 1024 * 16) DH_FAST(16, 1024, 8);
-    else if (top_k <= 256 && V <= 1024 * 36) DH_FAST(36, 1024, 8);
-    else if (top_k <= 256 && V <= 1024 * 64) DH_FAST(64, 1024, 4);
-    else
-        hipLaunchKernelGGL(beam_row_sample_kernel, dim3(rows), dim3(256), 0, (hipStream_t)stream, logits, ldl, V,
-                           rows_per_img, beam, top_k, temperature, unk_index, noise, seed, seed_ptr, img0, step, pick_idx,
-                           pick_val, err);
-#undef DH_FAST
-    DH_LAUNCH_CHECK();
+    return row_sample_launch<false>(logits, ldl, V, rows, rows_per_img, beam, top_k, temperature, unk_index, noise, seed, seed_ptr, img0, step,
+                                    nullptr, pick_idx, pick_val, err, false, stream);
 }
 
-// dh_beam_row_sample on the general kernel only (4-pass radix select over the whole row; any top_k, any V; a row with more survivors than
-// DH_BEAM_MAX_SURVIVORS is drawn over the row itself instead of flagging DH_BEAM_ERR_OVERFLOW): the fall-back the host takes when a batch
-// flagged that overflow in the pre-filtered kernels.
 extern "C" int dh_beam_row_sample_exact(const float* logits, int ldl, int V, int rows, int rows_per_img, int beam,
                                         int top_k, float temperature, int unk_index, const float* noise,
                                         uint64_t seed, const uint64_t* __restrict__ seed_ptr, int img0, int step, int32_t* pick_idx, float* pick_val,
                                         int32_t* err, void* stream) {
-    DH_REQUIRE(logits && pick_idx && pick_val && err && rows > 0 && rows_per_img > 0 && V > 0 && ldl >= V);
-    DH_REQUIRE(beam >= 1 && beam <= DH_BEAM_MAX_BEAMS && beam <= top_k && top_k <= V && temperature > 0.f);
-    DhProfScope prof("dh_beam_row_sample", 0.0, 0.0, stream);
-    hipLaunchKernelGGL(beam_row_sample_kernel, dim3(rows), dim3(256), 0, (hipStream_t)stream, logits, ldl, V,
-                       rows_per_img, beam, top_k, temperature, unk_index, noise, seed, seed_ptr, img0, step, pick_idx,
-                       pick_val, err);
-    DH_LAUNCH_CHECK();
+    return row_sample_launch<false>(logits, ldl, V, rows, rows_per_img, beam, top_k, temperature, unk_index, noise, seed, seed_ptr, img0, step,
+                                    nullptr, pick_idx, pick_val, err, true, stream);
+}
+
+extern "C" int dh_beam_row_sample_prompted(const float* logits, int ldl, int V, int rows, int rows_per_img, int beam,
+                                           int top_k, float temperature, int unk_index, const float* noise,
+                                           uint64_t seed, const uint64_t* seed_ptr, int img0, int step, const int32_t* first_pos,
+                                           int32_t* pick_idx, float* pick_val, int32_t* err, void* stream) {
+    return row_sample_launch<true>(logits, ldl, V, rows, rows_per_img, beam, top_k, temperature, unk_index, noise, seed, seed_ptr, img0, step,
+                                   first_pos, pick_idx, pick_val, err, false, stream);
+}
+
+extern "C" int dh_beam_row_sample_exact_prompted(const float* logits, int ldl, int V, int rows, int rows_per_img, int beam,
+                                                 int top_k, float temperature, int unk_index, const float* noise,
+                                                 uint64_t seed, const uint64_t* seed_ptr, int img0, int step, const int32_t* first_pos,
+                                                 int32_t* pick_idx, float* pick_val, int32_t* err, void* stream) {
+    return row_sample_launch<true>(logits, ldl, V, rows, rows_per_img, beam, top_k, temperature, unk_index, noise, seed, seed_ptr, img0, step,
+                                   first_pos, pick_idx, pick_val, err, true, stream);
 }
 
 // ------------------------------------------------------------------------------------------------
 
-template <int MB>
+template <int MB, bool PR>
 __global__ __launch_bounds__(64) void beam_select_kernel(SelectParams p) {
     extern __shared__ int32_t stage[];
     __shared__ int ctok[MB * MB], cpar[MB * MB], keep[MB];
@@ -777,7 +853,28 @@ __global__ __launch_bounds__(64) void beam_select_kernel(SelectParams p) {
     __shared__ int32_t pki[MB * MB];
     __shared__ float pkv[MB * MB];
     const SelLds L{stage, ctok, cpar, keep, cval, q, cend, &s_n, pki, pkv};
-    beam_select_image<MB>(p, blockIdx.x, threadIdx.x, L);
+    beam_select_image<MB, PR>(p, blockIdx.x, threadIdx.x, L);
+}
+
+template <bool PR>
+static int select_launch(const int32_t* pick_idx, const float* pick_val, int32_t* tokens, int tok_ld,
+                         float* vals, uint8_t* ended, int32_t* src, int src_ld, int32_t* parent,
+                         int32_t* hparent, uint8_t* done, int32_t* end_step, int n_img, int beam,
+                         int first, const int32_t* first_pos, int first_sets_ended, int write_pos, int t, int step_index,
+                         float temperature, int eos_index, const float* noise, uint64_t seed,
+                         const uint64_t* seed_ptr, int img0, void* stream) {
+    DH_REQUIRE(pick_idx && pick_val && tokens && vals && ended && parent && hparent && done && end_step);
+    DH_REQUIRE(n_img > 0 && beam >= 1 && beam <= DH_BEAM_MAX_BEAMS && tok_ld > 0 && t >= 0 && temperature > 0.f);
+    DH_REQUIRE(!src || src_ld > t);
+    DH_REQUIRE(!PR || first_pos);
+    DhProfScope prof("dh_beam_select", 0.0, 0.0, stream);
+    SelectParams p{pick_idx, pick_val, tokens, tok_ld, vals, ended, src, src_ld, parent, hparent, done, end_step,
+                   beam, first, first_sets_ended, write_pos, t, step_index, eos_index, img0, temperature, noise, seed, seed_ptr, first_pos};
+    const size_t lds = (size_t)beam * (tok_ld + (src ? t : 0)) * sizeof(int32_t);
+    DH_REQUIRE(lds <= 56 * 1024);                         // beam * (tok_ld + t) ints of staging next to the candidate arrays
+    if (beam <= 16) hipLaunchKernelGGL((beam_select_kernel<16, PR>), dim3(n_img), dim3(64), lds, (hipStream_t)stream, p);
+    else hipLaunchKernelGGL((beam_select_kernel<DH_BEAM_MAX_BEAMS, PR>), dim3(n_img), dim3(64), lds, (hipStream_t)stream, p);   // beam.py:7-9: any beam_size <= top_k
+    DH_LAUNCH_CHECK();
 }
 
 extern "C" int dh_beam_select(const int32_t* pick_idx, const float* pick_val, int32_t* tokens, int tok_ld,
@@ -786,17 +883,20 @@ extern "C" int dh_beam_select(const int32_t* pick_idx, const float* pick_val, in
                               int first, int first_sets_ended, int write_pos, int t, int step_index,
                               float temperature, int eos_index, const float* noise, uint64_t seed,
                               const uint64_t* seed_ptr, int img0, void* stream) {
-    DH_REQUIRE(pick_idx && pick_val && tokens && vals && ended && parent && hparent && done && end_step);
-    DH_REQUIRE(n_img > 0 && beam >= 1 && beam <= DH_BEAM_MAX_BEAMS && tok_ld > 0 && t >= 0 && temperature > 0.f);
-    DH_REQUIRE(!src || src_ld > t);
-    DhProfScope prof("dh_beam_select", 0.0, 0.0, stream);
-    SelectParams p{pick_idx, pick_val, tokens, tok_ld, vals, ended, src, src_ld, parent, hparent, done, end_step,
-                   beam, first, first_sets_ended, write_pos, t, step_index, eos_index, img0, temperature, noise, seed, seed_ptr};
-    const size_t lds = (size_t)beam * (tok_ld + (src ? t : 0)) * sizeof(int32_t);
-    DH_REQUIRE(lds <= 56 * 1024);                         // beam * (tok_ld + t) ints of staging next to the candidate arrays
-    if (beam <= 16) hipLaunchKernelGGL(beam_select_kernel<16>, dim3(n_img), dim3(64), lds, (hipStream_t)stream, p);
-    else hipLaunchKernelGGL(beam_select_kernel<DH_BEAM_MAX_BEAMS>, dim3(n_img), dim3(64), lds, (hipStream_t)stream, p);   // beam.py:7-9: any beam_size <= top_k
-    DH_LAUNCH_CHECK();
+    return select_launch<false>(pick_idx, pick_val, tokens, tok_ld, vals, ended, src, src_ld, parent, hparent, done, end_step, n_img, beam,
+                                first, nullptr, first_sets_ended, write_pos, t, step_index, temperature, eos_index, noise, seed, seed_ptr, img0,
+                                stream);
+}
+
+extern "C" int dh_beam_select_prompted(const int32_t* pick_idx, const float* pick_val, int32_t* tokens, int tok_ld,
+                                       float* vals, uint8_t* ended, int32_t* src, int src_ld, int32_t* parent,
+                                       int32_t* hparent, uint8_t* done, int32_t* end_step, int n_img, int beam,
+                                       const int32_t* first_pos, int first_sets_ended, int write_pos, int t, int step_index,
+                                       float temperature, int eos_index, const float* noise, uint64_t seed,
+                                       const uint64_t* seed_ptr, int img0, void* stream) {
+    return select_launch<true>(pick_idx, pick_val, tokens, tok_ld, vals, ended, src, src_ld, parent, hparent, done, end_step, n_img, beam,
+                               0, first_pos, first_sets_ended, write_pos, t, step_index, temperature, eos_index, noise, seed, seed_ptr, img0,
+                               stream);
 }
 
 // ---- the reference's METHOD surface (deephumor/models/beam.py:32-108), one kernel per method ------------------------------------

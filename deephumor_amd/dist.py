@@ -92,7 +92,13 @@ def gather_captions(tokens, lengths, n_total, group=None, always=None):
 
 def generate_sharded(generate_fn, n_total, group=None, always=None):
     """Runs ``generate_fn(lo, hi) -> (tokens, lengths)`` on this rank's shard (``lo`` is the global
-    index of its first image: pass it as ``img0``) and gathers the whole batch on every rank."""
+    index of its first image: pass it as ``img0``) and gathers the whole batch on every rank.
+
+    ``generate_fn`` closes over the batch and slices every per-image input itself -- a prompted batch slices ``caption_lengths``
+    exactly as it slices ``caption`` (same for ``generate_micro_sharded``)::
+
+        def generate_fn(lo, hi):
+            return model.generate_batch(images[lo:hi], caption=C[lo:hi], caption_lengths=L[lo:hi], img0=lo, seed=seed, **kw)"""
     rank = dist.get_rank(group) if dist.is_available() and dist.is_initialized() else 0
     world = dist.get_world_size(group) if dist.is_available() and dist.is_initialized() else 1
     lo, hi = shard_range(n_total, rank, world)

@@ -21,6 +21,27 @@ def text_to_seq(text, vocab, tokenizer):
     return torch.tensor(ids).unsqueeze(0)
 
 
+def prompts_to_batch(texts, vocab, tokenizer):
+    """The host text step in front of ``generate_batch(..., caption=C, caption_lengths=L)``: one optional caption beginning per
+    image -> ``(C int64 [N, P], L int64 [N])``.  Every text goes through ``text_to_seq``; a trailing ``<eos>`` is dropped, as the
+    notebook's ``get_a_meme`` does with ``_preprocess_text(caption)[:-1]`` (deephumor_demo.ipynb: the prompt is a beginning, not
+    a finished caption); ``None`` or ``''`` gives length 0 ("no prompt for this image"); rows are padded with ``<pad>`` to the
+    longest prompt (``P`` may be 0)."""
+    eos, pad = vocab.stoi[SPECIAL_TOKENS['EOS']], vocab.stoi[SPECIAL_TOKENS['PAD']]
+    rows = []
+    for text in texts:
+        ids = text_to_seq(text, vocab, tokenizer)[0].tolist() if text else []
+        if ids and ids[-1] == eos:
+            ids = ids[:-1]
+        rows.append(ids)
+    lengths = torch.tensor([len(r) for r in rows], dtype=torch.int64)
+    width = max([len(r) for r in rows], default=0)
+    caption = torch.full((len(rows), width), pad, dtype=torch.int64)
+    for i, r in enumerate(rows):
+        caption[i, :len(r)] = torch.tensor(r, dtype=torch.int64)
+    return caption, lengths
+
+
 def seq_to_text(seq, vocab, delimiter=' '):
     """1-D token tensor -> text, cut before the first ``<eos>``."""
     ids = seq.detach().cpu().reshape(-1).tolist()

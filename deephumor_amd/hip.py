@@ -886,6 +886,33 @@ def beam_select(pick_idx, pick_val, tokens, vals, ended, src, parent, hparent, d
                                  _ptr(noise), seed, _ptr(seed_ptr), img0, _stream())
 
 
+def beam_row_sample_prompted(logits, v, rows, beam, top_k, temperature, unk_index, noise, seed, img0, step, first_pos,
+                             pick_idx, pick_val, err, seed_ptr=None, exact=False, group_max=None):
+    """The row draw of a prompted batch (``first_pos`` int32 ``[rows // beam]``: every image's prompt length; ``step`` the absolute
+    position): ``dh_beam_row_sample_prompted`` / ``_exact_prompted``, or ``_groups_prompted`` with ``group_max``."""
+    _dev(logits, noise, pick_idx, pick_val, err, first_pos, group_max)
+    assert logits.dtype == torch.float32 and first_pos.dtype == torch.int32 and first_pos.numel() * beam == rows
+    if group_max is not None:
+        _launch("dh_beam_row_sample_groups_prompted", _ptr(logits), logits.stride(0), v, _ptr(group_max), group_max.stride(0),
+                n_groups(v), GROUP_COLS, rows, beam, beam, top_k, float(temperature), unk_index, _ptr(noise), seed,
+                _ptr(seed_ptr), img0, step, _ptr(first_pos), _ptr(pick_idx), _ptr(pick_val), _ptr(err), _stream())
+        return
+    _launch("dh_beam_row_sample_exact_prompted" if exact else "dh_beam_row_sample_prompted", _ptr(logits), logits.stride(0), v, rows,
+            beam, beam, top_k, float(temperature), unk_index, _ptr(noise), seed, _ptr(seed_ptr), img0, step, _ptr(first_pos),
+            _ptr(pick_idx), _ptr(pick_val), _ptr(err), _stream())
+
+
+def beam_select_prompted(pick_idx, pick_val, tokens, vals, ended, src, parent, hparent, done, end_step, n_img, beam, first_pos,
+                         first_sets_ended, write_pos, t, step_index, temperature, eos_index, noise, seed, img0, seed_ptr=None):
+    """``beam_select`` with the phase of every image taken from ``first_pos`` (int32 ``[n_img]``) against ``step_index``."""
+    _dev(pick_idx, pick_val, tokens, vals, ended, src, parent, hparent, done, end_step, noise, first_pos)
+    assert first_pos.dtype == torch.int32 and first_pos.numel() == n_img
+    _launch("dh_beam_select_prompted", _ptr(pick_idx), _ptr(pick_val), _ptr(tokens), tokens.stride(0), _ptr(vals),
+            _ptr(ended), _ptr(src), src.stride(0) if src is not None else 0, _ptr(parent), _ptr(hparent), _ptr(done),
+            _ptr(end_step), n_img, beam, _ptr(first_pos), int(first_sets_ended), write_pos, t, step_index, float(temperature),
+            eos_index, _ptr(noise), seed, _ptr(seed_ptr), img0, _stream())
+
+
 def beam_filter_top_k(logits, top_k, unk_index):
     """beam.py:32-37 in place on fp32 ``logits [rows, V]`` (unit column stride; the row stride may exceed V)."""
     _dev(logits)

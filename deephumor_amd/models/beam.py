@@ -209,6 +209,38 @@ class BeamSearchHelper:
         p = caption.shape[1]
         self.tokens[:, :p] = caption.to(torch.int32).repeat_interleave(self.beam_size, dim=0)
 
+    def set_prompts(self, caption, first_pos, pad_index=0):
+        """Prompted batch: ``caption`` int64 ``[n_img, P]`` and ``first_pos`` int32 ``[n_img]`` on the device -- image ``i`` is
+        teacher-forced with ``caption[i, :first_pos[i]]``; the rest of its row is the caller's padding and never reaches the token
+        table (columns ``>= first_pos[i]`` hold ``pad_index`` until the image's own draws fill them).  Every beam row points at its
+        image's base row (``parent`` / ``hparent``, as ``src`` does from the start): the one row with history behind it while the
+        image is forced.  From here on the steps go through ``step_prompted``."""
+        p = min(caption.shape[1], self.max_len)
+        dev = self.device
+        cap = caption[:, :p].to(device=dev, dtype=torch.int32)
+        used = torch.arange(p, device=dev, dtype=torch.int32)[None, :] < first_pos[:, None]
+        cap = torch.where(used, cap, torch.full_like(cap, pad_index))
+        self.tokens[:, :p] = cap.repeat_interleave(self.beam_size, dim=0)
+        base = (torch.arange(self.n_img * self.beam_size, dtype=torch.int32, device=dev) // self.beam_size) * self.beam_size
+        self.parent.copy_(base)
+        self.hparent.copy_(base)
+        self.first_pos = first_pos
+
+    def step_prompted(self, logits, write_pos, t, step_index, first_sets_ended=False, group_max=None):
+        """One beam step of a prompted batch from ``logits [n_img*beam, V]`` at absolute position ``step_index``: per image forced
+        (``step_index < first_pos``: nothing happens), first (``==``: ``step(first=True)`` from the image's base row) or normal
+        (``>``: ``step(first=False)``) -- ``dh_beam_row_sample*_prompted`` + ``dh_beam_select_prompted``.  Philox noise only."""
+        rows, v = logits.shape
+        assert rows == self.n_img * self.beam_size and self.noise_source is None
+        use_groups = group_max is not None and not self.exact and self.top_k <= hip.n_groups(v)
+        hip.beam_row_sample_prompted(logits, v, rows, self.beam_size, self.top_k, self.temperature, self.unk_index, None, self.seed,
+                                     self.img0, step_index, self.first_pos, self.pick_idx, self.pick_val, self.err,
+                                     seed_ptr=self.seed_tensor, exact=self.exact, group_max=group_max if use_groups else None)
+        hip.beam_select_prompted(self.pick_idx, self.pick_val, self.tokens, self.vals, self._ended, self.src, self.parent,
+                                 self.hparent, self.done, self.end_step, self.n_img, self.beam_size, self.first_pos,
+                                 first_sets_ended, write_pos, t, step_index, self.temperature, self.eos_index, None, self.seed,
+                                 self.img0, seed_ptr=self.seed_tensor)
+
     def _noise(self, kind, step, shape, ld=None):
         if self.noise_source is None:
             return None
@@ -376,18 +408,79 @@ def make_noise_source(rng, seed, noise_source, lo, hi, img0, state0=None):
     return TorchRngNoise(seed, hi - lo, img0 + lo, state0=state0)
 
 
-def check_ids(ids, n, capturing_ok=True):
+def check_ids(ids, n, capturing_ok=True, lengths=None):
     """``nn.Embedding``'s ``IndexError`` for ids outside ``[0, n)`` (reference: every token / label lookup).  The kernels gather rows by
     these ids without a bounds test, so an id outside the table would read foreign memory (round 5: a GPU memory fault on a label of -3,
     silent garbage on a token of V + 100): checked on the host, two scalars per call.  Inside a hipGraph capture nothing can be read
-    back: ``generate_batch_graphed`` checks its inputs before the replay instead."""
+    back: ``generate_batch_graphed`` checks its inputs before the replay instead.  ``lengths`` (``[rows]``, prompted batches): only
+    ``ids[i, :lengths[i]]`` is looked at -- the rest of a row is padding that no kernel reads."""
     if ids is None or ids.numel() == 0:
         return
     if ids.is_cuda and capturing_ok and torch.cuda.is_current_stream_capturing():
         return
+    if lengths is not None:
+        used = torch.arange(ids.shape[1], device=ids.device)[None, :] < torch.as_tensor(lengths).to(ids.device)[:, None]
+        ids = ids[used]
+        if ids.numel() == 0:
+            return
     lo, hi = torch.aminmax(ids)
     if int(lo) < 0 or int(hi) >= n:
         raise IndexError("index out of range in self")
+
+
+def check_prompts(caption, caption_lengths, max_len, num_tokens):
+    """Validation of a prompted batch (``generate_batch(..., caption=C, caption_lengths=L)``): ``C`` int64 ``[N, P]``, ``L`` int64 or
+    int32 ``[N]`` with ``0 <= L[i] <= P``; image ``i``'s prompt is ``C[i, :L[i]]`` and must leave at least one decode step
+    (``L[i] + 1 < max_len``: the reference's degenerate returns for a prompt that fills ``max_len - 1`` exist on the dense path only).
+    Token ids are range-checked over the used part of every row only (``check_ids``).  Host work (one read of ``L`` if it lives on
+    the device).  Returns ``L`` as an int64 CPU tensor, or ``None`` without ``caption_lengths``."""
+    if caption_lengths is None:
+        return None
+    if caption is None:
+        raise ValueError("caption_lengths without caption: pass the padded prompts as caption=[N, P]")
+    if caption.dim() != 2:
+        raise ValueError(f"caption must be [N, P] with caption_lengths, got shape {tuple(caption.shape)}")
+    lens = torch.as_tensor(caption_lengths)
+    if lens.dtype not in (torch.int32, torch.int64):
+        raise ValueError(f"caption_lengths must be int64 or int32, not {lens.dtype}")
+    if lens.dim() != 1 or lens.shape[0] != caption.shape[0]:
+        raise ValueError(f"caption_lengths must have shape [{caption.shape[0]}] (one length per caption row), got {tuple(lens.shape)}")
+    host = lens.detach().cpu().to(torch.int64)
+    if host.numel():
+        lo, hi, p = int(host.min()), int(host.max()), caption.shape[1]
+        if lo < 0 or hi > p:
+            raise ValueError(f"caption_lengths must lie in [0, {p}] (the width of caption), found {lo if lo < 0 else hi}")
+        if hi + 1 >= max_len:
+            raise ValueError(f"a prompt of {hi} tokens leaves no decode step at max_len={max_len}: caption_lengths[i] + 1 < max_len "
+                             "is required (use the dense caption=[N, p] call for the reference's behaviour in that case)")
+    check_ids(caption, num_tokens, capturing_ok=False, lengths=host)
+    return host
+
+
+def prompts_need_philox(rng, noise_source):
+    """A prompted batch draws with the kernels' Philox generator only."""
+    if rng == "torch" or noise_source is not None:
+        raise ValueError('caption_lengths needs the Philox generator: rng="torch" and noise_source draw in per-image shapes that '
+                         "differ by phase (dense caption=[N, p] calls, one per prompt length, support them)")
+
+
+def prompt_session_inputs(caption, caption_lengths, max_len, num_tokens, device, rng=None, noise_source=None, no_host_read=False):
+    """What the decoders' prompted sessions need, or ``None`` for a dense call: ``(caption [N, pw] on the device, first_pos int32
+    [N] on the device, the lengths as a Python list or None)``.  ``pw = min(P, max_len - 2)``: no valid prompt is longer.
+    ``no_host_read`` (``defer_check`` / hipGraph capture) with device-resident lengths: nothing is read back -- the caller has
+    validated them (``generate_batch_graphed`` does, before every replay) and the session treats ``0 .. pw`` as the mixed range."""
+    if caption_lengths is None:
+        return None
+    prompts_need_philox(rng, noise_source)
+    lens = torch.as_tensor(caption_lengths)
+    host = None
+    if not (lens.is_cuda and (no_host_read or torch.cuda.is_current_stream_capturing())):
+        host = check_prompts(caption, lens, max_len, num_tokens).tolist()
+    elif caption is None:
+        raise ValueError("caption_lengths without caption: pass the padded prompts as caption=[N, P]")
+    pw = max(0, min(caption.shape[1], max_len - 2))
+    first_pos = lens.to(device=device, dtype=torch.int32).contiguous()
+    return caption[:, :pw].to(device), first_pos, host
 
 
 def check_lengths(lengths, steps):

@@ -49,10 +49,32 @@ class _CaptioningBase(nn.Module):
         """Image (+ label) encoder -> tuple of feature tensors consumed by ``decode``."""
         raise NotImplementedError
 
-    def decode(self, encoded, caption=None, max_len=25, temperature=1.0, beam_size=10, top_k=50, eos_index=3, **kw):
-        """Batched beam-search decoding of ``encode``'s output -> ``(tokens [N, max_len], lengths [N])``."""
+    def decode(self, encoded, caption=None, max_len=25, temperature=1.0, beam_size=10, top_k=50, eos_index=3, *,
+               caption_lengths=None, **kw):
+        """Batched beam-search decoding of ``encode``'s output -> ``(tokens [N, max_len], lengths [N])``.
+        ``caption_lengths`` (keyword only, int64 / int32 ``[N]``): a prompt of its own length per image -- row ``i`` is
+        teacher-forced with ``caption[i, :caption_lengths[i]]`` (0: none; the rest of the row is ignored) and equals the dense
+        single-image call with that prompt and ``img0 + i`` (``LSTMDecoder.generate_batch``)."""
+        if caption_lengths is not None:
+            kw["caption_lengths"] = caption_lengths
         return self.decoder.generate_batch(*encoded, caption=caption, max_len=max_len, temperature=temperature,
                                            beam_size=beam_size, top_k=top_k, eos_index=eos_index, **kw)
+
+    def _check_prompts(self, caption, caption_lengths, max_len, kw):
+        """A prompted batch is validated BEFORE the encoder runs (``beam.check_prompts`` / ``prompt_session_inputs``: shapes, ranges,
+        the options it cannot be combined with); ``defer_check`` callers (graph capture, the pipeline) with device-resident lengths
+        have done so themselves."""
+        if caption_lengths is None:
+            return None
+        from .beam import check_prompts, prompts_need_philox
+        if getattr(self.decoder, "pad_index", 0) == 1:
+            raise NotImplementedError("caption_lengths with pad_index == 1: that decoder re-runs the whole sequence per token on the "
+                                      "module path, which has no per-image prompt phase")
+        prompts_need_philox(kw.get("rng"), kw.get("noise_source"))
+        lens = torch.as_tensor(caption_lengths)
+        if not (lens.is_cuda and (kw.get("defer_check") or torch.cuda.is_current_stream_capturing())):
+            return check_prompts(caption, lens, max_len, self._hp["num_tokens"])      # on the host from here on: the decoder's own
+        return lens                                                                      # check reads no length back again
 
     def _plan_signature(self):
         """Identity of everything a captured graph holds raw pointers to or derives constants from: storage pointer and
@@ -63,7 +85,7 @@ class _CaptioningBase(nn.Module):
 
     MAX_GRAPHS = 4      # captured graphs kept per model (one per (input shapes, decode settings))
 
-    def generate_batch_graphed(self, *inputs, seed=None, caption=None, **kw):
+    def generate_batch_graphed(self, *inputs, seed=None, caption=None, caption_lengths=None, **kw):
         """``generate_batch`` replayed from a captured hipGraph (torch.cuda.CUDAGraph on ROCm).
 
         The whole pass -- encoder, every decode position (a chain of ~70 dependent launches per position for
@@ -77,17 +99,27 @@ class _CaptioningBase(nn.Module):
         matrices, folded BatchNorm vectors, repacked convolution weights): it is valid only for the weight versions it
         was captured with.  Every cached graph therefore records the models' plan signature and keeps the plans
         themselves alive; ``load_state_dict`` / ``.to()`` / in-place weight updates change the signature and the
-        graph is re-captured instead of replayed against stale or freed memory."""
+        graph is re-captured instead of replayed against stale or freed memory.
+
+        ``caption_lengths`` (a prompt of its own length per image, see ``decode``): the lengths live in a device tensor of the graph
+        that is overwritten before every replay, like ``caption``, and are validated on the host first (``beam.check_prompts``).  NO
+        function of the lengths enters the graph cache key -- only the fact that lengths were passed, next to ``caption``'s shape:
+        the captured chain treats every position ``0 .. min(P, max_len - 2)`` as mixed (all ``N * beam`` rows, the prompted beam
+        step), so one graph serves every set of lengths of that shape and returns what eager returns for them."""
         from .beam import BeamOverflow, BeamSearchHelper, resolve_seed, warn_overflow_retry
         if kw.get("rng") == "torch":      # host-generated noise (parity mode): nothing to replay
-            return self.generate_batch(*inputs, caption=caption, seed=seed, **kw)
+            return self.generate_batch(*inputs, caption=caption, seed=seed, caption_lengths=caption_lengths, **kw)
+        if caption_lengths is not None:
+            caption_lengths = self._check_prompts(caption, torch.as_tensor(caption_lengths).cpu(), kw.get("max_len", 25), kw)
+            caption_lengths = caption_lengths.to(device=inputs[0].device, dtype=torch.int32)
+            caption = caption.to(inputs[0].device)
         seed = resolve_seed(seed)
         # ids are looked up without bounds tests and nothing can be read back inside a capture: the caption prefix and integer inputs
         # (labels) are range-checked here, in front of the capture / replay (beam.check_ids: nn.Embedding's IndexError)
         from .beam import check_ids
         dec = getattr(self, "decoder", None)
         emb = getattr(dec, "embedding", None) or getattr(dec, "tok_embedding", None)
-        if emb is not None:
+        if emb is not None and caption_lengths is None:       # (a prompted batch: _check_prompts above looked at the used ids)
             check_ids(caption, emb.num_embeddings, capturing_ok=False)
         lab = getattr(getattr(self, "encoder", None), "label_encoder", None)
         if lab is not None:
@@ -95,14 +127,15 @@ class _CaptioningBase(nn.Module):
                 if not t.is_floating_point() and t.dtype != torch.uint8:
                     check_ids(t, lab.embedding.num_embeddings, capturing_ok=False)
         key = (tuple((tuple(t.shape), t.dtype) for t in inputs), None if caption is None else tuple(caption.shape),
-               tuple(sorted(kw.items())), next(self.parameters()).dtype)
+               tuple(sorted(kw.items())), next(self.parameters()).dtype, caption_lengths is not None)
+        lens_kw = {} if caption_lengths is None else {"caption_lengths": caption_lengths}
         cache = self.__dict__.setdefault("_graphs", {})
         eager_keys = self.__dict__.setdefault("_graph_overflowed", {})       # key -> plan signature it overflowed with
         sig = self._plan_signature()
         if key in eager_keys and eager_keys[key] != sig:
             del eager_keys[key]           # other weights since: the graphed path gets another chance
         if key in eager_keys:             # this configuration overflowed the pre-filtered samplers before (flat logits): straight to
-            return self.generate_batch(*inputs, caption=caption, seed=seed, exact=True, **kw)     # the general sampler, eagerly
+            return self.generate_batch(*inputs, caption=caption, seed=seed, exact=True, **lens_kw, **kw)     # the general sampler, eagerly
         state = cache.get(key)
         if state is not None and state[5] != sig:
             cache.clear()                                 # weights changed: every captured graph points at dead tensors
@@ -110,10 +143,13 @@ class _CaptioningBase(nn.Module):
         if state is None:
             static = [t.clone() for t in inputs]
             scap = None if caption is None else caption.clone()
+            slens = None if caption_lengths is None else caption_lengths.clone()
             seed_t = torch.zeros(1, dtype=torch.int64, device=inputs[0].device)
 
+            slens_kw = {} if slens is None else {"caption_lengths": slens}
+
             def run():
-                return self.generate_batch(*static, caption=scap, seed=0, seed_tensor=seed_t, defer_check=True, **kw)
+                return self.generate_batch(*static, caption=scap, seed=0, seed_tensor=seed_t, defer_check=True, **slens_kw, **kw)
 
             cur = torch.cuda.current_stream()
             side = torch.cuda.Stream()
@@ -131,7 +167,7 @@ class _CaptioningBase(nn.Module):
             plans = [m._get_plan() for m in self.modules() if isinstance(m, _Planned)]     # outlive the graph
             while len(cache) >= self.MAX_GRAPHS:          # every graph keeps its activations / KV cache allocated: oldest out
                 cache.pop(next(iter(cache)))
-            state = cache[key] = (graph, static, scap, seed_t, out, sig, plans)
+            state = cache[key] = (graph, static, scap, seed_t, out, sig, plans, slens)
         else:
             cache[key] = cache.pop(key)                   # most recently used last
         graph, static, scap, seed_t, (toks, lens, err) = state[:5]
@@ -139,19 +175,21 @@ class _CaptioningBase(nn.Module):
             dst.copy_(src)
         if scap is not None:
             scap.copy_(caption)
+        if state[7] is not None:
+            state[7].copy_(caption_lengths)
         seed_t.fill_(int(seed))
         graph.replay()
         from .. import hip
         if next(self.parameters()).dtype == torch.float32 and hip.option("f32_split") and hip.f32x_take_overflow(inputs[0].device):
             # an activation left the fp16 range of the split-operand path inside the replayed graph: this batch eagerly (the guarded
             # generate_batch repeats itself on the exact-fp32 kernels)
-            return self.generate_batch(*inputs, caption=caption, seed=seed, **kw)
+            return self.generate_batch(*inputs, caption=caption, seed=seed, **lens_kw, **kw)
         try:
             BeamSearchHelper.raise_for(int(err.item()))
         except BeamOverflow:              # flat logits: the captured chain cannot switch samplers -- this batch (and, from now on, this
             warn_overflow_retry()         # configuration) eagerly through the general sampler
             eager_keys[key] = self._plan_signature()
-            return self.generate_batch(*inputs, caption=caption, seed=seed, exact=True, **kw)
+            return self.generate_batch(*inputs, caption=caption, seed=seed, exact=True, **lens_kw, **kw)
         return toks.clone(), lens.clone()
 
 
@@ -174,8 +212,9 @@ class CaptioningLSTM(_CaptioningBase):
         return (self.encoder(images),)
 
     def generate_batch(self, images, caption=None, max_len=25, temperature=1.0, beam_size=10, top_k=50,
-                       eos_index=3, **kw):
-        return self.decode(self.encode(images), caption, max_len, temperature, beam_size, top_k, eos_index, **kw)
+                       eos_index=3, *, caption_lengths=None, **kw):
+        caption_lengths = self._check_prompts(caption, caption_lengths, max_len, kw)
+        return self.decode(self.encode(images), caption, max_len, temperature, beam_size, top_k, eos_index, caption_lengths=caption_lengths, **kw)
 
     def generate(self, image, caption=None, max_len=25,
                  temperature=1.0, beam_size=10, top_k=50, eos_index=3, **kw):
@@ -204,8 +243,9 @@ class CaptioningLSTMWithLabels(_CaptioningBase):
         return (self.encoder(images, labels),)
 
     def generate_batch(self, images, labels, caption=None, max_len=25, temperature=1.0, beam_size=10, top_k=50,
-                       eos_index=3, **kw):
-        return self.decode(self.encode(images, labels), caption, max_len, temperature, beam_size, top_k, eos_index, **kw)
+                       eos_index=3, *, caption_lengths=None, **kw):
+        caption_lengths = self._check_prompts(caption, caption_lengths, max_len, kw)
+        return self.decode(self.encode(images, labels), caption, max_len, temperature, beam_size, top_k, eos_index, caption_lengths=caption_lengths, **kw)
 
     def generate(self, image, label, caption=None, max_len=25,
                  temperature=1.0, beam_size=10, top_k=50, eos_index=3, **kw):
@@ -239,8 +279,9 @@ class CaptioningTransformerBase(_CaptioningBase, _TransformerHP):
         return (self.encoder(images),)
 
     def generate_batch(self, images, caption=None, max_len=25, temperature=1.0, beam_size=10, top_k=50,
-                       eos_index=3, **kw):
-        return self.decode(self.encode(images), caption, max_len, temperature, beam_size, top_k, eos_index, **kw)
+                       eos_index=3, *, caption_lengths=None, **kw):
+        caption_lengths = self._check_prompts(caption, caption_lengths, max_len, kw)
+        return self.decode(self.encode(images), caption, max_len, temperature, beam_size, top_k, eos_index, caption_lengths=caption_lengths, **kw)
 
     def generate(self, image, caption=None, max_len=25,
                  temperature=1.0, beam_size=10, top_k=50, eos_index=3, **kw):
@@ -268,8 +309,9 @@ class CaptioningTransformer(_CaptioningBase, _TransformerHP):
         return tuple(self.encoder(images))                  # (image_emb, image_spatial_emb)
 
     def generate_batch(self, images, caption=None, max_len=25, temperature=1.0, beam_size=10, top_k=50,
-                       eos_index=3, **kw):
-        return self.decode(self.encode(images), caption, max_len, temperature, beam_size, top_k, eos_index, **kw)
+                       eos_index=3, *, caption_lengths=None, **kw):
+        caption_lengths = self._check_prompts(caption, caption_lengths, max_len, kw)
+        return self.decode(self.encode(images), caption, max_len, temperature, beam_size, top_k, eos_index, caption_lengths=caption_lengths, **kw)
 
     def generate(self, image, caption=None, max_len=25,
                  temperature=1.0, beam_size=10, top_k=50, eos_index=3, **kw):
@@ -297,8 +339,9 @@ class CaptioningTransformerWithLabels(_CaptioningBase, _TransformerHP):
         return tuple(self.encoder(images, labels))          # (start_emb, image_spatial_emb)
 
     def generate_batch(self, images, labels, caption=None, max_len=25, temperature=1.0, beam_size=10, top_k=50,
-                       eos_index=3, **kw):
-        return self.decode(self.encode(images, labels), caption, max_len, temperature, beam_size, top_k, eos_index, **kw)
+                       eos_index=3, *, caption_lengths=None, **kw):
+        caption_lengths = self._check_prompts(caption, caption_lengths, max_len, kw)
+        return self.decode(self.encode(images, labels), caption, max_len, temperature, beam_size, top_k, eos_index, caption_lengths=caption_lengths, **kw)
 
     def generate(self, image, label, caption=None, max_len=25,
                  temperature=1.0, beam_size=10, top_k=50, eos_index=3, **kw):

@@ -15,7 +15,7 @@ from torch import nn
 
 from .. import hip
 from ._f32x_guard import f32x_guarded
-from .beam import BeamOverflow, BeamSearchHelper, call_logits_hook, check_ids, check_lengths, classifier_must_be_finite, make_noise_source, resolve_seed, run_interleaved, warn_overflow_retry
+from .beam import BeamOverflow, BeamSearchHelper, call_logits_hook, check_ids, check_lengths, classifier_must_be_finite, make_noise_source, prompt_session_inputs, resolve_seed, run_interleaved, warn_overflow_retry
 from .encoders import _Planned
 
 
@@ -176,7 +176,7 @@ class LSTMDecoder(_Planned, nn.Module):
     @f32x_guarded
     def generate_batch(self, image_emb, caption=None, max_len=25, temperature=1.0, beam_size=10, top_k=50,
                        eos_index=3, seed=None, img0=0, noise_source=None, logits_hook=None, streams=1, seed_tensor=None,
-                       defer_check=False, early_stop_every=0, exact=False, rng=None):
+                       defer_check=False, early_stop_every=0, exact=False, rng=None, *, caption_lengths=None):
         """Batched beam-search sampling for ``image_emb [N, 1, E]`` or ``[N, E]``.
 
         Returns ``(tokens int64 [N, max_len] zero-padded, lengths int64 [N])``; row ``i`` equals
@@ -189,11 +189,19 @@ class LSTMDecoder(_Planned, nn.Module):
         when flat logits overflow the pre-filtered samplers, see ``BeamOverflow``).
         ``rng="torch"``: the draws consume torch CPU generators in the reference's order (``beam.TorchRngNoise``): on the fp32 path
         ``torch.manual_seed(s); decoder.generate(emb, rng="torch")`` returns the reference's sampled caption; in a batch image ``i``
-        replays ``torch.manual_seed(seed + img0 + i)``."""
+        replays ``torch.manual_seed(seed + img0 + i)``.
+        ``caption_lengths`` (int64 / int32 ``[N]``, host or device; keyword only): a prompt of its own length per image -- row ``i``
+        is teacher-forced with ``caption[i, :caption_lengths[i]]`` (0: no prompt; the rest of the row is ignored) and equals row 0 of
+        the dense call ``generate_batch(image_emb[i:i+1], caption=caption[i:i+1, :caption_lengths[i]], img0=img0 + i, ...)``.
+        All images walk the positions together; the beam step takes every image's phase from the lengths
+        (``BeamSearchHelper.step_prompted``).  Philox noise only (``beam.prompt_session_inputs``)."""
         self._check_mode()
         plan = self._get_plan()
         classifier_must_be_finite(plan)
-        check_ids(caption, self.embedding.num_embeddings)
+        prompts = prompt_session_inputs(caption, caption_lengths, max_len, self.embedding.num_embeddings, image_emb.device, rng,
+                                        noise_source, no_host_read=defer_check)
+        if prompts is None:
+            check_ids(caption, self.embedding.num_embeddings)
         rng_seed = seed
         seed = 0 if rng == "torch" else resolve_seed(seed, noise_source)
         # rng="torch" with seed=None draws from torch's DEFAULT generator: its state is snapshotted once per call so that a repeated
@@ -201,7 +209,44 @@ class LSTMDecoder(_Planned, nn.Module):
         rng_state0 = torch.get_rng_state() if (rng == "torch" and rng_seed is None) else None
         image_emb = image_emb.reshape(image_emb.shape[0], -1).to(plan["dtype"]).contiguous()
 
+        def prompted_session(lo, hi):
+            """``session`` for a batch with ``caption_lengths``.  Slot ``s`` consumes the image (s = 0) or token ``s - 1`` and
+            predicts token ``s``; image ``i`` makes its first draw at ``s = first_pos[i]``.  Slots below the shortest prompt run
+            as the dense prefix does (one compact row per image); from there to the longest prompt all ``n * beam`` rows run and
+            the prompted beam step sorts the images by phase (the rows of a still-forced image recompute copies of its base row,
+            which ``hparent`` keeps them reading from); past the longest prompt it is the dense loop."""
+            n, b = hi - lo, beam_size
+            r = n * b
+            dev = image_emb.device
+            cap, first_pos, host = prompts
+            pmin, pmax = (min(host[lo:hi]), max(host[lo:hi])) if host is not None else (0, cap.shape[1])
+            helper = BeamSearchHelper(temperature, beam_size, top_k, eos_index=eos_index, device=dev, n_img=n, max_len=max_len,
+                                      seed=seed, img0=img0 + lo, seed_tensor=seed_tensor, exact=exact[0])
+            helper.set_prompts(cap[lo:hi], first_pos[lo:hi])
+            st = self._State(self, plan, n, b, dev)
+            logits = torch.empty((r, (self.num_tokens + 255) // 256 * 256), device=dev)[:, :self.num_tokens]
+            gmax = (torch.empty((r, 4 * ((self.num_tokens + 255) // 256)), device=dev)[:, :hip.n_groups(self.num_tokens)]
+                    if plan["dtype"] in hip.HALF_DTYPES or plan.get("f32_planes") else None)
+            emb = image_emb[lo:hi]
+            for s in range(pmin):
+                self._step(plan, st, n, 1, b, r, img_emb=emb if s == 0 else None, tokens=None if s == 0 else helper.tokens, tok_pos=s - 1)
+            for s in range(pmin, max_len):
+                self._step(plan, st, r, b, 1, r, img_emb=emb if s == 0 else None, tokens=None if s == 0 else helper.tokens,
+                           tok_pos=s - 1, hparent=helper.hparent, logits=logits, group_max=gmax)
+                if logits_hook is not None:
+                    call_logits_hook(logits_hook, s, logits, helper)
+                if s <= pmax:
+                    helper.step_prompted(logits, write_pos=s, t=0, step_index=s, first_sets_ended=True, group_max=gmax)
+                else:
+                    helper.step(logits, first=False, write_pos=s, t=0, step_index=s, group_max=gmax)
+                yield
+                if early_stop_every and s > pmax and (s - pmax) % early_stop_every == 0 and bool(helper.done.all()):
+                    break
+            return helper.finalize(len_bias_done=1, full_len=max_len, defer_check=defer_check)
+
         def session(lo, hi):
+            if prompts is not None:
+                return (yield from prompted_session(lo, hi))
             n, b = hi - lo, beam_size
             r = n * b
             dev = image_emb.device

@@ -21,7 +21,7 @@ from torch import nn
 
 from .. import hip
 from ._f32x_guard import f32x_guarded
-from .beam import BeamOverflow, BeamSearchHelper, call_logits_hook, check_ids, classifier_must_be_finite, make_noise_source, resolve_seed, run_interleaved, warn_overflow_retry
+from .beam import BeamOverflow, BeamSearchHelper, call_logits_hook, check_ids, classifier_must_be_finite, make_noise_source, prompt_session_inputs, resolve_seed, run_interleaved, warn_overflow_retry
 from .encoders import _Planned
 
 
@@ -269,7 +269,7 @@ class _IncrementalDecoder(_Planned, nn.Module):
         """KV cache + cross-attention operands + scratch for one batch, described to the native step
         driver (``dh_transformer_decode_position``) through plain C structs."""
 
-        def __init__(self, dec, plan, n_img, beam, n_pos, enc_out, dev):
+        def __init__(self, dec, plan, n_img, beam, n_pos, enc_out, dev, use_layers=True):
             d, nl = dec.hid_dim, len(dec.layers)
             self.n_img, self.beam, self.rows_total, self.n_pos = n_img, beam, n_img * beam, n_pos
             self.dtype = plan["dtype"]
@@ -328,7 +328,8 @@ class _IncrementalDecoder(_Planned, nn.Module):
             # the decoder layers of a position as ONE persistent launch (csrc/decode_layers.hip): a device-resident table of this run's
             # per-layer pointers + the clusters' hand-over words (zero once; the kernel keeps them consistent from launch to launch)
             self.layers_table = self.layers_sync = None
-            if hip.option("decode_layers") and self.dtype in hip.HALF_DTYPES and hip.decode_layers_supported(m, 1, 0):
+            # (use_layers=False: a prompted batch always takes the launch chain)
+            if use_layers and hip.option("decode_layers") and self.dtype in hip.HALF_DTYPES and hip.decode_layers_supported(m, 1, 0):
                 self.layers_sync = torch.zeros((512,), device=dev, dtype=torch.int32)
                 self.layers_table = hip.decode_layers_table(m, dev)
                 m.layers_table, m.layers_sync = self.layers_table.data_ptr(), self.layers_sync.data_ptr()
@@ -541,11 +542,17 @@ class _IncrementalDecoder(_Planned, nn.Module):
 
     def _generate_batch(self, start_emb, enc_out, caption, max_len, temperature, beam_size, top_k, eos_index,
                         seed=None, img0=0, noise_source=None, logits_hook=None, streams=1, seed_tensor=None,
-                        defer_check=False, early_stop_every=0, exact=False, rng=None):
+                        defer_check=False, early_stop_every=0, exact=False, rng=None, caption_lengths=None):
         self._check_mode()
         plan = self._get_plan()
         classifier_must_be_finite(plan)
-        check_ids(caption, self.tok_embedding.num_embeddings)
+        if caption_lengths is not None and self.pad_index == 1:
+            raise NotImplementedError("caption_lengths with pad_index == 1: that decoder re-runs the whole sequence per token on the "
+                                      "module path (_generate_reforward), which has no per-image prompt phase")
+        prompts = prompt_session_inputs(caption, caption_lengths, max_len, self.tok_embedding.num_embeddings, start_emb.device, rng,
+                                        noise_source, no_host_read=defer_check)
+        if prompts is None:
+            check_ids(caption, self.tok_embedding.num_embeddings)
         rng_seed = seed                   # rng="torch": the draws replay torch CPU generators (beam.TorchRngNoise)
         seed = 0 if rng == "torch" else resolve_seed(seed, noise_source)
         # rng="torch" with seed=None draws from torch's DEFAULT generator: its state is snapshotted once per call so that a repeated
@@ -569,8 +576,47 @@ class _IncrementalDecoder(_Planned, nn.Module):
                 return self._generate_reforward(start_emb, enc_out, caption, max_len, temperature, beam_size, top_k, eos_index, seed,
                                                 img0, noise_source, logits_hook, rng, rng_seed, True)
 
+        def prompted_session(lo, hi):
+            """``session`` for a batch with ``caption_lengths``.  Positions are absolute (slot 0 the image, caption token j at slot
+            j + 1), so all images walk them together and only the beam step knows each image's phase: positions below the shortest
+            prompt run as the dense prefix does (one compact row per image), positions up to the longest prompt run all
+            ``n * beam`` rows -- the rows of a still-forced image recompute copies of its base row, the only one ``src`` lets
+            anybody read -- and the rest is the dense loop.  Always the launch chain (never option ``decode_layers``)."""
+            n, b = hi - lo, beam_size
+            r = n * b
+            dev = start_emb.device
+            cap, first_pos, host = prompts
+            pmin, pmax = (min(host[lo:hi]), max(host[lo:hi])) if host is not None else (0, cap.shape[1])
+            helper = BeamSearchHelper(temperature, beam_size, top_k, eos_index=eos_index, device=dev, n_img=n, max_len=max_len,
+                                      src_len=max_len + 1, seed=seed, img0=img0 + lo, seed_tensor=seed_tensor, exact=exact[0])
+            if self.pad_index != 0:
+                helper.tokens.fill_(self.pad_index)
+            helper.set_prompts(cap[lo:hi], first_pos[lo:hi], self.pad_index)
+            run = self._Run(self, plan, n, b, max_len + 1, None if enc_out is None else enc_out[lo:hi], dev, use_layers=False)
+            semb = start_emb[lo:hi]
+            logits = torch.empty((r, (self.num_tokens + 255) // 256 * 256), device=dev)[:, :self.num_tokens]
+            gmax = (torch.empty((r, 4 * ((self.num_tokens + 255) // 256)), device=dev)[:, :hip.n_groups(self.num_tokens)]
+                    if plan["dtype"] in hip.HALF_DTYPES or plan.get("f32_planes") else None)
+            for t in range(pmin):
+                self._decode_position(plan, run, t, n, 1, b, helper.tokens, helper.src, semb)
+                yield
+            for i in range(pmin, max_len + 1):
+                self._decode_position(plan, run, i, r, b, 1, helper.tokens, helper.src, semb, logits=logits, group_max=gmax)
+                if logits_hook is not None:
+                    call_logits_hook(logits_hook, i, logits, helper)
+                if i <= pmax:
+                    helper.step_prompted(logits, write_pos=i, t=i, step_index=i, first_sets_ended=False, group_max=gmax)
+                else:
+                    helper.step(logits, first=False, write_pos=i, t=i, step_index=i, group_max=gmax)
+                yield
+                if early_stop_every and i > pmax and (i - pmax) % early_stop_every == 0 and bool(helper.done.all()):
+                    break
+            return helper.finalize(len_bias_done=0, full_len=max_len, pad_index=self.pad_index, defer_check=defer_check)
+
         def session(lo, hi):
             """Decodes images [lo, hi); yields after every position (see ``run_interleaved``)."""
+            if prompts is not None:
+                return (yield from prompted_session(lo, hi))
             n, b = hi - lo, beam_size
             r = n * b
             dev = start_emb.device
@@ -645,10 +691,11 @@ class TransformerDecoder(_IncrementalDecoder):
 
     @f32x_guarded
     def generate_batch(self, start_emb, enc_out, caption=None, max_len=25, temperature=1.0, beam_size=10,
-                       top_k=50, eos_index=3, **kw):
-        """``start_emb [N, D]``, ``enc_out [N, S, D]`` -> ``(tokens [N, max_len], lengths [N])``."""
+                       top_k=50, eos_index=3, *, caption_lengths=None, **kw):
+        """``start_emb [N, D]``, ``enc_out [N, S, D]`` -> ``(tokens [N, max_len], lengths [N])``.  ``caption_lengths`` (keyword only):
+        a prompt of its own length per image, see ``LSTMDecoder.generate_batch``."""
         return self._generate_batch(start_emb, enc_out, caption, max_len, temperature, beam_size, top_k,
-                                    eos_index, **kw)
+                                    eos_index, caption_lengths=caption_lengths, **kw)
 
     def generate(self, start_emb, enc_out, caption=None, max_len=25,
                  temperature=1.0, beam_size=10, top_k=50, eos_index=3, **kw):
@@ -671,9 +718,10 @@ class SelfAttentionTransformerDecoder(_IncrementalDecoder):
 
     @f32x_guarded
     def generate_batch(self, start_emb, caption=None, max_len=25, temperature=1.0, beam_size=10,
-                       top_k=50, eos_index=3, **kw):
+                       top_k=50, eos_index=3, *, caption_lengths=None, **kw):
+        """``caption_lengths`` (keyword only): a prompt of its own length per image, see ``LSTMDecoder.generate_batch``."""
         return self._generate_batch(start_emb, None, caption, max_len, temperature, beam_size, top_k,
-                                    eos_index, **kw)
+                                    eos_index, caption_lengths=caption_lengths, **kw)
 
     def generate(self, start_emb, caption=None, max_len=25,
                  temperature=1.0, beam_size=10, top_k=50, eos_index=3, **kw):

@@ -38,7 +38,11 @@ def u8_preprocess(model, size=(224, 224)):
 class CaptionPipeline:
     def __init__(self, model, overlap=True, preprocess=None, **gen_kw):
         """``preprocess``: optional callable mapping the staged device tensors of a batch to ``model.encode``'s inputs
-        (e.g. ``u8_preprocess(model)``); it runs on the encode stream in front of the encoder."""
+        (e.g. ``u8_preprocess(model)``); it runs on the encode stream in front of the encoder.  ``gen_kw`` goes to every batch's
+        ``model.decode`` unchanged: ``caption`` -- and with it ``caption_lengths``, one prompt length per image -- is per pipeline,
+        not per batch, so every batch must have their row count.  Host-resident ``caption_lengths`` are validated with every batch
+        (``beam.check_prompts``; like the dense path's id check this reads the range of a device-resident ``caption`` back, one
+        host synchronisation per batch); device-resident lengths are not read back here and are the caller's to validate."""
         self.model, self.gen_kw, self.overlap, self.preprocess = model, gen_kw, overlap, preprocess
         self.dev = next(model.parameters()).device
         if overlap:

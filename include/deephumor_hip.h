@@ -25,7 +25,7 @@
 extern "C" {
 #endif
 
-#define DH_ABI_VERSION 31
+#define DH_ABI_VERSION 32
 
 enum { DH_OK = 0, DH_ERR_BAD_ARG = 1, DH_ERR_UNSUPPORTED = 2, DH_ERR_LAUNCH = 3 };
 enum { DH_F32 = 0, DH_BF16 = 1,          /* storage type of activations and weights */
@@ -483,6 +483,35 @@ int dh_beam_select(const int32_t* pick_idx, const float* pick_val, int32_t* toke
                    int first, int first_sets_ended, int write_pos, int t, int step_index,
                    float temperature, int eos_index, const float* noise, uint64_t seed,
                    const uint64_t* seed_ptr, int img0, void* stream);
+
+/* ---- Prompted batches: every image brings a caption prompt of its own length (the reference's `caption` argument,
+ * rnn_models.py:73-103 / transformers.py:517-545, one image per call there).  The *_prompted entry points take the arguments of their
+ * namesakes with the launch-wide `first` flag replaced by first_pos [n_img] int32 (device): image img's prompt length.  `step` /
+ * `step_index` is the launch's absolute position; rows_per_img must equal beam.  Per image:
+ *   step <  first_pos[img]  forced: no draw, no error bits, no noise consumed, its logits rows are not read (NaN there is harmless);
+ *                           tokens / vals / ended / done untouched; parent, hparent and src[., t] of its rows = its base row img*beam.
+ *   step == first_pos[img]  first : what first != 0 does with logical row img*beam as the single source row (its picks are row
+ *                           img*beam of pick_*; noise keyed with row index 0, as the dense first step).
+ *   step >  first_pos[img]  normal: the first == 0 step, bit for bit. */
+int dh_beam_row_sample_prompted(const float* logits, int ldl, int V, int rows, int rows_per_img, int beam,
+                                int top_k, float temperature, int unk_index, const float* noise,
+                                uint64_t seed, const uint64_t* seed_ptr, int img0, int step, const int32_t* first_pos,
+                                int32_t* pick_idx, float* pick_val, int32_t* err, void* stream);
+int dh_beam_row_sample_exact_prompted(const float* logits, int ldl, int V, int rows, int rows_per_img, int beam,
+                                      int top_k, float temperature, int unk_index, const float* noise,
+                                      uint64_t seed, const uint64_t* seed_ptr, int img0, int step, const int32_t* first_pos,
+                                      int32_t* pick_idx, float* pick_val, int32_t* err, void* stream);
+int dh_beam_row_sample_groups_prompted(const float* logits, int ldl, int V, const float* group_max, int gm_ld,
+                                       int n_groups, int group_cols, int rows, int rows_per_img, int beam,
+                                       int top_k, float temperature, int unk_index, const float* noise,
+                                       uint64_t seed, const uint64_t* seed_ptr, int img0, int step, const int32_t* first_pos,
+                                       int32_t* pick_idx, float* pick_val, int32_t* err, void* stream);
+int dh_beam_select_prompted(const int32_t* pick_idx, const float* pick_val, int32_t* tokens, int tok_ld,
+                            float* vals, uint8_t* ended, int32_t* src, int src_ld, int32_t* parent,
+                            int32_t* hparent, uint8_t* done, int32_t* end_step, int n_img, int beam,
+                            const int32_t* first_pos, int first_sets_ended, int write_pos, int t, int step_index,
+                            float temperature, int eos_index, const float* noise, uint64_t seed,
+                            const uint64_t* seed_ptr, int img0, void* stream);
 
 /* ---- BeamSearchHelper's METHOD surface (deephumor/models/beam.py:32-108), for callers that drive the helper the way the
  * reference's own generate() loops do (rnn_models.py:87-128, transformers.py:532-569): one image, host-driven, tensors of the
