@@ -5,7 +5,7 @@ import ctypes
 import torch
 
 F32, BF16, BF16_OUT_F32, F16, F16_OUT_F32 = 0, 1, 2, 3, 4
-ABI_VERSION = 32
+ABI_VERSION = 33
 HALF_DTYPES = (torch.bfloat16, torch.float16)       # the two 16-bit storage / MFMA operand types
 ERR_ALL_FILTERED, ERR_OVERFLOW, ERR_TOO_FEW, ERR_NONFINITE = 1, 2, 4, 8
 MAX_BEAMS = 64
@@ -148,6 +148,8 @@ SIGNATURES = {
     "dh_prof_get": [_I, _c.c_char_p, _I, _c.POINTER(_I), _c.POINTER(_c.c_double), _c.POINTER(_c.c_double),
                     _c.POINTER(_c.c_double)],
     "dh_beam_finalize": [_P, _I, _P, _P, _P, _P, _I, _P, _I, _I, _I, _I, _I, _F, _P, _U64, _P, _I, _P],
+    "dh_beam_finalize_beams": [_P, _I, _P, _P, _P, _P, _I, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P, _F, _P, _U64, _P,
+                               _I, _P],
     "dh_beam_filter_top_k": [_P, _I, _I, _I, _I, _I, _P],
     "dh_beam_sample_k": [_P, _I, _I, _I, _I, _F, _P, _I, _U64, _P, _I, _I, _P, _P, _P],
     "dh_beam_gather": [_P, _I, _I, _P, _I, _P, _I, _P, _P],

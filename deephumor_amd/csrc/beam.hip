@@ -1104,3 +1104,81 @@ extern "C" int dh_beam_finalize(const int32_t* tokens, int tok_ld, const float* 
                        temperature, noise, seed, seed_ptr, img0);
     DH_LAUNCH_CHECK();
 }
+
+// ---- n-best finalisation: every beam of every image, ordered by score ---------------------------------------------------------
+// One wave per image, lane = beam (beam <= DH_BEAM_MAX_BEAMS = one wave).  The final draw is beam_finalize_kernel's, statement for
+// statement (same softmax, same Philox counters, same `noise` override), so out_drawn names the beam the plain call copies.  Every
+// lane then ranks its own score among the image's beams with wave shuffles (registers only): slot = #beams with a larger score +
+// #equal-score beams with a smaller engine index -- stable and descending; a NaN score orders like -inf, so the slots are always a
+// permutation and the dead beams of DH_BEAM_ERR_TOO_FEW (score -inf) come last.  The rows are copied beam by beam the way the plain
+// kernel copies the drawn one (columns < row_len from the token table, the rest pad_index), 64 columns per round; the same round
+// looks for the row's first eos_index at or after the image's first generated column (ballot + find-first).
+__global__ __launch_bounds__(64) void beam_finalize_beams_kernel(
+    const int32_t* __restrict__ tokens, int tok_ld, const float* __restrict__ vals, const uint8_t* __restrict__ done,
+    const int32_t* __restrict__ end_step, int32_t* __restrict__ out_tokens, int out_ld, int32_t* __restrict__ out_len,
+    float* __restrict__ out_score, int32_t* __restrict__ out_index, int32_t* __restrict__ out_drawn, int32_t* __restrict__ out_row_len,
+    int beam, int len_bias_done, int full_len, int pad_index, int eos_index, int pos, const int32_t* __restrict__ first_pos,
+    float temperature, const float* __restrict__ noise, uint64_t seed, const uint64_t* __restrict__ seed_ptr, int img0) {
+    const int img = blockIdx.x, lane = threadIdx.x, base = img * beam;
+    const float score = lane < beam ? vals[base + lane] : -INFINITY;
+    // ind = multinomial(softmax(vals / T), 1) == arg-max of p / Exp(1) (first index on ties): as beam_finalize_kernel
+    float x = lane < beam ? score / temperature : -INFINITY;
+    const float m = wave_max(x);
+    float e = lane < beam ? expf(x - m) : 0.f;
+    const float s = wave_sum(e);
+    float qq = -1.f;
+    if (lane < beam) {
+        const float nz = noise ? noise[(size_t)img * beam + lane]
+                               : philox_exp1(seed ^ (seed_ptr ? *seed_ptr : 0ull), (uint32_t)(img0 + img), 0xFFFFFFFFu, 2u, 0u, (uint32_t)lane);
+        qq = (e / s) / nz;
+    }
+    const float best = wave_max(qq);
+    const unsigned long long bal = __ballot(qq == best && lane < beam);
+    const int ind = max(__ffsll((long long)bal) - 1, 0);
+    int len = done[img] ? end_step[img] + len_bias_done : full_len;
+    len = min(len, min(out_ld, tok_ld));
+    // rank of my score among the image's beams (lanes >= beam take no part: they are never compared against, j < beam)
+    const float key = score == score ? score : -INFINITY;
+    int rank = 0;
+    for (int j = 0; j < beam; ++j) {
+        const float o = __shfl(key, j);
+        rank += (o > key) || (o == key && j < lane);
+    }
+    if (lane < beam) {
+        out_score[base + rank] = score;
+        out_index[base + rank] = lane;
+    }
+    const int drawn = __shfl(rank, ind);
+    if (lane == 0) { out_drawn[img] = drawn; out_row_len[img] = len; }
+    const int p0 = first_pos ? first_pos[img] : pos;
+    for (int b = 0; b < beam; ++b) {
+        const int slot = __shfl(rank, b);
+        const int32_t* __restrict__ src = tokens + (size_t)(base + b) * tok_ld;
+        int32_t* __restrict__ dst = out_tokens + (size_t)(base + slot) * out_ld;
+        int eos_at = -1;                                    // (wave-uniform)
+        for (int c0 = 0; c0 < out_ld; c0 += 64) {
+            const int i = c0 + lane;
+            const int tok = i < len ? src[i] : pad_index;
+            if (i < out_ld) dst[i] = tok;
+            const unsigned long long hit = __ballot(i < len && i >= p0 && tok == eos_index);
+            if (eos_at < 0 && hit) eos_at = c0 + __ffsll((long long)hit) - 1;
+        }
+        if (lane == 0) out_len[base + slot] = eos_at >= 0 ? eos_at + 1 : len;      // (eos_at < len: never past the row)
+    }
+}
+
+extern "C" int dh_beam_finalize_beams(const int32_t* tokens, int tok_ld, const float* vals, const uint8_t* done,
+                                      const int32_t* end_step, int32_t* out_tokens, int out_ld, int32_t* out_len,
+                                      float* out_score, int32_t* out_index, int32_t* out_drawn, int32_t* out_row_len,
+                                      int n_img, int beam, int len_bias_done, int full_len, int pad_index, int eos_index,
+                                      int pos, const int32_t* first_pos, float temperature, const float* noise, uint64_t seed,
+                                      const uint64_t* seed_ptr, int img0, void* stream) {
+    DH_REQUIRE(tokens && vals && done && end_step && out_tokens && out_len && out_score && out_index && out_drawn && out_row_len);
+    DH_REQUIRE(n_img > 0 && tok_ld > 0 && out_ld > 0 && pos >= 0);
+    DH_REQUIRE(beam >= 1 && beam <= DH_BEAM_MAX_BEAMS && temperature > 0.f);
+    DhProfScope prof("dh_beam_finalize_beams", 0.0, 0.0, stream);
+    hipLaunchKernelGGL(beam_finalize_beams_kernel, dim3(n_img), dim3(64), 0, (hipStream_t)stream, tokens, tok_ld, vals,
+                       done, end_step, out_tokens, out_ld, out_len, out_score, out_index, out_drawn, out_row_len, beam,
+                       len_bias_done, full_len, pad_index, eos_index, pos, first_pos, temperature, noise, seed, seed_ptr, img0);
+    DH_LAUNCH_CHECK();
+}

@@ -13,7 +13,7 @@ import os
 import torch
 import torch.distributed as dist
 
-__all__ = ["shard_range", "gather_captions", "gather_captions_async", "generate_sharded", "generate_micro_sharded"]
+__all__ = ["shard_range", "gather_captions", "gather_captions_async", "gather_beams", "generate_sharded", "generate_micro_sharded"]
 
 
 def shard_range(n_total, rank, world_size):
@@ -90,8 +90,36 @@ def gather_captions(tokens, lengths, n_total, group=None, always=None):
     return gather_captions_async(tokens, lengths, n_total, group, always).wait()
 
 
+def _pack_beams(beams):
+    """Every field of a ``BeamCaptions`` as ONE int64 payload row per image: ``[B*T tokens | B lengths | B score bits | B beam
+    indices | drawn | row length]``.  The float32 scores travel as their bit patterns (int32 view, sign-extended), so ``-inf`` and
+    every finite value come back bit-identical."""
+    n, b, t = beams.tokens.shape
+    bits = beams.scores.contiguous().view(torch.int32).to(torch.int64)
+    return torch.cat([beams.tokens.reshape(n, b * t), beams.lengths, bits, beams.beam_index, beams.drawn[:, None],
+                      beams.row_lengths[:, None]], 1)
+
+
+def _unpack_beams(rows, b, t):
+    from .models.beam import BeamCaptions
+    n, bt = rows.shape[0], b * t
+    scores = rows[:, bt + b:bt + 2 * b].to(torch.int32).contiguous().view(torch.float32)
+    return BeamCaptions(rows[:, :bt].reshape(n, b, t).contiguous(), rows[:, bt:bt + b].contiguous(), scores,
+                        rows[:, bt + 2 * b:bt + 3 * b].contiguous(), rows[:, bt + 3 * b].contiguous(), rows[:, bt + 3 * b + 1].contiguous())
+
+
+def gather_beams(beams, n_total, group=None, always=None):
+    """``gather_captions`` for a ``BeamCaptions`` of this rank's shard (``generate_batch(..., return_beams=True)``): the whole
+    batch's ``BeamCaptions`` on every rank, in global image order, with ONE ``all_gather_into_tensor`` -- every field rides in one
+    int64 payload row per image (``_pack_beams``)."""
+    if _skip_collective(group, always):
+        return beams
+    _, b, t = beams.tokens.shape
+    return _unpack_beams(gather_rows(_pack_beams(beams), n_total, group, always=True), b, t)
+
+
 def generate_sharded(generate_fn, n_total, group=None, always=None):
-    """Runs ``generate_fn(lo, hi) -> (tokens, lengths)`` on this rank's shard (``lo`` is the global
+    """Runs ``generate_fn(lo, hi) -> (tokens, lengths)`` (or a ``BeamCaptions``: ``return_beams=True``) on this rank's shard (``lo`` is the global
     index of its first image: pass it as ``img0``) and gathers the whole batch on every rank.
 
     ``generate_fn`` closes over the batch and slices every per-image input itself -- a prompted batch slices ``caption_lengths``
@@ -102,8 +130,11 @@ def generate_sharded(generate_fn, n_total, group=None, always=None):
     rank = dist.get_rank(group) if dist.is_available() and dist.is_initialized() else 0
     world = dist.get_world_size(group) if dist.is_available() and dist.is_initialized() else 1
     lo, hi = shard_range(n_total, rank, world)
-    tokens, lengths = generate_fn(lo, hi)
-    return gather_captions(tokens, lengths, n_total, group, always)
+    from .models.beam import BeamCaptions
+    res = generate_fn(lo, hi)
+    if isinstance(res, BeamCaptions):
+        return gather_beams(res, n_total, group, always)
+    return gather_captions(res[0], res[1], n_total, group, always)
 
 
 def generate_micro_sharded(generate_fn, n_total, n_shards, group=None, always=None):
@@ -112,17 +143,25 @@ def generate_micro_sharded(generate_fn, n_total, n_shards, group=None, always=No
     decodes shards ``r * (n_shards / W) ...`` in order, and after each of its shards the ranks exchange that round's shards with
     the same single ``all_gather`` as ``gather_captions``.  Every image keeps its GLOBAL index (``generate_fn(lo, hi)`` must pass
     ``img0=lo``), so the captions equal those of an ``n_shards``-rank run and of one big batch.  Returns the whole
-    ``(tokens [n_total, T], lengths [n_total])`` on every rank."""
+    ``(tokens [n_total, T], lengths [n_total])`` on every rank -- the whole ``BeamCaptions`` if ``generate_fn`` returns one."""
     rank = dist.get_rank(group) if dist.is_available() and dist.is_initialized() else 0
     world = dist.get_world_size(group) if dist.is_available() and dist.is_initialized() else 1
     if n_shards % world:
         raise ValueError(f"n_shards ({n_shards}) must be a multiple of the world size ({world})")
+    from .models.beam import BeamCaptions
     per = n_shards // world
     spans = [shard_range(n_total, s, n_shards) for s in range(n_shards)]
     got = [None] * n_shards
     for j in range(per):
         lo, hi = spans[rank * per + j]
-        toks, lens = generate_fn(lo, hi)
+        res = generate_fn(lo, hi)
+        if isinstance(res, BeamCaptions):  # its payload rows (_pack_beams) take the place of tokens | length
+            beam_shape = tuple(res.tokens.shape[1:])
+            pay = _pack_beams(res)
+            toks, lens = pay[:, :-1], pay[:, -1]
+        else:
+            beam_shape = None
+            toks, lens = res
         # this round holds shards {r * per + j}: a sub-batch whose shards are NOT contiguous in the global order, so it is gathered
         # as raw padded payloads (the largest shard of the whole batch sets the padding) and re-assembled below
         t = toks.shape[1]
@@ -139,6 +178,8 @@ def generate_micro_sharded(generate_fn, n_total, n_shards, group=None, always=No
             a, b = spans[r * per + j]
             got[r * per + j] = out[r * cap:r * cap + (b - a)]
     full = torch.cat(got, 0)
+    if beam_shape is not None:
+        return _unpack_beams(full, *beam_shape)
     return full[:, :-1].contiguous(), full[:, -1].contiguous()
 
 

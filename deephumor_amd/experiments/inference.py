@@ -51,6 +51,34 @@ def seq_to_text(seq, vocab, delimiter=' '):
     return delimiter.join(vocab.itos[i] for i in ids)
 
 
+def beams_to_texts(beams, vocab, delimiter=' '):
+    """``BeamCaptions`` (``generate_batch(..., return_beams=True)``) -> for every image a list of ``(text, score)`` in slot order
+    (best score first).  Every row is cut at its OWN length, then read by ``seq_to_text`` (which stops before ``<eos>``)."""
+    toks, lens, scores = beams.tokens.cpu(), beams.lengths.cpu().tolist(), beams.scores.cpu().tolist()
+    return [[(seq_to_text(toks[i, j, :lens[i][j]], vocab, delimiter), scores[i][j]) for j in range(toks.shape[1])]
+            for i in range(toks.shape[0])]
+
+
+def rank_beams(model, inputs, beams, labels=None):
+    """Ranks every image's candidates by MODEL probability: ``beams.scores`` cannot do that -- the search re-normalises them over
+    the drawn candidates at every step (``log_softmax`` over each row's ``beam_size`` picks, reference beam.py:79), so they are not
+    log-probabilities of the captions.  The ``N * B`` rows, each cut at its own length and padded with ``<pad>``, are scored
+    teacher-forced by ``experiments.scoring.score_captions`` (``inputs``: the ``N`` images the beams were generated for, encoded
+    once; ``template_index = repeat_interleave(arange(N), B)``; ``labels`` for the label models).
+    Returns ``(order int64 [N, B], perplexity float32 [N, B])``: ``order[i]`` lists image ``i``'s slots by ascending perplexity
+    (stable), ``perplexity[i, j]`` belongs to slot ``j``."""
+    from .scoring import score_captions
+    n, b, t = beams.tokens.shape
+    pad = getattr(model.decoder, "pad_index", 0)
+    dev = beams.tokens.device
+    lens = beams.lengths.reshape(n * b)
+    keep = torch.arange(t, device=dev)[None, :] < lens[:, None]
+    rows = torch.where(keep, beams.tokens.reshape(n * b, t), torch.full((), pad, dtype=torch.int64, device=dev))
+    index = torch.arange(n, device=dev).repeat_interleave(b)
+    pp = score_captions(model, inputs, index, rows, lens, labels=labels, pad_index=pad).view(n, b)
+    return torch.argsort(pp, dim=1, stable=True), pp
+
+
 def _clean_block(block):
     block = _SPECIAL.sub('', block).strip(' \t\n\r\f\v')
     return _SPACE_BEFORE_PUNCT.sub(r'\2', block)

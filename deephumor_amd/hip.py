@@ -953,6 +953,19 @@ def beam_finalize(tokens, vals, done, end_step, out, out_len, n_img, beam, len_b
                                    pad_index, float(temperature), _ptr(noise), seed, _ptr(seed_ptr), img0, _stream())
 
 
+def beam_finalize_beams(tokens, vals, done, end_step, out_tokens, out_len, out_score, out_index, out_drawn, out_row_len, n_img, beam,
+                        len_bias_done, full_len, pad_index, eos_index, pos, first_pos, temperature, noise, seed, img0, seed_ptr=None):
+    """``dh_beam_finalize_beams``: the final draw of ``beam_finalize`` plus every beam's row, own length, score and engine index in
+    score order.  ``out_tokens`` int32 ``[n_img, beam, T]``; ``first_pos`` int32 ``[n_img]`` (prompted batches) or None (``pos``)."""
+    _dev(tokens, vals, done, end_step, out_tokens, out_len, out_score, out_index, out_drawn, out_row_len, noise, first_pos)
+    assert out_tokens.is_contiguous() and out_tokens.shape[:2] == (n_img, beam) and out_tokens.dtype == torch.int32
+    assert first_pos is None or (first_pos.dtype == torch.int32 and first_pos.numel() == n_img)
+    _launch("dh_beam_finalize_beams", _ptr(tokens), tokens.stride(0), _ptr(vals), _ptr(done), _ptr(end_step), _ptr(out_tokens),
+            out_tokens.shape[2], _ptr(out_len), _ptr(out_score), _ptr(out_index), _ptr(out_drawn), _ptr(out_row_len), n_img, beam,
+            len_bias_done, full_len, pad_index, eos_index, int(pos), _ptr(first_pos), float(temperature), _ptr(noise), seed,
+            _ptr(seed_ptr), img0, _stream())
+
+
 GROUP_COLS = 64     # column-group width of dh_vocab_logits' group maxima
 
 

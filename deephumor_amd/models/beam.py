@@ -12,10 +12,57 @@ token)`` -- results do not depend on batch composition or rank layout -- or, for
 tests, from caller-supplied tensors (``noise_source``).
 """
 import os
+from typing import NamedTuple
 
 import torch
 
 from .. import hip
+
+
+class BeamCaptions(NamedTuple):
+    """What ``generate_batch(..., return_beams=True)`` returns: EVERY beam the search holds at its end (the plain call draws one of
+    them and drops the rest), per image in descending order of score.  Device tensors, ``N`` images, ``B = beam_size`` slots,
+    ``T`` = the width of the plain call's ``tokens``:
+
+    ``tokens`` int64 ``[N, B, T]``   slot ``j`` of image ``i`` is a complete beam row (padded like the plain call's row);
+    ``lengths`` int64 ``[N, B]``     the beam's OWN length: up to and including its first ``<eos>`` at or after the image's first
+                                     generated column, never more than ``row_lengths[i]``; ``row_lengths[i]`` without one;
+    ``scores`` float32 ``[N, B]``    the engine's ``vals`` -- the reference's cumulative ``sample_val`` -- non-increasing along ``B``
+                                     (equal scores keep the engine's order; a dead beam, score ``-inf``, comes last);
+    ``beam_index`` int64 ``[N, B]``  the engine beam each slot holds (a permutation of ``0 .. B-1``);
+    ``drawn`` int64 ``[N]``          the slot of the beam the plain call returns (its final draw, same noise);
+    ``row_lengths`` int64 ``[N]``    the plain call's ``lengths``.
+
+    ``scores`` are re-normalised over the drawn candidates at every step (``log_softmax`` over each row's ``B`` picks, reference
+    beam.py:79): they order the beams the way the search does, but are NOT model log-probabilities --
+    ``experiments.rank_beams`` ranks by those."""
+    tokens: torch.Tensor
+    lengths: torch.Tensor
+    scores: torch.Tensor
+    beam_index: torch.Tensor
+    drawn: torch.Tensor
+    row_lengths: torch.Tensor
+
+    def best(self):
+        """``(tokens [N, T], lengths [N])`` of the drawn beams: exactly the plain call's pair."""
+        n = self.tokens.shape[0]
+        return self.tokens[torch.arange(n, device=self.tokens.device), self.drawn], self.row_lengths
+
+    def map(self, fn):
+        """``BeamCaptions`` of ``fn(field)`` for every field (``clone``, ``cpu`` ...)."""
+        return BeamCaptions(*(fn(t) for t in self))
+
+    @staticmethod
+    def cat(parts):
+        """The images of several results, in order."""
+        return BeamCaptions(*(torch.cat(ts, 0) for ts in zip(*parts)))
+
+
+def check_return_beams(return_beams):
+    """``return_beams`` is a plain bool (a tensor or an int here is a misplaced positional argument): checked before anything runs."""
+    if not isinstance(return_beams, bool):
+        raise TypeError(f"return_beams must be a bool, not {type(return_beams).__name__}")
+    return return_beams
 
 
 class BeamOverflow(RuntimeError):
@@ -177,6 +224,7 @@ class BeamSearchHelper:
         # optional device-resident int64 word XOR-ed into the seed by the kernels: lets a captured hipGraph of the
         # whole decode be replayed with a fresh seed (kernel arguments are frozen at capture)
         self.seed_tensor = seed_tensor
+        self.first_pos = None             # int32 [n_img] prompt lengths of a prompted session (set_prompts); None: dense
         r = n_img * beam_size
         dev = device
         # all zero-initialised state carved out of ONE zeroed arena (one fill launch instead of eight per generate call)
@@ -278,19 +326,36 @@ class BeamSearchHelper:
                         first_sets_ended, write_pos, t, step_index, self.temperature, self.eos_index, noise,
                         self.seed, self.img0, seed_ptr=self.seed_tensor)
 
-    def finalize(self, len_bias_done, full_len, pad_index=0, defer_check=False, first_beam=False):
+    def finalize(self, len_bias_done, full_len, pad_index=0, defer_check=False, first_beam=False, beams=False, pos=0):
         """Final draw among the beams and output copy; returns (tokens int64 [n_img, max_len], lengths).
         ``defer_check``: skip the host read of the device error word (hipGraph capture) -- the caller checks
         ``self.err`` after replay.  ``first_beam``: no draw, beam 0 -- what the reference's final
         ``sample_k_indices(sample_val, k=1)`` degenerates to when ``sample_val`` is still the ``[beam, 1]`` column of the
-        first step (rnn_models.py:93, 140-141: no decode step ran because the prefix already fills ``max_len - 1``)."""
-        out = torch.empty((self.n_img, self.max_len), dtype=torch.int32, device=self.device)
-        out_len = torch.empty((self.n_img,), dtype=torch.int32, device=self.device)
+        first step (rnn_models.py:93, 140-141: no decode step ran because the prefix already fills ``max_len - 1``).
+        ``beams=True``: one launch of ``dh_beam_finalize_beams`` instead -- the same draw, and every beam kept: returns a
+        ``BeamCaptions`` (then the error word with ``defer_check``).  ``pos``: the first generated column of a dense session (the
+        prefix length), from where a beam's own ``<eos>`` is looked for; a prompted session's comes from ``self.first_pos``."""
         if first_beam:                 # the kernel's race p / noise with an infinite handicap on every beam but the first
             noise = torch.full((self.n_img, self.beam_size), float("inf"), dtype=torch.float32, device=self.device)
             noise[:, 0] = 1.0
         else:
             noise = self._noise("final", 0, (self.n_img, self.beam_size))
+        if beams:
+            n, b, dev = self.n_img, self.beam_size, self.device
+            out = torch.empty((n, b, self.max_len), dtype=torch.int32, device=dev)
+            ints = torch.empty((2 * n * b + 2 * n,), dtype=torch.int32, device=dev)
+            o_len, o_idx, o_drawn, o_row = ints[:n * b].view(n, b), ints[n * b:2 * n * b].view(n, b), ints[2 * n * b:2 * n * b + n], ints[2 * n * b + n:]
+            o_score = torch.empty((n, b), dtype=torch.float32, device=dev)
+            hip.beam_finalize_beams(self.tokens, self.vals, self.done, self.end_step, out, o_len, o_score, o_idx, o_drawn, o_row, n, b,
+                                    len_bias_done, full_len, pad_index, self.eos_index, pos, self.first_pos,
+                                    self.temperature, noise, self.seed, self.img0, seed_ptr=self.seed_tensor)
+            res = BeamCaptions(out.long(), o_len.long(), o_score, o_idx.long(), o_drawn.long(), o_row.long())
+            if defer_check:
+                return res, self.err
+            self.check()
+            return res
+        out = torch.empty((self.n_img, self.max_len), dtype=torch.int32, device=self.device)
+        out_len = torch.empty((self.n_img,), dtype=torch.int32, device=self.device)
         hip.beam_finalize(self.tokens, self.vals, self.done, self.end_step, out, out_len, self.n_img, self.beam_size,
                           len_bias_done, full_len, pad_index, self.temperature, noise, self.seed, self.img0,
                           seed_ptr=self.seed_tensor)
@@ -581,6 +646,20 @@ def run_interleaved(make_session, n_img, n_streams):
                     alive.discard(i)
     for st in pool[:n_streams]:
         main.wait_stream(st)
+    if isinstance(results[0], BeamCaptions) or isinstance(results[0][0], BeamCaptions):
+        # return_beams sessions: a BeamCaptions, or (BeamCaptions, error word) with defer_check -- every field concatenated
+        deferred = not isinstance(results[0], BeamCaptions)
+        parts = [r[0] if deferred else r for r in results]
+        for part in parts:
+            for t in part:
+                t.record_stream(main)
+        out = BeamCaptions.cat(parts)
+        if not deferred:
+            return out
+        err = results[0][1].clone()
+        for r in results[1:]:
+            err |= r[1]
+        return out, err
     for r in results:
         for t in r:
             t.record_stream(main)

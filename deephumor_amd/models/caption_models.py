@@ -39,7 +39,12 @@ class _CaptioningBase(nn.Module):
         return model
 
     @staticmethod
-    def _one(toks, lens):
+    def _one(res):
+        """``generate``'s result from ``generate_batch``'s for one image: the 1-D caption, or the ``BeamCaptions`` as it is."""
+        from .beam import BeamCaptions
+        if isinstance(res, BeamCaptions):
+            return res
+        toks, lens = res
         return toks[0, :int(lens[0])].squeeze()
 
     # ``generate_batch`` = ``decode(encode(...))``.  The two halves are exposed separately so that a serving loop can run
@@ -51,7 +56,8 @@ class _CaptioningBase(nn.Module):
 
     def decode(self, encoded, caption=None, max_len=25, temperature=1.0, beam_size=10, top_k=50, eos_index=3, *,
                caption_lengths=None, **kw):
-        """Batched beam-search decoding of ``encode``'s output -> ``(tokens [N, max_len], lengths [N])``.
+        """Batched beam-search decoding of ``encode``'s output -> ``(tokens [N, max_len], lengths [N])``, or with
+        ``return_beams=True`` every beam of every image as a ``beam.BeamCaptions`` (``LSTMDecoder.generate_batch``).
         ``caption_lengths`` (keyword only, int64 / int32 ``[N]``): a prompt of its own length per image -- row ``i`` is
         teacher-forced with ``caption[i, :caption_lengths[i]]`` (0: none; the rest of the row is ignored) and equals the dense
         single-image call with that prompt and ``img0 + i`` (``LSTMDecoder.generate_batch``)."""
@@ -63,10 +69,11 @@ class _CaptioningBase(nn.Module):
     def _check_prompts(self, caption, caption_lengths, max_len, kw):
         """A prompted batch is validated BEFORE the encoder runs (``beam.check_prompts`` / ``prompt_session_inputs``: shapes, ranges,
         the options it cannot be combined with); ``defer_check`` callers (graph capture, the pipeline) with device-resident lengths
-        have done so themselves."""
+        have done so themselves.  So is the type of ``return_beams`` (``beam.check_return_beams``), for every batch."""
+        from .beam import check_prompts, check_return_beams, prompts_need_philox
+        check_return_beams(kw.get("return_beams", False))
         if caption_lengths is None:
             return None
-        from .beam import check_prompts, prompts_need_philox
         if getattr(self.decoder, "pad_index", 0) == 1:
             raise NotImplementedError("caption_lengths with pad_index == 1: that decoder re-runs the whole sequence per token on the "
                                       "module path, which has no per-image prompt phase")
@@ -106,7 +113,10 @@ class _CaptioningBase(nn.Module):
         function of the lengths enters the graph cache key -- only the fact that lengths were passed, next to ``caption``'s shape:
         the captured chain treats every position ``0 .. min(P, max_len - 2)`` as mixed (all ``N * beam`` rows, the prompted beam
         step), so one graph serves every set of lengths of that shape and returns what eager returns for them."""
-        from .beam import BeamOverflow, BeamSearchHelper, resolve_seed, warn_overflow_retry
+        from .beam import BeamCaptions, BeamOverflow, BeamSearchHelper, check_return_beams, resolve_seed, warn_overflow_retry
+        # ``return_beams=True`` is part of the cache key like every decode setting (``kw``): its graph ends in dh_beam_finalize_beams and
+        # lives beside the plain one of the same shapes; a replay returns clones of every field
+        check_return_beams(kw.get("return_beams", False))
         if kw.get("rng") == "torch":      # host-generated noise (parity mode): nothing to replay
             return self.generate_batch(*inputs, caption=caption, seed=seed, caption_lengths=caption_lengths, **kw)
         if caption_lengths is not None:
@@ -170,7 +180,8 @@ class _CaptioningBase(nn.Module):
             state = cache[key] = (graph, static, scap, seed_t, out, sig, plans, slens)
         else:
             cache[key] = cache.pop(key)                   # most recently used last
-        graph, static, scap, seed_t, (toks, lens, err) = state[:5]
+        graph, static, scap, seed_t, out = state[:5]
+        err = out[-1]
         for dst, src in zip(static, inputs):
             dst.copy_(src)
         if scap is not None:
@@ -190,7 +201,9 @@ class _CaptioningBase(nn.Module):
             warn_overflow_retry()         # configuration) eagerly through the general sampler
             eager_keys[key] = self._plan_signature()
             return self.generate_batch(*inputs, caption=caption, seed=seed, exact=True, **lens_kw, **kw)
-        return toks.clone(), lens.clone()
+        if isinstance(out[0], BeamCaptions):          # (BeamCaptions, error word): clones of every field
+            return out[0].map(torch.Tensor.clone)
+        return out[0].clone(), out[1].clone()
 
 
 class CaptioningLSTM(_CaptioningBase):
@@ -218,7 +231,7 @@ class CaptioningLSTM(_CaptioningBase):
 
     def generate(self, image, caption=None, max_len=25,
                  temperature=1.0, beam_size=10, top_k=50, eos_index=3, **kw):
-        return self.decoder.single_output(*self.generate_batch(image, caption, max_len, temperature, beam_size, top_k, eos_index, **kw),
+        return self.decoder.single_output(self.generate_batch(image, caption, max_len, temperature, beam_size, top_k, eos_index, **kw),
                                           caption, max_len, beam_size)
 
 
@@ -249,8 +262,8 @@ class CaptioningLSTMWithLabels(_CaptioningBase):
 
     def generate(self, image, label, caption=None, max_len=25,
                  temperature=1.0, beam_size=10, top_k=50, eos_index=3, **kw):
-        return self.decoder.single_output(*self.generate_batch(image, label, caption, max_len, temperature, beam_size, top_k,
-                                                               eos_index, **kw), caption, max_len, beam_size)
+        return self.decoder.single_output(self.generate_batch(image, label, caption, max_len, temperature, beam_size, top_k,
+                                                              eos_index, **kw), caption, max_len, beam_size)
 
 
 class _TransformerHP:
@@ -285,7 +298,7 @@ class CaptioningTransformerBase(_CaptioningBase, _TransformerHP):
 
     def generate(self, image, caption=None, max_len=25,
                  temperature=1.0, beam_size=10, top_k=50, eos_index=3, **kw):
-        return self._one(*self.generate_batch(image, caption, max_len, temperature, beam_size, top_k, eos_index, **kw))
+        return self._one(self.generate_batch(image, caption, max_len, temperature, beam_size, top_k, eos_index, **kw))
 
 
 class CaptioningTransformer(_CaptioningBase, _TransformerHP):
@@ -315,7 +328,7 @@ class CaptioningTransformer(_CaptioningBase, _TransformerHP):
 
     def generate(self, image, caption=None, max_len=25,
                  temperature=1.0, beam_size=10, top_k=50, eos_index=3, **kw):
-        return self._one(*self.generate_batch(image, caption, max_len, temperature, beam_size, top_k, eos_index, **kw))
+        return self._one(self.generate_batch(image, caption, max_len, temperature, beam_size, top_k, eos_index, **kw))
 
 
 class CaptioningTransformerWithLabels(_CaptioningBase, _TransformerHP):
@@ -345,5 +358,5 @@ class CaptioningTransformerWithLabels(_CaptioningBase, _TransformerHP):
 
     def generate(self, image, label, caption=None, max_len=25,
                  temperature=1.0, beam_size=10, top_k=50, eos_index=3, **kw):
-        return self._one(*self.generate_batch(image, label, caption, max_len, temperature, beam_size, top_k,
+        return self._one(self.generate_batch(image, label, caption, max_len, temperature, beam_size, top_k,
                                               eos_index, **kw))

@@ -15,7 +15,7 @@ from torch import nn
 
 from .. import hip
 from ._f32x_guard import f32x_guarded
-from .beam import BeamOverflow, BeamSearchHelper, call_logits_hook, check_ids, check_lengths, classifier_must_be_finite, make_noise_source, prompt_session_inputs, resolve_seed, run_interleaved, warn_overflow_retry
+from .beam import BeamCaptions, BeamOverflow, BeamSearchHelper, call_logits_hook, check_return_beams, check_ids, check_lengths, classifier_must_be_finite, make_noise_source, prompt_session_inputs, resolve_seed, run_interleaved, warn_overflow_retry
 from .encoders import _Planned
 
 
@@ -176,7 +176,7 @@ class LSTMDecoder(_Planned, nn.Module):
     @f32x_guarded
     def generate_batch(self, image_emb, caption=None, max_len=25, temperature=1.0, beam_size=10, top_k=50,
                        eos_index=3, seed=None, img0=0, noise_source=None, logits_hook=None, streams=1, seed_tensor=None,
-                       defer_check=False, early_stop_every=0, exact=False, rng=None, *, caption_lengths=None):
+                       defer_check=False, early_stop_every=0, exact=False, rng=None, *, caption_lengths=None, return_beams=False):
         """Batched beam-search sampling for ``image_emb [N, 1, E]`` or ``[N, E]``.
 
         Returns ``(tokens int64 [N, max_len] zero-padded, lengths int64 [N])``; row ``i`` equals
@@ -194,7 +194,11 @@ class LSTMDecoder(_Planned, nn.Module):
         is teacher-forced with ``caption[i, :caption_lengths[i]]`` (0: no prompt; the rest of the row is ignored) and equals row 0 of
         the dense call ``generate_batch(image_emb[i:i+1], caption=caption[i:i+1, :caption_lengths[i]], img0=img0 + i, ...)``.
         All images walk the positions together; the beam step takes every image's phase from the lengths
-        (``BeamSearchHelper.step_prompted``).  Philox noise only (``beam.prompt_session_inputs``)."""
+        (``BeamSearchHelper.step_prompted``).  Philox noise only (``beam.prompt_session_inputs``).
+        ``return_beams=True`` (keyword only): every beam the search ends with instead of the one drawn among them -- a
+        ``beam.BeamCaptions`` whose ``best()`` is the plain call's pair, bit for bit (``dh_beam_finalize_beams`` in place of
+        ``dh_beam_finalize``; nothing else changes)."""
+        check_return_beams(return_beams)
         self._check_mode()
         plan = self._get_plan()
         classifier_must_be_finite(plan)
@@ -242,7 +246,7 @@ class LSTMDecoder(_Planned, nn.Module):
                 yield
                 if early_stop_every and s > pmax and (s - pmax) % early_stop_every == 0 and bool(helper.done.all()):
                     break
-            return helper.finalize(len_bias_done=1, full_len=max_len, defer_check=defer_check)
+            return helper.finalize(len_bias_done=1, full_len=max_len, defer_check=defer_check, beams=return_beams)
 
         def session(lo, hi):
             if prompts is not None:
@@ -289,7 +293,8 @@ class LSTMDecoder(_Planned, nn.Module):
                 if early_stop_every and (i - pos) % early_stop_every == 0 and bool(helper.done.all()):
                     break                                   # finished images are frozen by dh_beam_select: nothing left to do
             # (no decode step when the prefix fills max_len - 1: the reference then returns beam 0 -- see finalize)
-            return helper.finalize(len_bias_done=1, full_len=eff_len, defer_check=defer_check, first_beam=pos + 1 >= max_len)
+            return helper.finalize(len_bias_done=1, full_len=eff_len, defer_check=defer_check, first_beam=pos + 1 >= max_len,
+                                   beams=return_beams, pos=pos)
 
         exact = [bool(exact)]
         try:
@@ -304,14 +309,18 @@ class LSTMDecoder(_Planned, nn.Module):
     def generate(self, image_emb, caption=None, max_len=25,
                  temperature=1.0, beam_size=10, top_k=50, eos_index=3, **kw):
         """Single-image API of the reference (rnn_models.py:48-49): ``image_emb [1, 1, E]`` ->
-        1-D int64 token tensor."""
-        toks, lens = self.generate_batch(image_emb, caption=caption, max_len=max_len, temperature=temperature,
-                                         beam_size=beam_size, top_k=top_k, eos_index=eos_index, **kw)
-        return self.single_output(toks, lens, caption, max_len, beam_size)
+        1-D int64 token tensor; with ``return_beams=True`` the image's ``BeamCaptions`` (``N = 1``, nothing squeezed)."""
+        res = self.generate_batch(image_emb, caption=caption, max_len=max_len, temperature=temperature,
+                                  beam_size=beam_size, top_k=top_k, eos_index=eos_index, **kw)
+        return self.single_output(res, caption, max_len, beam_size)
 
     @staticmethod
-    def single_output(toks, lens, caption, max_len, beam_size):
-        """Row 0 of ``generate_batch``'s result in the shape the reference's single-image ``generate`` returns."""
+    def single_output(res, caption, max_len, beam_size):
+        """Row 0 of ``generate_batch``'s result in the shape the reference's single-image ``generate`` returns; a ``BeamCaptions``
+        (``return_beams=True``) as it is."""
+        if isinstance(res, BeamCaptions):
+            return res
+        toks, lens = res
         seq = toks[0, :int(lens[0])]
         if (0 if caption is None else caption.shape[1]) + 1 >= max_len:
             # no decode step ran: the reference indexes ``sample_seq`` with the [beam, 1] result of its final draw on the

@@ -21,7 +21,7 @@ from torch import nn
 
 from .. import hip
 from ._f32x_guard import f32x_guarded
-from .beam import BeamOverflow, BeamSearchHelper, call_logits_hook, check_ids, classifier_must_be_finite, make_noise_source, prompt_session_inputs, resolve_seed, run_interleaved, warn_overflow_retry
+from .beam import BeamCaptions, BeamOverflow, BeamSearchHelper, call_logits_hook, check_ids, check_return_beams, classifier_must_be_finite, make_noise_source, prompt_session_inputs, resolve_seed, run_interleaved, warn_overflow_retry
 from .encoders import _Planned
 
 
@@ -434,7 +434,7 @@ class _IncrementalDecoder(_Planned, nn.Module):
         return out.view(bs, seq, -1)
 
     def _generate_reforward(self, start_emb, enc_out, caption, max_len, temperature, beam_size, top_k, eos_index, seed, img0,
-                            noise_source, logits_hook, rng, rng_seed, exact):
+                            noise_source, logits_hook, rng, rng_seed, exact, return_beams=False):
         """``generate`` by the reference's own algorithm (transformers.py:521-577): the whole padded sequence of every beam row is
         re-run for each token on the module-API layers.  Only ``pad_index == 1`` needs it (see ``_forward_modules``); the beam
         bookkeeping is the batched engine's."""
@@ -464,7 +464,7 @@ class _IncrementalDecoder(_Planned, nn.Module):
             if logits_hook is not None:
                 call_logits_hook(logits_hook, i, lg, helper)
             helper.step(lg, first=False, write_pos=i, t=i, step_index=i)
-        return helper.finalize(len_bias_done=0, full_len=max_len, pad_index=self.pad_index)
+        return helper.finalize(len_bias_done=0, full_len=max_len, pad_index=self.pad_index, beams=return_beams, pos=pos)
 
     def _prefill_ok(self, plan, seq):
         """All positions at once (batched GEMMs, one causal-attention launch per layer) when the attention kernels'
@@ -540,9 +540,18 @@ class _IncrementalDecoder(_Planned, nn.Module):
         out = hip.linear(x, plan["cls_w"], plan["cls_b"], out_dtype=torch.float32, tag="vocab", w_x=plan.get("cls_w_x"))
         return out.view(bs, seq, -1)
 
+    @staticmethod
+    def _one(res):
+        """``generate``'s result from ``_generate_batch``'s for one image: the caption, or the ``BeamCaptions`` (N = 1) as it is."""
+        if isinstance(res, BeamCaptions):
+            return res
+        toks, lens = res
+        return toks[0, :int(lens[0])].squeeze()
+
     def _generate_batch(self, start_emb, enc_out, caption, max_len, temperature, beam_size, top_k, eos_index,
                         seed=None, img0=0, noise_source=None, logits_hook=None, streams=1, seed_tensor=None,
-                        defer_check=False, early_stop_every=0, exact=False, rng=None, caption_lengths=None):
+                        defer_check=False, early_stop_every=0, exact=False, rng=None, caption_lengths=None, return_beams=False):
+        check_return_beams(return_beams)
         self._check_mode()
         plan = self._get_plan()
         classifier_must_be_finite(plan)
@@ -566,7 +575,7 @@ class _IncrementalDecoder(_Planned, nn.Module):
                 raise NotImplementedError("pad_index == 1 decodes by full re-forward on the host-driven module path: no hipGraph capture")
             try:
                 return self._generate_reforward(start_emb, enc_out, caption, max_len, temperature, beam_size, top_k, eos_index, seed,
-                                                img0, noise_source, logits_hook, rng, rng_seed, bool(exact))
+                                                img0, noise_source, logits_hook, rng, rng_seed, bool(exact), return_beams)
             except BeamOverflow:
                 if exact:
                     raise
@@ -574,7 +583,7 @@ class _IncrementalDecoder(_Planned, nn.Module):
                 if rng_state0 is not None:
                     torch.set_rng_state(rng_state0)
                 return self._generate_reforward(start_emb, enc_out, caption, max_len, temperature, beam_size, top_k, eos_index, seed,
-                                                img0, noise_source, logits_hook, rng, rng_seed, True)
+                                                img0, noise_source, logits_hook, rng, rng_seed, True, return_beams)
 
         def prompted_session(lo, hi):
             """``session`` for a batch with ``caption_lengths``.  Positions are absolute (slot 0 the image, caption token j at slot
@@ -611,7 +620,8 @@ class _IncrementalDecoder(_Planned, nn.Module):
                 yield
                 if early_stop_every and i > pmax and (i - pmax) % early_stop_every == 0 and bool(helper.done.all()):
                     break
-            return helper.finalize(len_bias_done=0, full_len=max_len, pad_index=self.pad_index, defer_check=defer_check)
+            return helper.finalize(len_bias_done=0, full_len=max_len, pad_index=self.pad_index, defer_check=defer_check,
+                                   beams=return_beams)
 
         def session(lo, hi):
             """Decodes images [lo, hi); yields after every position (see ``run_interleaved``)."""
@@ -656,7 +666,8 @@ class _IncrementalDecoder(_Planned, nn.Module):
                 yield
                 if early_stop_every and (i - pos) % early_stop_every == 0 and bool(helper.done.all()):
                     break                                   # all_ended() break of the reference (transformers.py:585)
-            out = helper.finalize(len_bias_done=0, full_len=max_len, pad_index=self.pad_index, defer_check=defer_check)
+            out = helper.finalize(len_bias_done=0, full_len=max_len, pad_index=self.pad_index, defer_check=defer_check,
+                                  beams=return_beams, pos=pos)
             if run.layers_sync is not None and not defer_check and int(run.layers_sync[320]) != 0:
                 # a hand-over of the persistent layer kernel timed out (fewer than 256 resident workgroups?): its results are undefined
                 hip.set_option("decode_layers", 0)
@@ -693,16 +704,16 @@ class TransformerDecoder(_IncrementalDecoder):
     def generate_batch(self, start_emb, enc_out, caption=None, max_len=25, temperature=1.0, beam_size=10,
                        top_k=50, eos_index=3, *, caption_lengths=None, **kw):
         """``start_emb [N, D]``, ``enc_out [N, S, D]`` -> ``(tokens [N, max_len], lengths [N])``.  ``caption_lengths`` (keyword only):
-        a prompt of its own length per image, see ``LSTMDecoder.generate_batch``."""
+        a prompt of its own length per image, see ``LSTMDecoder.generate_batch``; ``return_beams=True`` (in ``kw``): every beam as a
+        ``beam.BeamCaptions``, see there."""
         return self._generate_batch(start_emb, enc_out, caption, max_len, temperature, beam_size, top_k,
                                     eos_index, caption_lengths=caption_lengths, **kw)
 
     def generate(self, start_emb, enc_out, caption=None, max_len=25,
                  temperature=1.0, beam_size=10, top_k=50, eos_index=3, **kw):
         """Reference single-image API (transformers.py:492-493) -> 1-D (0-D for one token) int64."""
-        toks, lens = self._generate_batch(start_emb, enc_out, caption, max_len, temperature, beam_size, top_k,
-                                          eos_index, **kw)
-        return toks[0, :int(lens[0])].squeeze()
+        res = self._generate_batch(start_emb, enc_out, caption, max_len, temperature, beam_size, top_k, eos_index, **kw)
+        return self._one(res)
 
 
 class SelfAttentionTransformerDecoder(_IncrementalDecoder):
@@ -719,13 +730,13 @@ class SelfAttentionTransformerDecoder(_IncrementalDecoder):
     @f32x_guarded
     def generate_batch(self, start_emb, caption=None, max_len=25, temperature=1.0, beam_size=10,
                        top_k=50, eos_index=3, *, caption_lengths=None, **kw):
-        """``caption_lengths`` (keyword only): a prompt of its own length per image, see ``LSTMDecoder.generate_batch``."""
+        """``caption_lengths`` (keyword only): a prompt of its own length per image; ``return_beams=True`` (in ``kw``): every beam as
+        a ``beam.BeamCaptions`` -- see ``LSTMDecoder.generate_batch`` for both."""
         return self._generate_batch(start_emb, None, caption, max_len, temperature, beam_size, top_k,
                                     eos_index, caption_lengths=caption_lengths, **kw)
 
     def generate(self, start_emb, caption=None, max_len=25,
                  temperature=1.0, beam_size=10, top_k=50, eos_index=3, **kw):
         """Reference single-image API (transformers.py:740-741)."""
-        toks, lens = self._generate_batch(start_emb, None, caption, max_len, temperature, beam_size, top_k,
-                                          eos_index, **kw)
-        return toks[0, :int(lens[0])].squeeze()
+        res = self._generate_batch(start_emb, None, caption, max_len, temperature, beam_size, top_k, eos_index, **kw)
+        return self._one(res)

@@ -37,7 +37,8 @@ def u8_preprocess(model, size=(224, 224)):
 
 class CaptionPipeline:
     def __init__(self, model, overlap=True, preprocess=None, **gen_kw):
-        """``preprocess``: optional callable mapping the staged device tensors of a batch to ``model.encode``'s inputs
+        """``return_beams=True`` (one of ``gen_kw``): every batch comes out as a ``beam.BeamCaptions`` instead of the pair.
+        ``preprocess``: optional callable mapping the staged device tensors of a batch to ``model.encode``'s inputs
         (e.g. ``u8_preprocess(model)``); it runs on the encode stream in front of the encoder.  ``gen_kw`` goes to every batch's
         ``model.decode`` unchanged: ``caption`` -- and with it ``caption_lengths``, one prompt length per image -- is per pipeline,
         not per batch, so every batch must have their row count.  Host-resident ``caption_lengths`` are validated with every batch
@@ -61,6 +62,9 @@ class CaptionPipeline:
         # decode is queued without a host read of the beam engine's error word (examined at hand-over); decoders that cannot defer it
         # (pad_index == 1: host-driven full re-forward) decode synchronously
         self._async = getattr(getattr(model, "decoder", None), "pad_index", 0) != 1
+        # return_beams=True (in gen_kw): every batch is yielded as a beam.BeamCaptions (to_host: its fields in pinned memory)
+        from .models.beam import check_return_beams
+        self._beams = check_return_beams(gen_kw.get("return_beams", False))
 
     # -- stages ------------------------------------------------------------------------------------------------------
     def _stage(self, host_inputs):
@@ -119,28 +123,34 @@ class CaptionPipeline:
         with torch.cuda.stream(self.dec_s), torch.no_grad():
             self.dec_s.wait_event(ev)
             res = self.model.decode(enc, seed=seed, img0=img0, defer_check=self._async, **self.gen_kw)
-            toks, lens = res[0], res[1]
+            err = None
+            if self._beams:               # return_beams: a BeamCaptions, in front of the error word when that is deferred
+                if self._async:
+                    res, err = res
+            elif len(res) > 2:
+                res, err = res[:2], res[2]
             err_host = None
-            if len(res) > 2:
+            if err is not None:
                 err_host = torch.empty((1,), dtype=torch.int32).pin_memory()
-                err_host.copy_(res[2].view(-1)[:1], non_blocking=True)
+                err_host.copy_(err.view(-1)[:1], non_blocking=True)
             slot = None
             if to_host:
                 slot = self._out_slot
                 self._out_slot = (self._out_slot + 1) % 3
-                toks, lens = self._to_host(toks, lens, slot)
+                res = self._to_host(res, slot)
             done = torch.cuda.Event()
             done.record(self.dec_s)
-        return dict(toks=toks, lens=lens, done=done, err=err_host, redo=(enc, seed, img0, to_host, slot))
+        return dict(res=res, done=done, err=err_host, redo=(enc, seed, img0, to_host, slot))
 
-    def _to_host(self, toks, lens, key):
+    def _to_host(self, res, key):
+        """``res`` (the ``(tokens, lengths)`` pair, or every field of a ``BeamCaptions``) into the slot's pinned buffers."""
         bufs = self._host_out.get(key)
-        if bufs is None or bufs[0].shape != toks.shape:    # (a replaced pinned pair stays alive while a consumer holds it)
-            bufs = self._host_out[key] = (torch.empty(toks.shape, dtype=toks.dtype).pin_memory(),
-                                          torch.empty(lens.shape, dtype=lens.dtype).pin_memory())
-        bufs[0].copy_(toks, non_blocking=True)
-        bufs[1].copy_(lens, non_blocking=True)
-        return bufs
+        if bufs is None or len(bufs) != len(res) or any(b.shape != t.shape for b, t in zip(bufs, res)):
+            # (a replaced pinned set stays alive while a consumer holds it)
+            bufs = self._host_out[key] = tuple(torch.empty(t.shape, dtype=t.dtype).pin_memory() for t in res)
+        for b, t in zip(bufs, res):
+            b.copy_(t, non_blocking=True)
+        return type(res)(*bufs) if self._beams else bufs
 
     def _finish(self, q):
         """Waits for a queued batch and returns its ``(tokens, lengths)``; reads the deferred error word: flat logits that
@@ -155,12 +165,12 @@ class CaptionPipeline:
                 warn_overflow_retry()
                 enc, seed, img0, to_host, slot = q["redo"]
                 with torch.cuda.stream(self.dec_s), torch.no_grad():
-                    toks, lens = self.model.decode(enc, seed=seed, img0=img0, exact=True, **self.gen_kw)
+                    res = self.model.decode(enc, seed=seed, img0=img0, exact=True, **self.gen_kw)
                     if to_host:           # into the pinned pair THIS batch already owns (the other two may still be held by the consumer)
-                        toks, lens = self._to_host(toks, lens, slot)
+                        res = self._to_host(res, slot)
                 self.dec_s.synchronize()
-                return toks, lens
-        return q["toks"], q["lens"]
+                return res
+        return q["res"]
 
     # -- driver ------------------------------------------------------------------------------------------------------
     def run(self, batches, seeds=None, img0=0, to_host=True, low_latency=False):

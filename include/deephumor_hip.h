@@ -25,7 +25,7 @@
 extern "C" {
 #endif
 
-#define DH_ABI_VERSION 32
+#define DH_ABI_VERSION 33
 
 enum { DH_OK = 0, DH_ERR_BAD_ARG = 1, DH_ERR_UNSUPPORTED = 2, DH_ERR_LAUNCH = 3 };
 enum { DH_F32 = 0, DH_BF16 = 1,          /* storage type of activations and weights */
@@ -550,6 +550,21 @@ int dh_beam_finalize(const int32_t* tokens, int tok_ld, const float* vals, const
                      int n_img, int beam, int len_bias_done, int full_len, int pad_index,
                      float temperature, const float* noise, uint64_t seed, const uint64_t* seed_ptr, int img0,
                      void* stream);
+
+/* dh_beam_finalize that keeps EVERY beam (n-best output): the same final draw (same inputs, Philox counters and noise override:
+ * out_drawn names the beam dh_beam_finalize copies) and the same len -> out_row_len [n_img]; the image's beams are then ordered by
+ * score, descending and stable (slot = #beams with a larger score + #equal-score beams with a smaller engine index; NaN orders like
+ * -inf, so dead beams come last), and for every slot j:  out_tokens [n_img, beam, out_ld] the beam's row copied as above,
+ * out_score / out_index [n_img, beam] its cumulative score (vals) and its engine beam index, out_len [n_img, beam] its own length
+ * -- up to and including its first eos_index at a column >= the image's first generated column (pos, or first_pos[img] when
+ * first_pos is not NULL: prompted batches) and < len, or len without one.  out_drawn [n_img] = the slot of the drawn beam.
+ * rnn_models.py:139-141; transformers.py:571-577 (the sample_seq / sample_val the final draw indexes). */
+int dh_beam_finalize_beams(const int32_t* tokens, int tok_ld, const float* vals, const uint8_t* done,
+                           const int32_t* end_step, int32_t* out_tokens, int out_ld, int32_t* out_len,
+                           float* out_score, int32_t* out_index, int32_t* out_drawn, int32_t* out_row_len,
+                           int n_img, int beam, int len_bias_done, int full_len, int pad_index, int eos_index,
+                           int pos, const int32_t* first_pos, float temperature, const float* noise, uint64_t seed,
+                           const uint64_t* seed_ptr, int img0, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Teacher-forced scoring (deephumor/experiments/metrics.py:4-9; call shape trainer.py:69-81)
