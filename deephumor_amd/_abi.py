@@ -5,7 +5,7 @@ import ctypes
 import torch
 
 F32, BF16, BF16_OUT_F32, F16, F16_OUT_F32 = 0, 1, 2, 3, 4
-ABI_VERSION = 33
+ABI_VERSION = 34
 HALF_DTYPES = (torch.bfloat16, torch.float16)       # the two 16-bit storage / MFMA operand types
 ERR_ALL_FILTERED, ERR_OVERFLOW, ERR_TOO_FEW, ERR_NONFINITE = 1, 2, 4, 8
 MAX_BEAMS = 64
@@ -126,6 +126,7 @@ SIGNATURES = {
     "dh_beam_row_sample_groups_prompted": [_P, _I, _I, _P, _I, _I, _I, _I, _I, _I, _I, _F, _I, _P, _U64, _P, _I, _I, _P, _P, _P, _P, _P],
     "dh_beam_select_prompted": [_P, _P, _P, _I, _P, _P, _P, _I, _P, _P, _P, _P, _I, _I, _P, _I, _I, _I, _I, _F, _I, _P,
                                 _U64, _P, _I, _P],
+    "dh_beam_row_sample_nucleus": [_P, _I, _I, _P, _I, _I, _I, _I, _I, _I, _I, _F, _F, _I, _P, _U64, _P, _I, _I, _P, _I, _P, _P, _P, _P],
     "dh_decode_layers_supported": [_c.POINTER(TrModel), _I, _I],
     "dh_decode_layers_table_bytes": [_I],
     "dh_decode_layers_table": [_c.POINTER(TrModel), _P, _P],

@@ -63,6 +63,12 @@ __device__ __forceinline__ void wave_lds_sync() {
     __builtin_amdgcn_wave_barrier();
 }
 
+// DPP move with zero fill: row_shr:n (CTRL 0x110 + n) hands lane l the value of lane l - n of its 16-lane row, 0.f before the row start
+template <int CTRL>
+__device__ __forceinline__ float dpp_shr0(float v) {
+    return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, 0xF, 0xF, true));
+}
+
 __device__ __forceinline__ float block_reduce_256(float v, float* red, bool is_max) {
     const int tid = threadIdx.x;
     red[tid] = v;
@@ -102,11 +108,24 @@ __device__ __forceinline__ bool prompt_row_idle(const int32_t* __restrict__ firs
     return step < fp || (step == fp && rc % rows_per_img != 0);
 }
 
-template <bool PR>
+struct RowLds {
+    int* idx_a; int* idx_b; float* val_a; float* val_b; float* qv; float* red; int* picks; int* s_cnt; uint32_t* s_thr;
+};
+template <int NT, bool NU>
+__device__ __forceinline__ void row_tail(const RowLds& L, int rc, int ldl, int rows_per_img, int beam, int top_k,
+                                         float temperature, int unk, const float* __restrict__ noise, uint64_t seed,
+                                         const uint64_t* __restrict__ seed_ptr, int img0, int step, int32_t* __restrict__ pick_idx,
+                                         float* __restrict__ pick_val, int32_t* __restrict__ err, float top_p);
+
+// NU (dh_beam_row_sample_nucleus; the same parameter on the two pre-filtered kernels below): the draw runs over the row's NUCLEUS --
+// the survivors whose exclusive prefix of p, in the order (p descending, token index ascending), is < top_p, and never fewer than
+// `beam` of them (row_tail).  The NU = false instantiations are the kernels of every other entry point: top_p is not read there.
+template <bool PR, bool NU = false>
 __global__ __launch_bounds__(256) void beam_row_sample_kernel(
     const float* __restrict__ logits, int ldl, int V, int rows_per_img, int beam, int top_k,
     float temperature, int unk, const float* __restrict__ noise, uint64_t seed, const uint64_t* __restrict__ seed_ptr, int img0, int step,
-    int32_t* __restrict__ pick_idx, float* __restrict__ pick_val, int32_t* __restrict__ err, const int32_t* __restrict__ first_pos) {
+    int32_t* __restrict__ pick_idx, float* __restrict__ pick_val, int32_t* __restrict__ err, const int32_t* __restrict__ first_pos,
+    float top_p) {
     __shared__ int hist[4][256];
     __shared__ uint32_t s_prefix;
     __shared__ int s_k, s_cnt, wtot[4];
@@ -147,6 +166,23 @@ __global__ __launch_bounds__(256) void beam_row_sample_kernel(
     }
     __syncthreads();
     int n = s_cnt;
+    if constexpr (NU) {
+        // No nucleus over a row in global memory: more survivors than the candidate buffers hold is DH_BEAM_ERR_OVERFLOW here too
+        // (row_overflow is not entered).  Otherwise the common tail: its threshold search finds no better value than the preset
+        // one when <unk> has already left the candidates (every candidate is >= thr, so thr is the only key it can write).
+        __shared__ uint32_t s_thr;
+        if (n > CAP) {
+            if (tid == 0) atomicOr(err, DH_BEAM_ERR_OVERFLOW);
+            if (tid < beam) { pick_idx[(size_t)rc * beam + tid] = 0; pick_val[(size_t)rc * beam + tid] = 0.f; }
+            return;
+        }
+        if (tid == 0) s_thr = thr;
+        __syncthreads();
+        const RowLds L{idx_a, idx_b, val_a, val_b, qv, red, picks, &s_cnt, &s_thr};
+        row_tail<256, true>(L, rc, ldl, rows_per_img, beam, top_k, temperature, unk, noise, seed, seed_ptr, img0, step, pick_idx, pick_val,
+                            err, top_p);
+        return;
+    }
     if (n > CAP) {                   // more ties at the threshold than the candidate buffers hold: the draw over the row itself
         row_overflow<256>(row, V, thr, rc, ldl, rows_per_img, beam, temperature, unk, noise, seed, seed_ptr, img0, step, pick_idx, pick_val,
                           qv, idx_b, picks, err);
@@ -337,18 +373,17 @@ __device__ __attribute__((noinline)) void row_overflow(const float* __restrict__
     }
 }
 
-struct RowLds {
-    int* idx_a; int* idx_b; float* val_a; float* val_b; float* qv; float* red; int* picks; int* s_cnt; uint32_t* s_thr;
-};
-
 // Common tail of the row kernels.  On entry idx_a/val_a hold *s_cnt candidates that include every value >= the
 // row's k-th largest (block-synchronised).  Exact threshold -> survivors (ties kept, unk dropped) -> index
 // order -> softmax(filtered / T) -> Exp(1) race for `beam` picks -> log_softmax over the picks.
-template <int NT>
+// NU: between softmax and race the nucleus mask -- p = e / s in index order (val_b), rank sort by (p descending, index ascending)
+// (idx_b[rank] = index-order slot), exclusive block scan of p in that order, and a survivor at sorted position j whose prefix is
+// >= top_p leaves the race (q = -1 < every real q) unless j < beam.  The noise stays indexed by token id.
+template <int NT, bool NU>
 __device__ __forceinline__ void row_tail(const RowLds& L, int rc, int ldl, int rows_per_img, int beam, int top_k,
                                          float temperature, int unk, const float* __restrict__ noise, uint64_t seed,
                                          const uint64_t* __restrict__ seed_ptr, int img0, int step, int32_t* __restrict__ pick_idx,
-                                         float* __restrict__ pick_val, int32_t* __restrict__ err) {
+                                         float* __restrict__ pick_val, int32_t* __restrict__ err, float top_p) {
     const int tid = threadIdx.x;
     int* idx_a = L.idx_a; int* idx_b = L.idx_b; float* val_a = L.val_a; float* val_b = L.val_b;
     float* qv = L.qv; float* red = L.red; int* picks = L.picks;
@@ -417,10 +452,52 @@ __device__ __forceinline__ void row_tail(const RowLds& L, int rc, int ldl, int r
     for (int i = tid; i < n; i += NT) {
         const float nz = noise ? noise[(size_t)rc * ldl + idx_a[i]]
                                : philox_exp1(seed ^ (seed_ptr ? *seed_ptr : 0ull), (uint32_t)(img0 + img), (uint32_t)step, 0u, (uint32_t)rin, (uint32_t)idx_a[i]);
+        if constexpr (NU) val_b[i] = qv[i] / s;
         qv[i] = (qv[i] / s) / nz;
     }
     if (tid < DH_BEAM_MAX_BEAMS) picks[tid] = -1;
     __syncthreads();
+    if constexpr (NU) {
+        // rank sort like the index sort above (n is ~top_k: every thread reads the same address, an LDS broadcast)
+        for (int i = tid; i < n; i += NT) {
+            const float me = val_b[i];
+            int r = 0;
+            for (int j = 0; j < n; ++j) r += (val_b[j] > me) || (val_b[j] == me && j < i);
+            idx_b[r] = i;
+        }
+        __syncthreads();
+        // exclusive scan of p over the sorted positions: thread t owns positions [t * IPT, (t + 1) * IPT) -- its own run serially,
+        // the runs of a wave by DPP row_shr inside the 16-lane rows (a lane shifted in from before the row start reads 0) plus
+        // the totals of the lower rows through v_readlane, the waves through their totals in LDS
+        constexpr int IPT = CAP / NT;
+        static_assert(IPT * NT == CAP && IPT >= 1, "one contiguous run of sorted positions per thread");
+        const int lane = tid & 63, wave = tid >> 6;
+        float loc[IPT], run = 0.f;
+#pragma unroll
+        for (int k = 0; k < IPT; ++k) {
+            const int pos = tid * IPT + k;
+            loc[k] = pos < n ? val_b[idx_b[min(pos, n - 1)]] : 0.f;
+            run += loc[k];
+        }
+        float inc = run;
+        inc += dpp_shr0<0x111>(inc); inc += dpp_shr0<0x112>(inc); inc += dpp_shr0<0x114>(inc); inc += dpp_shr0<0x118>(inc);
+        const float t0 = lane_get(inc, 15), t1 = lane_get(inc, 31), t2 = lane_get(inc, 47), t3 = lane_get(inc, 63);
+        const int drow = lane >> 4;
+        float pre = (drow == 0 ? 0.f : drow == 1 ? t0 : drow == 2 ? t0 + t1 : (t0 + t1) + t2) + dpp_shr0<0x111>(inc);
+        if (lane == 0) red[wave] = ((t0 + t1) + t2) + t3;
+        __syncthreads();
+        float below = 0.f;
+#pragma unroll
+        for (int w = 0; w < NWV; ++w) below += w < wave ? red[w] : 0.f;
+        pre += below;
+#pragma unroll
+        for (int k = 0; k < IPT; ++k) {
+            const int pos = tid * IPT + k;
+            if (pos < n && !(pre < top_p || pos < beam)) qv[idx_b[pos]] = -1.f;
+            pre += loc[k];
+        }
+        __syncthreads();
+    }
     for (int i = tid; i < n; i += NT) {
         const float me = qv[i];
         int r = 0;
@@ -444,11 +521,12 @@ __device__ __forceinline__ void row_tail(const RowLds& L, int rc, int ldl, int r
 #undef s_thr
 }
 
-template <int EPT, int NT, int WPE, bool PR>
+template <int EPT, int NT, int WPE, bool PR, bool NU = false>
 __global__ __launch_bounds__(NT, WPE) void beam_row_sample_fast_kernel(
     const float* __restrict__ logits, int ldl, int V, int rows_per_img, int beam, int top_k,
     float temperature, int unk, const float* __restrict__ noise, uint64_t seed, const uint64_t* __restrict__ seed_ptr, int img0, int step,
-    int32_t* __restrict__ pick_idx, float* __restrict__ pick_val, int32_t* __restrict__ err, const int32_t* __restrict__ first_pos) {
+    int32_t* __restrict__ pick_idx, float* __restrict__ pick_val, int32_t* __restrict__ err, const int32_t* __restrict__ first_pos,
+    float top_p) {
     __shared__ uint32_t lmax[NT];
     __shared__ int hist[4 * 256];
     __shared__ uint32_t s_prefix;
@@ -502,7 +580,7 @@ __global__ __launch_bounds__(NT, WPE) void beam_row_sample_fast_kernel(
     __syncthreads();
     if (s_cnt > CAP) radix_row_candidates<NT>(row, V, top_k, hist, &s_prefix, &s_k, &s_cnt, wtot, idx_a, val_a);
     const RowLds L{idx_a, idx_b, val_a, val_b, qv, red, picks, &s_cnt, &s_thr};
-    row_tail<NT>(L, rc, ldl, rows_per_img, beam, top_k, temperature, unk, noise, seed, seed_ptr, img0, step, pick_idx, pick_val, err);
+    row_tail<NT, NU>(L, rc, ldl, rows_per_img, beam, top_k, temperature, unk, noise, seed, seed_ptr, img0, step, pick_idx, pick_val, err, top_p);
 }
 
 // ---- candidate draw of one image (beam_select_kernel) -----------------------------------------------------------------------
@@ -672,12 +750,12 @@ __device__ __forceinline__ void beam_select_image(const SelectParams& p, const i
 // consecutive columns of each row.  The k-th largest GROUP maximum is a lower bound of the row's k-th largest
 // value (k groups hold a value >= it), and only groups whose maximum reaches that bound can contain one of the
 // top-k values: about top_k of the ~570 groups.  So this kernel reads ~9 % of the row instead of all of it.
-template <int NT, bool PR>
+template <int NT, bool PR, bool NU = false>
 __global__ __launch_bounds__(NT) void beam_row_sample_groups_kernel(
     const float* __restrict__ logits, int ldl, int V, const float* __restrict__ gmax, int gm_ld, int n_groups,
     int gcols, int rows_per_img, int beam, int top_k, float temperature, int unk, const float* __restrict__ noise,
     uint64_t seed, const uint64_t* __restrict__ seed_ptr, int img0, int step, int32_t* __restrict__ pick_idx, float* __restrict__ pick_val,
-    int32_t* __restrict__ err, const int32_t* __restrict__ first_pos) {
+    int32_t* __restrict__ err, const int32_t* __restrict__ first_pos, float top_p) {
     constexpr int MAXG = 1024, GPT = MAXG / NT;       // group keys per thread, kept in registers
     __shared__ int glist[MAXG];
     __shared__ int hist[4][256];
@@ -742,25 +820,25 @@ __global__ __launch_bounds__(NT) void beam_row_sample_groups_kernel(
     __syncthreads();
     if (s_cnt > CAP) radix_row_candidates<NT>(row, V, top_k, &hist[0][0], &s_prefix, &s_k, &s_cnt, wtot, idx_a, val_a);
     const RowLds L{idx_a, idx_b, val_a, val_b, qv, red, picks, &s_cnt, &s_thr};
-    row_tail<NT>(L, rc, ldl, rows_per_img, beam, top_k, temperature, unk, noise, seed, seed_ptr, img0, step, pick_idx, pick_val, err);
+    row_tail<NT, NU>(L, rc, ldl, rows_per_img, beam, top_k, temperature, unk, noise, seed, seed_ptr, img0, step, pick_idx, pick_val, err, top_p);
 }
 
 // The launches of the three row-sampler entry points and of their *_prompted twins (PR: with first_pos, see prompt_row_idle)
-template <bool PR>
+template <bool PR, bool NU = false>
 static int row_sample_groups_launch(const float* logits, int ldl, int V, const float* group_max, int gm_ld,
                                     int n_groups, int group_cols, int rows, int rows_per_img, int beam,
                                     int top_k, float temperature, int unk_index, const float* noise,
                                     uint64_t seed, const uint64_t* seed_ptr, int img0, int step, const int32_t* first_pos,
-                                    int32_t* pick_idx, float* pick_val, int32_t* err, void* stream) {
+                                    int32_t* pick_idx, float* pick_val, int32_t* err, void* stream, float top_p = 1.f) {
     DH_REQUIRE(logits && group_max && pick_idx && pick_val && err && rows > 0 && rows_per_img > 0 && V > 0 && ldl >= V);
     DH_REQUIRE(beam >= 1 && beam <= DH_BEAM_MAX_BEAMS && beam <= top_k && top_k <= V && temperature > 0.f);
     DH_REQUIRE(n_groups > 0 && n_groups <= 1024 && top_k <= n_groups && gm_ld >= n_groups && group_cols > 0 && group_cols <= 64 &&
                (long long)n_groups * group_cols >= V);
     DH_REQUIRE(!PR || (first_pos && rows_per_img == beam && rows % beam == 0));
-    DhProfScope prof("dh_beam_row_sample", 0.0, 0.0, stream);
-    hipLaunchKernelGGL((beam_row_sample_groups_kernel<256, PR>), dim3(rows), dim3(256), 0, (hipStream_t)stream, logits, ldl, V,
+    DhProfScope prof(NU ? "dh_beam_row_sample_nucleus" : "dh_beam_row_sample", 0.0, 0.0, stream);
+    hipLaunchKernelGGL((beam_row_sample_groups_kernel<256, PR, NU>), dim3(rows), dim3(256), 0, (hipStream_t)stream, logits, ldl, V,
                        group_max, gm_ld, n_groups, group_cols, rows_per_img, beam, top_k, temperature, unk_index, noise,
-                       seed, seed_ptr, img0, step, pick_idx, pick_val, err, first_pos);
+                       seed, seed_ptr, img0, step, pick_idx, pick_val, err, first_pos, top_p);
     DH_LAUNCH_CHECK();
 }
 
@@ -785,26 +863,26 @@ extern "C" int dh_beam_row_sample_groups_prompted(const float* logits, int ldl, 
 // exact: the general kernel only (4-pass radix select over the whole row; any top_k, any V; a row with more survivors than
 // DH_BEAM_MAX_SURVIVORS is drawn over the row itself instead of flagging DH_BEAM_ERR_OVERFLOW): the fall-back the host takes when a batch
 // flagged that overflow in the pre-filtered kernels.
-template <bool PR>
+template <bool PR, bool NU = false>
 static int row_sample_launch(const float* logits, int ldl, int V, int rows, int rows_per_img, int beam,
                              int top_k, float temperature, int unk_index, const float* noise,
                              uint64_t seed, const uint64_t* seed_ptr, int img0, int step, const int32_t* first_pos, int32_t* pick_idx,
-                             float* pick_val, int32_t* err, bool exact, void* stream) {
+                             float* pick_val, int32_t* err, bool exact, void* stream, float top_p = 1.f) {
     DH_REQUIRE(logits && pick_idx && pick_val && err && rows > 0 && rows_per_img > 0 && V > 0 && ldl >= V);
     DH_REQUIRE(beam >= 1 && beam <= DH_BEAM_MAX_BEAMS && beam <= top_k && top_k <= V && temperature > 0.f);
     DH_REQUIRE(!PR || (first_pos && rows_per_img == beam && rows % beam == 0));
-    DhProfScope prof("dh_beam_row_sample", 0.0, 0.0, stream);
-#define DH_FAST(EPT, NT, WPE) hipLaunchKernelGGL((beam_row_sample_fast_kernel<EPT, NT, WPE, PR>), dim3(rows), dim3(NT), 0, \
+    DhProfScope prof(NU ? "dh_beam_row_sample_nucleus" : "dh_beam_row_sample", 0.0, 0.0, stream);
+#define DH_FAST(EPT, NT, WPE) hipLaunchKernelGGL((beam_row_sample_fast_kernel<EPT, NT, WPE, PR, NU>), dim3(rows), dim3(NT), 0, \
         (hipStream_t)stream, logits, ldl, V, rows_per_img, beam, top_k, temperature, unk_index, noise, seed, seed_ptr, img0, \
-        step, pick_idx, pick_val, err, first_pos)
+        step, pick_idx, pick_val, err, first_pos, top_p)
     if (!exact && top_k <= 256 && V <= 512 * 8) DH_FAST(8, 512, 4);
     else if (!exact && top_k <= 256 && V <= 1024 * 16) DH_FAST(16, 1024, 8);
     else if (!exact && top_k <= 256 && V <= 1024 * 36) DH_FAST(36, 1024, 8);
     else if (!exact && top_k <= 256 && V <= 1024 * 64) DH_FAST(64, 1024, 4);
     else
-        hipLaunchKernelGGL(beam_row_sample_kernel<PR>, dim3(rows), dim3(256), 0, (hipStream_t)stream, logits, ldl, V,
+        hipLaunchKernelGGL((beam_row_sample_kernel<PR, NU>), dim3(rows), dim3(256), 0, (hipStream_t)stream, logits, ldl, V,
                            rows_per_img, beam, top_k, temperature, unk_index, noise, seed, seed_ptr, img0, step, pick_idx,
-                           pick_val, err, first_pos);
+                           pick_val, err, first_pos, top_p);
 #undef DH_FAST
     DH_LAUNCH_CHECK();
 }
@@ -839,6 +917,32 @@ extern "C" int dh_beam_row_sample_exact_prompted(const float* logits, int ldl, i
                                                  int32_t* pick_idx, float* pick_val, int32_t* err, void* stream) {
     return row_sample_launch<true>(logits, ldl, V, rows, rows_per_img, beam, top_k, temperature, unk_index, noise, seed, seed_ptr, img0, step,
                                    first_pos, pick_idx, pick_val, err, true, stream);
+}
+
+// Nucleus (top-p) row draw, every route through one entry point: the NU = true instantiations of the three kernels above.
+// exact != 0: the general kernel; else group_max != NULL: the group-guided kernel; else the single-pass kernels by V as dh_beam_row_sample
+// picks them.  first_pos != NULL: the prompted phases (prompt_row_idle).  top_p outside (0, 1) is a bad argument: 1 is the callers'
+// "no nucleus", which is the other entry points' business.
+extern "C" int dh_beam_row_sample_nucleus(const float* logits, int ldl, int V, const float* group_max, int gm_ld, int n_groups,
+                                          int group_cols, int rows, int rows_per_img, int beam, int top_k, float top_p,
+                                          float temperature, int unk_index, const float* noise, uint64_t seed, const uint64_t* seed_ptr,
+                                          int img0, int step, const int32_t* first_pos, int exact, int32_t* pick_idx, float* pick_val,
+                                          int32_t* err, void* stream) {
+    DH_REQUIRE(top_p > 0.f && top_p < 1.f);
+    if (group_max && !exact) {
+        if (first_pos)
+            return row_sample_groups_launch<true, true>(logits, ldl, V, group_max, gm_ld, n_groups, group_cols, rows, rows_per_img, beam, top_k,
+                                                        temperature, unk_index, noise, seed, seed_ptr, img0, step, first_pos, pick_idx, pick_val,
+                                                        err, stream, top_p);
+        return row_sample_groups_launch<false, true>(logits, ldl, V, group_max, gm_ld, n_groups, group_cols, rows, rows_per_img, beam, top_k,
+                                                     temperature, unk_index, noise, seed, seed_ptr, img0, step, nullptr, pick_idx, pick_val, err,
+                                                     stream, top_p);
+    }
+    if (first_pos)
+        return row_sample_launch<true, true>(logits, ldl, V, rows, rows_per_img, beam, top_k, temperature, unk_index, noise, seed, seed_ptr, img0,
+                                             step, first_pos, pick_idx, pick_val, err, exact != 0, stream, top_p);
+    return row_sample_launch<false, true>(logits, ldl, V, rows, rows_per_img, beam, top_k, temperature, unk_index, noise, seed, seed_ptr, img0,
+                                          step, nullptr, pick_idx, pick_val, err, exact != 0, stream, top_p);
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -902,6 +902,20 @@ def beam_row_sample_prompted(logits, v, rows, beam, top_k, temperature, unk_inde
             _ptr(pick_idx), _ptr(pick_val), _ptr(err), _stream())
 
 
+def beam_row_sample_nucleus(logits, v, rows, rows_per_img, beam, top_k, top_p, temperature, unk_index, noise, seed, img0, step,
+                            pick_idx, pick_val, err, seed_ptr=None, exact=False, group_max=None, first_pos=None):
+    """The row draw over the nucleus of the top-k survivors (``0 < top_p < 1``; ``dh_beam_row_sample_nucleus``, one entry point for
+    every route): ``exact`` the general kernel, else ``group_max`` the group-guided one, else the single-pass kernels; ``first_pos``
+    (int32 ``[rows // beam]``) the prompted phases."""
+    _dev(logits, noise, pick_idx, pick_val, err, first_pos, group_max)
+    assert logits.dtype == torch.float32
+    assert first_pos is None or (first_pos.dtype == torch.int32 and rows_per_img == beam and first_pos.numel() * beam == rows)
+    _launch("dh_beam_row_sample_nucleus", _ptr(logits), logits.stride(0), v, _ptr(group_max),
+            group_max.stride(0) if group_max is not None else 0, n_groups(v), GROUP_COLS, rows, rows_per_img, beam, top_k, float(top_p),
+            float(temperature), unk_index, _ptr(noise), seed, _ptr(seed_ptr), img0, step, _ptr(first_pos), int(bool(exact)),
+            _ptr(pick_idx), _ptr(pick_val), _ptr(err), _stream())
+
+
 def beam_select_prompted(pick_idx, pick_val, tokens, vals, ended, src, parent, hparent, done, end_step, n_img, beam, first_pos,
                          first_sets_ended, write_pos, t, step_index, temperature, eos_index, noise, seed, img0, seed_ptr=None):
     """``beam_select`` with the phase of every image taken from ``first_pos`` (int32 ``[n_img]``) against ``step_index``."""

@@ -65,9 +65,26 @@ def check_return_beams(return_beams):
     return return_beams
 
 
+def check_top_p(top_p):
+    """``top_p`` is a real number in ``(0, 1]`` (1.0: no nucleus, today's kernels): checked where ``check_return_beams`` is, before
+    anything runs.  A ``bool`` is a misplaced flag, not a probability.  Returns it as a float."""
+    import math
+    import numbers
+    if isinstance(top_p, bool):
+        raise ValueError("top_p must be a number in (0, 1], not a bool")
+    if not isinstance(top_p, numbers.Real):
+        raise TypeError(f"top_p must be a real number in (0, 1], not {type(top_p).__name__}")
+    top_p = float(top_p)
+    if math.isnan(top_p) or not 0.0 < top_p <= 1.0:
+        raise ValueError(f"top_p must lie in (0, 1], got {top_p}")
+    return top_p
+
+
 class BeamOverflow(RuntimeError):
     """A row had more logits at its top-k threshold than the pre-filtered samplers' candidate buffers hold (flat / constant logits):
-    the decoders catch this and repeat the batch with ``exact=True`` (the general sampler, which draws such rows over the whole row)."""
+    the decoders catch this and repeat the batch with ``exact=True`` (the general sampler, which draws such rows over the whole row).
+    With ``top_p < 1`` the general sampler has no such draw (the nucleus is taken among at most 1,024 survivors): the repeated batch
+    raises this again, with a message that says so."""
 
 
 class _TorchCpuStream:
@@ -207,11 +224,18 @@ class BeamSearchHelper:
 
     Reference signature kept: ``BeamSearchHelper(temperature, beam_size, top_k, unk_index,
     eos_index, device)`` (beam.py:7-8); ``n_img``, ``max_len`` and the rest are new keyword arguments.
+
+    ``top_p < 1`` (nucleus filtering, not in the reference): every row draw of ``step`` / ``step_prompted`` runs over the row's
+    nucleus of the top-k survivors -- with ``p = softmax(survivors / temperature)`` ordered by ``p`` descending (equal ``p``: lower
+    token index first), the survivor at sorted position ``j`` stays iff the exclusive prefix ``p[0] + ... + p[j-1]`` is ``< top_p``
+    or ``j < beam_size`` -- through ``dh_beam_row_sample_nucleus``; the candidate draw and the final draw are untouched.  The
+    default ``top_p=1.0`` makes today's calls.
     """
 
     def __init__(self, temperature=1.0, beam_size=10, top_k=50, unk_index=1, eos_index=3, device='cuda',
-                 n_img=1, max_len=25, src_len=0, seed=0, img0=0, noise_source=None, seed_tensor=None, exact=False):
+                 n_img=1, max_len=25, src_len=0, seed=0, img0=0, noise_source=None, seed_tensor=None, exact=False, top_p=1.0):
         assert beam_size <= top_k, '`beam_size` should be less than `top_k`'          # beam.py:9
+        self.top_p = check_top_p(top_p)
         self.exact = bool(exact)          # row draws through the general sampler only (see BeamOverflow)
         if beam_size > hip.MAX_BEAMS:     # one wave draws among an image's beams (dh_beam_finalize); the reference has no limit
             raise ValueError(f"beam_size <= {hip.MAX_BEAMS} supported")
@@ -281,9 +305,15 @@ class BeamSearchHelper:
         rows, v = logits.shape
         assert rows == self.n_img * self.beam_size and self.noise_source is None
         use_groups = group_max is not None and not self.exact and self.top_k <= hip.n_groups(v)
-        hip.beam_row_sample_prompted(logits, v, rows, self.beam_size, self.top_k, self.temperature, self.unk_index, None, self.seed,
-                                     self.img0, step_index, self.first_pos, self.pick_idx, self.pick_val, self.err,
-                                     seed_ptr=self.seed_tensor, exact=self.exact, group_max=group_max if use_groups else None)
+        if self.top_p < 1.0:
+            hip.beam_row_sample_nucleus(logits, v, rows, self.beam_size, self.beam_size, self.top_k, self.top_p, self.temperature,
+                                        self.unk_index, None, self.seed, self.img0, step_index, self.pick_idx, self.pick_val, self.err,
+                                        seed_ptr=self.seed_tensor, exact=self.exact, group_max=group_max if use_groups else None,
+                                        first_pos=self.first_pos)
+        else:
+            hip.beam_row_sample_prompted(logits, v, rows, self.beam_size, self.top_k, self.temperature, self.unk_index, None, self.seed,
+                                         self.img0, step_index, self.first_pos, self.pick_idx, self.pick_val, self.err,
+                                         seed_ptr=self.seed_tensor, exact=self.exact, group_max=group_max if use_groups else None)
         hip.beam_select_prompted(self.pick_idx, self.pick_val, self.tokens, self.vals, self._ended, self.src, self.parent,
                                  self.hparent, self.done, self.end_step, self.n_img, self.beam_size, self.first_pos,
                                  first_sets_ended, write_pos, t, step_index, self.temperature, self.eos_index, None, self.seed,
@@ -311,7 +341,13 @@ class BeamSearchHelper:
         v = logits.shape[1]
         if self.exact:
             group_max = None              # the general sampler reads the whole row
-        if group_max is not None and self.top_k <= hip.n_groups(v):   # k group maxima bound the k-th logit
+        if self.top_p < 1.0:              # the nucleus of the survivors: one entry point for the three routes below
+            use_groups = group_max is not None and self.top_k <= hip.n_groups(v)
+            hip.beam_row_sample_nucleus(logits, v, rows, rpi, self.beam_size, self.top_k, self.top_p, self.temperature, self.unk_index,
+                                        self._noise("row", step_index, (rows, v), logits.stride(0)), self.seed, self.img0, step_index,
+                                        self.pick_idx, self.pick_val, self.err, seed_ptr=self.seed_tensor, exact=self.exact,
+                                        group_max=group_max if use_groups else None)
+        elif group_max is not None and self.top_k <= hip.n_groups(v):   # k group maxima bound the k-th logit
             # bf16 path: the vocabulary GEMM left per-row maxima of every 64-column group (dh_vocab_logits)
             hip.beam_row_sample_groups(logits, v, group_max, rows, rpi, self.beam_size, self.top_k, self.temperature,
                                        self.unk_index, self._noise("row", step_index, (rows, v), logits.stride(0)), self.seed, self.img0,
@@ -366,10 +402,12 @@ class BeamSearchHelper:
 
     def check(self):
         """Raises like the reference does when every logit of a row was filtered (beam.py:46)."""
-        self.raise_for(int(self.err.item()))
+        self.raise_for(int(self.err.item()), self.top_p if self.exact else 1.0)
 
     @staticmethod
-    def raise_for(code):
+    def raise_for(code, top_p=1.0):
+        """``top_p < 1``: the word of a session that already ran ``exact=True`` with a nucleus -- its overflow has no further
+        fall-back."""
         if code == 0:
             return
         if code & hip.ERR_NONFINITE:
@@ -378,6 +416,9 @@ class BeamSearchHelper:
         if code & hip.ERR_ALL_FILTERED:
             raise RuntimeError("probability tensor contains either `inf`, `nan` or element < 0 "
                                "(every logit of a row was filtered: <unk> was the only top-k token)")
+        if code & hip.ERR_OVERFLOW and top_p < 1.0:
+            raise BeamOverflow(f"more than 1024 logits of a row survive its top-k filter (DH_BEAM_MAX_SURVIVORS) and top_p={top_p} takes the "
+                               "nucleus among at most that many: flat logits have no nucleus draw, exact=True included -- use top_p=1.0")
         if code & hip.ERR_OVERFLOW:
             raise BeamOverflow("more than 1024 logits of a row tie at its top-k threshold (DH_BEAM_MAX_SURVIVORS): repeat with exact=True")
         # hip.ERR_TOO_FEW (fewer positive-probability tokens than beams: top_k == beam_size with <unk> in the top-k, or
@@ -404,6 +445,11 @@ class BeamSearchHelper:
         t = self.noise_source("multinomial", self._draws - 1, shape)
         return None if t is None else t.to(device=self.device, dtype=torch.float32).reshape(shape).contiguous()
 
+    def _no_nucleus(self, what):
+        if self.top_p < 1.0:
+            raise NotImplementedError(f"{what} with top_p < 1: the nucleus lives in the batched engine's row draw (step / step_prompted); "
+                                      "the reference-style method surface has none")
+
     def filter_top_k(self, logits):
         """beam.py:32-37: IN PLACE -- entries strictly below the row's ``top_k``-th largest value and the ``unk`` column become
         ``-inf`` (ties at the threshold stay); returns its argument."""
@@ -413,6 +459,7 @@ class BeamSearchHelper:
     def sample_k_indices(self, logits, k=None):
         """beam.py:39-48: ``torch.multinomial(softmax(logits / temperature), k)`` (no replacement) as an Exp(1) race on the
         device; ``logits`` is ``[n, V]`` -> int64 ``[n, k]`` or 1-D ``[V]`` -> ``[k]`` (the candidate draws, rnn_models.py:120)."""
+        self._no_nucleus("sample_k_indices")
         k = self.beam_size if k is None else int(k)
         x = logits if logits.dim() == 2 else logits.reshape(1, -1)
         if x.dtype != torch.float32 or x.stride(-1) != 1:
@@ -437,6 +484,7 @@ class BeamSearchHelper:
         """beam.py:55-108.  ``logits [n, V]`` fp32 (filtered IN PLACE, as the reference does), ``sample_seq [n, L]`` int64,
         ``sample_val [n]`` or ``[n, 1]``, ``self.has_ended [n]`` -> ``(prev_seqs, prev_vals), (new_ind, new_val)`` over the
         ``n_cand = sum(1 if ended else beam_size)`` candidates; ``self.has_ended`` becomes the ``[n_cand]`` bool flags."""
+        self._no_nucleus("process_logits")
         b = self.beam_size
         logits = self.filter_top_k(logits)
         new_ind = self.sample_k_indices(logits, k=b)

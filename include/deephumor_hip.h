@@ -25,7 +25,7 @@
 extern "C" {
 #endif
 
-#define DH_ABI_VERSION 33
+#define DH_ABI_VERSION 34
 
 enum { DH_OK = 0, DH_ERR_BAD_ARG = 1, DH_ERR_UNSUPPORTED = 2, DH_ERR_LAUNCH = 3 };
 enum { DH_F32 = 0, DH_BF16 = 1,          /* storage type of activations and weights */
@@ -512,6 +512,25 @@ int dh_beam_select_prompted(const int32_t* pick_idx, const float* pick_val, int3
                             const int32_t* first_pos, int first_sets_ended, int write_pos, int t, int step_index,
                             float temperature, int eos_index, const float* noise, uint64_t seed,
                             const uint64_t* seed_ptr, int img0, void* stream);
+
+/* ---- Nucleus (top-p) row draw: dh_beam_row_sample on the nucleus of the top-k survivors, every route through ONE entry point.
+ * 0 < top_p < 1 (anything else, 1 included, is DH_ERR_BAD_ARG: without a nucleus the entry points above are the call).  Per row:
+ *   1. survivors as dh_beam_row_sample: logits >= the top_k-th largest, ties kept, unk dropped; p = softmax(survivors / temperature);
+ *   2. survivors ordered by p descending, equal p by token index ascending;
+ *   3. the survivor at sorted position j stays iff the exclusive prefix p[0] + ... + p[j-1] (fp32) is < top_p, or j < beam;
+ *   4. the race of dh_beam_row_sample over those that stay: `beam` winners of p / Exp(1), ties to the lower index.  The noise is indexed
+ *      by token id (Philox counter or noise[row, token]) as there; pick_val = log_softmax over the picks' untempered logits.
+ * DH_BEAM_ERR_TOO_FEW keeps its meaning (fewer than `beam` survivors BEFORE the cut).  A row with more than DH_BEAM_MAX_SURVIVORS survivors
+ * flags DH_BEAM_ERR_OVERFLOW on every route, exact included: there is no nucleus over a row in global memory.
+ *   exact != 0       the general kernel (dh_beam_row_sample_exact's), group_max ignored;
+ *   group_max != NULL (exact == 0) dh_beam_row_sample_groups' route: [rows, gm_ld] group maxima, n_groups groups of group_cols columns;
+ *   otherwise        dh_beam_row_sample's choice of kernel by V and top_k (group_max, gm_ld, n_groups, group_cols unused);
+ *   first_pos != NULL the prompted phases of the *_prompted entry points ([rows / beam] int32, rows_per_img == beam). */
+int dh_beam_row_sample_nucleus(const float* logits, int ldl, int V, const float* group_max, int gm_ld, int n_groups,
+                               int group_cols, int rows, int rows_per_img, int beam, int top_k, float top_p,
+                               float temperature, int unk_index, const float* noise, uint64_t seed, const uint64_t* seed_ptr,
+                               int img0, int step, const int32_t* first_pos, int exact, int32_t* pick_idx, float* pick_val,
+                               int32_t* err, void* stream);
 
 /* ---- BeamSearchHelper's METHOD surface (deephumor/models/beam.py:32-108), for callers that drive the helper the way the
  * reference's own generate() loops do (rnn_models.py:87-128, transformers.py:532-569): one image, host-driven, tensors of the
