@@ -54,8 +54,9 @@ __device__ __forceinline__ float lf_tanh(float x) {
     return copysignf(t, x);
 }
 
-// BM = 64 (default): 64 x 64 tiles (640 workgroups at 1280 rows x 2048 gate columns, 2-3 per CU).  BM = 160 (opt-in, see the
-// entry point): 160 x 64 tiles, 80 x 32 per wave -- at 1280 rows exactly 256 workgroups, one per CU.
+// BM = 64: 64 x 64 tiles (640 workgroups at 1280 rows x 2048 gate columns, 2-3 per CU); the only form the entry point launches,
+// with NS = 4, 3 or 2 slabs by workgroup count.  The template also compiles for BM = 160 (160 x 64 tiles, 80 x 32 per wave), which
+// nothing instantiates: the wait counts 7 / 14 / 21 / 28 of lf_wait_vmcnt belong to it and are unreachable.
 template <typename OT, int NS, int BM = 64>
 __global__ __launch_bounds__(256) void lstm_layer_fused_kernel(LstmFusedParams p) {
     constexpr int BN = 64, BK = 64, NW = 4, WAVES_M = 2;

@@ -96,6 +96,26 @@ def attn_cross_decode_planes(q, kv, keymask, n_img, rows_per_img, s, d, n_heads,
     return out
 
 
+def lstm_prepare_f32x(emb, img_emb, tokens, tok_pos, hparent, h_prev, c_prev, xcat0, xcatl, c_cur, xcat0_planes, xcatl_planes, rows,
+                      rows_per_img, row_mult, rows_total, n_layers, e, hh):
+    """``dh_lstm_prepare_f32x``: ``hip.lstm_prepare`` of fp32 rows, which also stores them as planes: ``xcat0_planes [2, rows, E + Hh]``,
+    ``xcatl_planes [n_layers - 1, 2, rows, 2 Hh]`` (the h halves; the x halves are ``lstm_cell_f32x``'s)."""
+    hip._dev(emb, img_emb, tokens, hparent, h_prev, c_prev, xcat0, xcatl, c_cur, xcat0_planes, xcatl_planes)
+    assert xcat0.dtype == torch.float32 and xcat0_planes.dtype == torch.float16
+    hip._launch("dh_lstm_prepare_f32x", hip._ptr(emb), hip._ptr(img_emb), hip._ptr(tokens), tokens.stride(0) if tokens is not None else 0,
+                tok_pos, hip._ptr(hparent), hip._ptr(h_prev), hip._ptr(c_prev), hip._ptr(xcat0), hip._ptr(xcatl), hip._ptr(c_cur),
+                hip._ptr(xcat0_planes), hip._ptr(xcatl_planes), rows, rows_per_img, row_mult, rows_total, n_layers, e, hh, hip._stream())
+
+
+def lstm_cell_f32x(gates, c_cur, h_new, c_new, h_out, ld_out, h_planes, plane, ld_planes, rows, row_mult, hh):
+    """``dh_lstm_cell_f32x``: ``hip.lstm_cell`` of fp32 rows, which also stores the new hidden rows as planes: hi at ``h_planes``, lo
+    ``plane`` elements behind it, row stride ``ld_planes``."""
+    hip._dev(gates, c_cur, h_new, c_new, h_out, h_planes)
+    assert h_new.dtype == torch.float32 and h_planes.dtype == torch.float16
+    hip._launch("dh_lstm_cell_f32x", hip._ptr(gates), hip._ptr(c_cur), hip._ptr(h_new), hip._ptr(c_new), hip._ptr(h_out), ld_out,
+                hip._ptr(h_planes), plane, ld_planes, rows, row_mult, hh, hip._stream())
+
+
 def pack_conv1x1(w_planes):
     """The planes of ``hip.split_f32x(w [Cout, Cin])`` in MFMA fragment order ``[2, Cin / 32, Cout / 16, 64, 8]`` for
     ``conv1x1_stream``; None when the layer is not one the streaming kernel takes at any row count."""
