@@ -945,6 +945,108 @@ extern "C" int dh_beam_row_sample_nucleus(const float* logits, int ldl, int V, c
                                           step, nullptr, pick_idx, pick_val, err, exact != 0, stream, top_p);
 }
 
+// ---- history-dependent logit edits (no_repeat_ngram_size, repetition_penalty) in front of the row draw ---------------------------
+// One workgroup per logits row; the row's own history h[0 .. pos) is columns < pos of its token row (r * tok_row_mult: the dense
+// first step has one logits row per image and the image's tokens at row img * beam).  Ids outside [0, V) take part in the n-gram
+// comparison as they are and are never a column.  Three phases, a workgroup barrier between them:
+//   1. penalty != 1: every history position READS its column (into LDS), barrier, every position WRITES x < 0 ? x * penalty : x / penalty of
+//      the value it read.  All reads of the row precede all writes, so the positions of one token store the same word: each
+//      distinct token is damped exactly once without a de-duplication pass (-inf stays -inf: -inf * penalty, penalty > 0).
+//   2. ngram = n >= 1, pos >= n: position j in [0, pos - n] whose n - 1 tokens equal the row's last n - 1 bans h[j + n - 1]
+//      (-inf; n == 1: every token of the history).  After the barrier, so a ban wins over the penalty's store to the same column.
+//   3. group_max != NULL: every group that received a store is put on a list once (atomicExch on its flag), and after the barrier
+//      (workgroup-scope release / acquire: the stores above are visible to the other waves of the CU) one wave per listed group reads
+//      the group's columns back and stores their fp32 maximum.  CONVENTION: the maximum runs over the group's REAL columns (< V)
+//      only.  dh_vocab_logits and dh_linear_f32xp do the same (`n < N` in their epilogues); dh_vocab_logits_wreg folds the written pad
+//      columns of the last partial group in, which are copies of column V - 1 (pack_vocab_weights), so its word is the real columns'
+//      maximum too -- until column V - 1 is edited: the pads then keep the old value, and a maximum over them would be one that no
+//      column the sampler reads attains (its bound needs the k-th largest group maximum <= the k-th largest logit).  A group whose
+//      real columns are all -inf gets -inf; groups without a store, groups past V among them, are not written.
+// Forced / idle rows of a prompted launch leave before the first barrier (prompt_row_idle with step = pos).
+__global__ __launch_bounds__(256) void beam_history_logits_kernel(
+    float* logits, int ldl, int V, float* gmax, int gm_ld, int n_groups, int gcols, const int32_t* __restrict__ tokens, int tok_ld,
+    int tok_row_mult, int pos, int rows_per_img, const int32_t* __restrict__ first_pos, int ngram, float penalty) {
+    constexpr int NT = 256, PPT = DH_BEAM_MAX_HISTORY / NT, MAXG = 1024;
+    __shared__ int hist[DH_BEAM_MAX_HISTORY];
+    __shared__ float hval[DH_BEAM_MAX_HISTORY];      // the penalty's loaded logits, one per history position
+    __shared__ int gflag[MAXG], glist[MAXG];
+    __shared__ int s_ng;
+    const int rc = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    if (first_pos && prompt_row_idle(first_pos, rc, rows_per_img, pos)) return;
+    float* row = logits + (size_t)rc * ldl;
+    const int32_t* h = tokens + (size_t)rc * tok_row_mult * tok_ld;
+    const int L = pos;
+    for (int i = tid; i < L; i += NT) hist[i] = h[i];
+    if (gmax)
+        for (int g = tid; g < n_groups; g += NT) gflag[g] = 0;
+    if (tid == 0) s_ng = 0;
+    __syncthreads();
+    auto mark = [&](int t) {              // column t (< V <= n_groups * gcols) received a store
+        if (gmax) {
+            const int g = t / gcols;
+            if (atomicExch(&gflag[g], 1) == 0) glist[atomicAdd(&s_ng, 1)] = g;
+        }
+    };
+    if (penalty != 1.f) {
+        int tk[PPT];
+#pragma unroll
+        for (int e = 0; e < PPT; ++e) {
+            const int i = tid + e * NT;
+            const int t = i < L ? hist[i] : -1;
+            tk[e] = (t >= 0 && t < V) ? t : -1;
+            hval[i] = tk[e] >= 0 ? row[tk[e]] : 0.f;
+        }
+        // Every load of the row has completed before any store to it: a thread parks what it loaded in LDS, which needs the loaded
+        // word itself, before it reaches the barrier, and takes its own words back behind it.
+        __syncthreads();
+#pragma unroll
+        for (int e = 0; e < PPT; ++e)
+            if (tk[e] >= 0) {
+                const float x = hval[tid + e * NT];
+                row[tk[e]] = x < 0.f ? x * penalty : __fdiv_rn(x, penalty);
+                mark(tk[e]);
+            }
+        __syncthreads();
+    }
+    if (ngram >= 1 && L >= ngram) {
+        const int m = ngram - 1, p0 = L - m;
+        for (int j = tid; j + ngram <= L; j += NT) {
+            bool eq = true;
+            for (int k = 0; k < m && eq; ++k) eq = hist[j + k] == hist[p0 + k];
+            const int t = hist[j + m];
+            if (eq && t >= 0 && t < V) { row[t] = -INFINITY; mark(t); }
+        }
+    }
+    if (gmax) {
+        __threadfence_block();
+        __syncthreads();
+        const int ng = s_ng;
+        for (int q = wave; q < ng; q += NT / 64) {
+            const int g = glist[q], c = g * gcols + lane;
+            float v = (lane < gcols && c < V) ? row[c] : -INFINITY;
+#pragma unroll
+            for (int s = 32; s > 0; s >>= 1) v = fmaxf(v, __shfl_xor(v, s, 64));
+            if (lane == 0) gmax[(size_t)rc * gm_ld + g] = v;
+        }
+    }
+}
+
+extern "C" int dh_beam_history_logits(float* logits, int ldl, int V, float* group_max, int gm_ld, int n_groups, int group_cols,
+                                      const int32_t* tokens, int tok_ld, int tok_row_mult, int pos, int rows, int rows_per_img,
+                                      const int32_t* first_pos, int ngram, float penalty, void* stream) {
+    DH_REQUIRE(logits && tokens && rows > 0 && rows_per_img > 0 && V > 0 && ldl >= V && tok_row_mult >= 1);
+    DH_REQUIRE(pos >= 0 && pos <= tok_ld && pos <= DH_BEAM_MAX_HISTORY);
+    DH_REQUIRE(ngram >= 0 && penalty > 0.f && penalty < INFINITY);            // (a NaN penalty fails both comparisons)
+    DH_REQUIRE(ngram > 0 || penalty != 1.f);                                   // both controls off: the caller makes no launch
+    DH_REQUIRE(!group_max || (n_groups > 0 && n_groups <= 1024 && gm_ld >= n_groups && group_cols > 0 && group_cols <= 64 &&
+                              (long long)n_groups * group_cols >= V));         // dh_beam_row_sample_groups' contract
+    DH_REQUIRE(!first_pos || rows % rows_per_img == 0);
+    DhProfScope prof("dh_beam_history_logits", 0.0, 0.0, stream);
+    hipLaunchKernelGGL(beam_history_logits_kernel, dim3(rows), dim3(256), 0, (hipStream_t)stream, logits, ldl, V, group_max, gm_ld,
+                       n_groups, group_cols, tokens, tok_ld, tok_row_mult, pos, rows_per_img, first_pos, ngram, penalty);
+    DH_LAUNCH_CHECK();
+}
+
 // ------------------------------------------------------------------------------------------------
 
 template <int MB, bool PR>

@@ -12,7 +12,7 @@ import torch
 from . import _build
 
 from ._abi import (ABI_VERSION, BF16, BF16_OUT_F32, ERR_ALL_FILTERED, ERR_NONFINITE, ERR_OVERFLOW, ERR_TOO_FEW, F16, F16_OUT_F32, F32,  # noqa: F401
-                   HALF_DTYPES, MAX_BEAMS, SIGNATURES, LnFold, LstmLayer, LstmModel, LstmScratch, TrLayer, TrModel, TrScratch)
+                   HALF_DTYPES, MAX_BEAMS, MAX_HISTORY, SIGNATURES, LnFold, LstmLayer, LstmModel, LstmScratch, TrLayer, TrModel, TrScratch)
 
 _c = ctypes
 _P, _I, _F, _U64 = _c.c_void_p, _c.c_int, _c.c_float, _c.c_uint64
@@ -914,6 +914,21 @@ def beam_row_sample_nucleus(logits, v, rows, rows_per_img, beam, top_k, top_p, t
             group_max.stride(0) if group_max is not None else 0, n_groups(v), GROUP_COLS, rows, rows_per_img, beam, top_k, float(top_p),
             float(temperature), unk_index, _ptr(noise), seed, _ptr(seed_ptr), img0, step, _ptr(first_pos), int(bool(exact)),
             _ptr(pick_idx), _ptr(pick_val), _ptr(err), _stream())
+
+
+def beam_history_logits(logits, v, tokens, tok_row_mult, pos, rows, rows_per_img, ngram, penalty, group_max=None, first_pos=None):
+    """``dh_beam_history_logits``: the ``no_repeat_ngram_size`` / ``repetition_penalty`` edits of fp32 ``logits [rows, V]`` in place,
+    from every row's own history ``tokens[r * tok_row_mult, :pos]`` (int32); with ``group_max`` the 64-column group maxima of every
+    edited group are recomputed (pass it exactly when the sampler that follows reads it); ``first_pos`` (int32
+    ``[rows // rows_per_img]``): the prompted phases."""
+    _dev(logits, tokens, group_max, first_pos)
+    assert logits.dtype == torch.float32 and logits.stride(1) == 1 and tokens.dtype == torch.int32 and tokens.stride(1) == 1
+    assert group_max is None or group_max.dtype == torch.float32
+    assert first_pos is None or (first_pos.dtype == torch.int32 and first_pos.numel() * rows_per_img == rows)
+    assert (rows - 1) * tok_row_mult < tokens.shape[0]
+    _launch("dh_beam_history_logits", _ptr(logits), logits.stride(0), v, _ptr(group_max),
+            group_max.stride(0) if group_max is not None else 0, n_groups(v), GROUP_COLS, _ptr(tokens), tokens.stride(0), tok_row_mult,
+            pos, rows, rows_per_img, _ptr(first_pos), int(ngram), float(penalty), _stream())
 
 
 def beam_select_prompted(pick_idx, pick_val, tokens, vals, ended, src, parent, hparent, done, end_step, n_img, beam, first_pos,

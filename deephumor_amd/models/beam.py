@@ -11,6 +11,8 @@ noise either from a counter-based Philox stream keyed by ``(seed, global image i
 token)`` -- results do not depend on batch composition or rank layout -- or, for RNG-replay parity
 tests, from caller-supplied tensors (``noise_source``).
 """
+import math
+import numbers
 import os
 from typing import NamedTuple
 
@@ -68,8 +70,6 @@ def check_return_beams(return_beams):
 def check_top_p(top_p):
     """``top_p`` is a real number in ``(0, 1]`` (1.0: no nucleus, today's kernels): checked where ``check_return_beams`` is, before
     anything runs.  A ``bool`` is a misplaced flag, not a probability.  Returns it as a float."""
-    import math
-    import numbers
     if isinstance(top_p, bool):
         raise ValueError("top_p must be a number in (0, 1], not a bool")
     if not isinstance(top_p, numbers.Real):
@@ -78,6 +78,32 @@ def check_top_p(top_p):
     if math.isnan(top_p) or not 0.0 < top_p <= 1.0:
         raise ValueError(f"top_p must lie in (0, 1], got {top_p}")
     return top_p
+
+
+def check_repeat(no_repeat_ngram_size=0, repetition_penalty=1.0, max_len=None):
+    """``no_repeat_ngram_size`` is an ``int >= 0`` (0: off; a ``bool`` is a misplaced flag, a float a ``TypeError``) and
+    ``repetition_penalty`` a finite real number ``> 0`` (1.0: off; no ``bool``): checked where ``check_top_p`` is, before anything
+    runs.  With ``max_len`` and a control on, a history longer than the kernel looks at (``hip.MAX_HISTORY`` columns) is a
+    ``ValueError`` here, not a failed launch in the middle of a batch.  Returns ``(int, float)``."""
+    n, pen = no_repeat_ngram_size, repetition_penalty
+    if isinstance(n, bool):
+        raise ValueError("no_repeat_ngram_size must be an int >= 0, not a bool")
+    if not isinstance(n, numbers.Integral):
+        raise TypeError(f"no_repeat_ngram_size must be an int >= 0, not {type(n).__name__}")
+    n = int(n)
+    if n < 0:
+        raise ValueError(f"no_repeat_ngram_size must be >= 0, got {n}")
+    if isinstance(pen, bool):
+        raise ValueError("repetition_penalty must be a finite number > 0, not a bool")
+    if not isinstance(pen, numbers.Real):
+        raise TypeError(f"repetition_penalty must be a finite real number > 0, not {type(pen).__name__}")
+    pen = float(pen)
+    if not (math.isfinite(pen) and pen > 0.0):
+        raise ValueError(f"repetition_penalty must be finite and > 0, got {pen}")
+    if max_len is not None and (n > 0 or pen != 1.0) and int(max_len) > hip.MAX_HISTORY:
+        raise ValueError(f"no_repeat_ngram_size / repetition_penalty look at a row history of at most {hip.MAX_HISTORY} tokens "
+                         f"(DH_BEAM_MAX_HISTORY): max_len={int(max_len)} is above it")
+    return n, pen
 
 
 class BeamOverflow(RuntimeError):
@@ -230,12 +256,23 @@ class BeamSearchHelper:
     token index first), the survivor at sorted position ``j`` stays iff the exclusive prefix ``p[0] + ... + p[j-1]`` is ``< top_p``
     or ``j < beam_size`` -- through ``dh_beam_row_sample_nucleus``; the candidate draw and the final draw are untouched.  The
     default ``top_p=1.0`` makes today's calls.
+
+    ``no_repeat_ngram_size = n > 0`` / ``repetition_penalty != 1`` (not in the reference either): in front of every row draw of
+    ``step`` / ``step_prompted`` one launch of ``dh_beam_history_logits`` edits the logits IN PLACE from every row's own history (the
+    token table's columns ``< write_pos``): each distinct token of the history is damped CTRL-style (``x < 0 ? x * penalty :
+    x / penalty``), then every token that would complete an n-gram the row already holds becomes ``-inf``; the 64-column group
+    maxima are repaired when -- and only when -- the sampler that follows reads them.  A caller's ``logits_hook`` runs before
+    ``step`` and therefore sees the model's raw logits.  Deterministic, so it composes with ``rng="torch"``, ``noise_source``,
+    ``exact``, streams and hipGraph capture (the position is a launch constant).  The defaults ``0`` / ``1.0`` make no launch.
     """
 
     def __init__(self, temperature=1.0, beam_size=10, top_k=50, unk_index=1, eos_index=3, device='cuda',
-                 n_img=1, max_len=25, src_len=0, seed=0, img0=0, noise_source=None, seed_tensor=None, exact=False, top_p=1.0):
+                 n_img=1, max_len=25, src_len=0, seed=0, img0=0, noise_source=None, seed_tensor=None, exact=False, top_p=1.0,
+                 no_repeat_ngram_size=0, repetition_penalty=1.0):
         assert beam_size <= top_k, '`beam_size` should be less than `top_k`'          # beam.py:9
         self.top_p = check_top_p(top_p)
+        self.no_repeat_ngram_size, self.repetition_penalty = check_repeat(no_repeat_ngram_size, repetition_penalty, max_len)
+        self._history_edits = self.no_repeat_ngram_size > 0 or self.repetition_penalty != 1.0
         self.exact = bool(exact)          # row draws through the general sampler only (see BeamOverflow)
         if beam_size > hip.MAX_BEAMS:     # one wave draws among an image's beams (dh_beam_finalize); the reference has no limit
             raise ValueError(f"beam_size <= {hip.MAX_BEAMS} supported")
@@ -305,6 +342,9 @@ class BeamSearchHelper:
         rows, v = logits.shape
         assert rows == self.n_img * self.beam_size and self.noise_source is None
         use_groups = group_max is not None and not self.exact and self.top_k <= hip.n_groups(v)
+        if self._history_edits:
+            hip.beam_history_logits(logits, v, self.tokens, 1, write_pos, rows, self.beam_size, self.no_repeat_ngram_size,
+                                    self.repetition_penalty, group_max=group_max if use_groups else None, first_pos=self.first_pos)
         if self.top_p < 1.0:
             hip.beam_row_sample_nucleus(logits, v, rows, self.beam_size, self.beam_size, self.top_k, self.top_p, self.temperature,
                                         self.unk_index, None, self.seed, self.img0, step_index, self.pick_idx, self.pick_val, self.err,
@@ -339,15 +379,19 @@ class BeamSearchHelper:
         rpi = 1 if first else self.beam_size
         assert rows == self.n_img * rpi
         v = logits.shape[1]
-        if self.exact:
-            group_max = None              # the general sampler reads the whole row
+        # the general sampler reads the whole row; otherwise k group maxima bound the k-th logit.  Decided ONCE: the history pass
+        # repairs the maxima exactly when the sampler below reads them
+        use_groups = group_max is not None and not self.exact and self.top_k <= hip.n_groups(v)
+        if self._history_edits:           # no_repeat_ngram_size / repetition_penalty: the row's own history edits its logits first
+            hip.beam_history_logits(logits, v, self.tokens, self.beam_size if first else 1, write_pos, rows, rpi,
+                                    self.no_repeat_ngram_size, self.repetition_penalty,
+                                    group_max=group_max if use_groups else None)
         if self.top_p < 1.0:              # the nucleus of the survivors: one entry point for the three routes below
-            use_groups = group_max is not None and self.top_k <= hip.n_groups(v)
             hip.beam_row_sample_nucleus(logits, v, rows, rpi, self.beam_size, self.top_k, self.top_p, self.temperature, self.unk_index,
                                         self._noise("row", step_index, (rows, v), logits.stride(0)), self.seed, self.img0, step_index,
                                         self.pick_idx, self.pick_val, self.err, seed_ptr=self.seed_tensor, exact=self.exact,
                                         group_max=group_max if use_groups else None)
-        elif group_max is not None and self.top_k <= hip.n_groups(v):   # k group maxima bound the k-th logit
+        elif use_groups:
             # bf16 path: the vocabulary GEMM left per-row maxima of every 64-column group (dh_vocab_logits)
             hip.beam_row_sample_groups(logits, v, group_max, rows, rpi, self.beam_size, self.top_k, self.temperature,
                                        self.unk_index, self._noise("row", step_index, (rows, v), logits.stride(0)), self.seed, self.img0,
@@ -446,6 +490,9 @@ class BeamSearchHelper:
         return None if t is None else t.to(device=self.device, dtype=torch.float32).reshape(shape).contiguous()
 
     def _no_nucleus(self, what):
+        if self._history_edits:
+            raise NotImplementedError(f"{what} with no_repeat_ngram_size / repetition_penalty: the history edits live in the batched "
+                                      "engine's row draw (step / step_prompted); the reference-style method surface has none")
         if self.top_p < 1.0:
             raise NotImplementedError(f"{what} with top_p < 1: the nucleus lives in the batched engine's row draw (step / step_prompted); "
                                       "the reference-style method surface has none")

@@ -15,7 +15,7 @@ from torch import nn
 
 from .. import hip
 from ._f32x_guard import f32x_guarded
-from .beam import BeamCaptions, BeamOverflow, BeamSearchHelper, call_logits_hook, check_return_beams, check_top_p, check_ids, check_lengths, classifier_must_be_finite, make_noise_source, prompt_session_inputs, resolve_seed, run_interleaved, warn_overflow_retry
+from .beam import BeamCaptions, BeamOverflow, BeamSearchHelper, call_logits_hook, check_return_beams, check_top_p, check_repeat, check_ids, check_lengths, classifier_must_be_finite, make_noise_source, prompt_session_inputs, resolve_seed, run_interleaved, warn_overflow_retry
 from .encoders import _Planned
 
 
@@ -176,7 +176,8 @@ class LSTMDecoder(_Planned, nn.Module):
     @f32x_guarded
     def generate_batch(self, image_emb, caption=None, max_len=25, temperature=1.0, beam_size=10, top_k=50,
                        eos_index=3, seed=None, img0=0, noise_source=None, logits_hook=None, streams=1, seed_tensor=None,
-                       defer_check=False, early_stop_every=0, exact=False, rng=None, *, caption_lengths=None, return_beams=False, top_p=1.0):
+                       defer_check=False, early_stop_every=0, exact=False, rng=None, *, caption_lengths=None, return_beams=False, top_p=1.0,
+                       no_repeat_ngram_size=0, repetition_penalty=1.0):
         """Batched beam-search sampling for ``image_emb [N, 1, E]`` or ``[N, E]``.
 
         Returns ``(tokens int64 [N, max_len] zero-padded, lengths int64 [N])``; row ``i`` equals
@@ -201,9 +202,16 @@ class LSTMDecoder(_Planned, nn.Module):
         ``top_p`` (keyword only, a number in ``(0, 1]``): nucleus filtering beside ``top_k`` -- every row draw runs over the smallest
         set of the row's top-k survivors, most probable first, whose probabilities reach ``top_p`` (never fewer than ``beam_size``;
         the exact rule: ``BeamSearchHelper``).  ``1.0``, the default, is the call without the keyword: same launches, same bits.
-        Flat logits (more than 1,024 survivors) raise ``BeamOverflow`` with ``top_p < 1``."""
+        Flat logits (more than 1,024 survivors) raise ``BeamOverflow`` with ``top_p < 1``.
+        ``no_repeat_ngram_size=n`` (keyword only, int ``>= 0``): no row draws a token that would complete an n-gram its own history
+        (prompt included) already holds; ``repetition_penalty`` (keyword only, finite ``> 0``): every distinct token of the row's
+        history has its logit ``x`` replaced by ``x * penalty`` if ``x < 0`` else ``x / penalty`` (CTRL).  Penalty first, ban second,
+        one launch of ``dh_beam_history_logits`` in front of every row draw (``BeamSearchHelper``); ``logits_hook`` still sees the
+        model's raw logits.  ``0`` / ``1.0``, the defaults, are the call without the keywords: same launches, same bits.  ``max_len``
+        above ``hip.MAX_HISTORY`` with a control on is a ``ValueError``."""
         check_return_beams(return_beams)
         top_p = check_top_p(top_p)
+        no_repeat_ngram_size, repetition_penalty = check_repeat(no_repeat_ngram_size, repetition_penalty, max_len)
         self._check_mode()
         plan = self._get_plan()
         classifier_must_be_finite(plan)
@@ -230,7 +238,8 @@ class LSTMDecoder(_Planned, nn.Module):
             cap, first_pos, host = prompts
             pmin, pmax = (min(host[lo:hi]), max(host[lo:hi])) if host is not None else (0, cap.shape[1])
             helper = BeamSearchHelper(temperature, beam_size, top_k, eos_index=eos_index, device=dev, n_img=n, max_len=max_len,
-                                      seed=seed, img0=img0 + lo, seed_tensor=seed_tensor, exact=exact[0], top_p=top_p)
+                                      seed=seed, img0=img0 + lo, seed_tensor=seed_tensor, exact=exact[0], top_p=top_p,
+                                      no_repeat_ngram_size=no_repeat_ngram_size, repetition_penalty=repetition_penalty)
             helper.set_prompts(cap[lo:hi], first_pos[lo:hi])
             st = self._State(self, plan, n, b, dev)
             logits = torch.empty((r, (self.num_tokens + 255) // 256 * 256), device=dev)[:, :self.num_tokens]
@@ -265,7 +274,8 @@ class LSTMDecoder(_Planned, nn.Module):
             helper = BeamSearchHelper(temperature, beam_size, top_k, eos_index=eos_index, device=dev, n_img=n,
                                       max_len=eff_len, seed=seed, img0=img0 + lo,
                                       noise_source=make_noise_source(rng, rng_seed, noise_source, lo, hi, img0, rng_state0), seed_tensor=seed_tensor,
-                                      exact=exact[0], top_p=top_p)
+                                      exact=exact[0], top_p=top_p,
+                                      no_repeat_ngram_size=no_repeat_ngram_size, repetition_penalty=repetition_penalty)
             pos = 0
             if caption is not None:
                 pos = caption.shape[1]
@@ -314,8 +324,8 @@ class LSTMDecoder(_Planned, nn.Module):
     def generate(self, image_emb, caption=None, max_len=25,
                  temperature=1.0, beam_size=10, top_k=50, eos_index=3, **kw):
         """Single-image API of the reference (rnn_models.py:48-49): ``image_emb [1, 1, E]`` ->
-        1-D int64 token tensor; with ``return_beams=True`` the image's ``BeamCaptions`` (``N = 1``, nothing squeezed).  ``top_p`` (in ``kw``): see
-        ``generate_batch``."""
+        1-D int64 token tensor; with ``return_beams=True`` the image's ``BeamCaptions`` (``N = 1``, nothing squeezed).  ``top_p``,
+        ``no_repeat_ngram_size``, ``repetition_penalty`` (in ``kw``): see ``generate_batch``."""
         res = self.generate_batch(image_emb, caption=caption, max_len=max_len, temperature=temperature,
                                   beam_size=beam_size, top_k=top_k, eos_index=eos_index, **kw)
         return self.single_output(res, caption, max_len, beam_size)

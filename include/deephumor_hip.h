@@ -46,6 +46,7 @@ enum { DH_BEAM_ERR_ALL_FILTERED = 1,   /* every logit filtered (-inf): reference
                                           RuntimeError (beam.py:46); the kernels hand on a finite dummy pick (token 0) */
 #define DH_BEAM_MAX_SURVIVORS 1024
 #define DH_BEAM_MAX_BEAMS 64
+#define DH_BEAM_MAX_HISTORY 1024     /* longest row history dh_beam_history_logits looks at (token columns < pos) */
 
 int dh_abi_version(void);
 const char* dh_error_string(int code);
@@ -531,6 +532,26 @@ int dh_beam_row_sample_nucleus(const float* logits, int ldl, int V, const float*
                                float temperature, int unk_index, const float* noise, uint64_t seed, const uint64_t* seed_ptr,
                                int img0, int step, const int32_t* first_pos, int exact, int32_t* pick_idx, float* pick_val,
                                int32_t* err, void* stream);
+
+/* ---- History-dependent logit edits in front of a row draw: no_repeat_ngram_size and repetition_penalty, IN PLACE on fp32 logits
+ * [rows, ldl], one launch.  Logits row r reads its history h[0 .. pos) from tokens[r * tok_row_mult, 0 .. pos) (int32, row stride tok_ld):
+ * tok_row_mult = beam for the dense first step (logits [n_img, V], image i's tokens at row i * beam), 1 otherwise.  Ids outside [0, V)
+ * are never a column (they still take part in the n-gram comparison).  Per row, in this order:
+ *   1. penalty != 1: for every DISTINCT token t of h, x = logits[t] becomes x < 0 ? x * penalty : x / penalty (fp32, correctly
+ *      rounded division; once per token however often it occurs; -inf stays -inf);
+ *   2. ngram = n >= 1 and pos >= n: for every j in [0, pos - n] with h[j .. j+n-2] == h[pos-n+1 .. pos-1], logits[h[j+n-1]] = -inf
+ *      (n == 1: every token of h).  A banned column is -inf whatever the penalty did;
+ *   3. group_max != NULL ([rows, gm_ld], n_groups groups of group_cols columns: dh_beam_row_sample_groups' contract): every group
+ *      holding a column that step 1 or 2 stored to is recomputed as the exact fp32 maximum of the row's stored logits over the
+ *      group's real columns (< V; pad columns a producer wrote are not looked at), -inf if they are all -inf.  Other groups,
+ *      other logits are not written.  Pass group_max exactly when the sampler that follows reads it.
+ * first_pos != NULL ([rows / rows_per_img] int32): the prompted phases with step = pos -- rows the *_prompted samplers do not
+ * draw from (forced images; all but the base row of an image at its first step) are left untouched.
+ * pos <= tok_ld and <= DH_BEAM_MAX_HISTORY, ngram >= 0 (0: off), penalty finite and > 0 (1: off); both off is DH_ERR_BAD_ARG: the
+ * caller makes no launch then.  pos is a launch constant like `step`, so the call can be captured into a hipGraph. */
+int dh_beam_history_logits(float* logits, int ldl, int V, float* group_max, int gm_ld, int n_groups, int group_cols,
+                           const int32_t* tokens, int tok_ld, int tok_row_mult, int pos, int rows, int rows_per_img,
+                           const int32_t* first_pos, int ngram, float penalty, void* stream);
 
 /* ---- BeamSearchHelper's METHOD surface (deephumor/models/beam.py:32-108), for callers that drive the helper the way the
  * reference's own generate() loops do (rnn_models.py:87-128, transformers.py:532-569): one image, host-driven, tensors of the
