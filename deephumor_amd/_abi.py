@@ -10,6 +10,7 @@ HALF_DTYPES = (torch.bfloat16, torch.float16)       # the two 16-bit storage / M
 ERR_ALL_FILTERED, ERR_OVERFLOW, ERR_TOO_FEW, ERR_NONFINITE = 1, 2, 4, 8
 MAX_BEAMS = 64
 MAX_HISTORY = 1024          # DH_BEAM_MAX_HISTORY: the longest row history dh_beam_history_logits looks at
+MAX_BAD_WORDS, MAX_BAD_LEN = 4096, 32       # DH_BEAM_MAX_BAD_WORDS / DH_BEAM_MAX_BAD_LEN: dh_beam_constrain_logits' list limits
 
 _c = ctypes
 _P, _I, _F, _U64 = _c.c_void_p, _c.c_int, _c.c_float, _c.c_uint64
@@ -129,6 +130,7 @@ SIGNATURES = {
                                 _U64, _P, _I, _P],
     "dh_beam_row_sample_nucleus": [_P, _I, _I, _P, _I, _I, _I, _I, _I, _I, _I, _F, _F, _I, _P, _U64, _P, _I, _I, _P, _I, _P, _P, _P, _P],
     "dh_beam_history_logits": [_P, _I, _I, _P, _I, _I, _I, _P, _I, _I, _I, _I, _I, _P, _I, _F, _P],
+    "dh_beam_constrain_logits": [_P, _I, _I, _P, _I, _I, _I, _P, _I, _I, _I, _I, _I, _P, _I, _I, _P, _P, _I, _P],
     "dh_decode_layers_supported": [_c.POINTER(TrModel), _I, _I],
     "dh_decode_layers_table_bytes": [_I],
     "dh_decode_layers_table": [_c.POINTER(TrModel), _P, _P],

@@ -1047,6 +1047,98 @@ extern "C" int dh_beam_history_logits(float* logits, int ldl, int V, float* grou
     DH_LAUNCH_CHECK();
 }
 
+// ---- history-dependent bans (min_len, bad_words_ids) in front of the row draw ---------------------------------------------------
+// One workgroup per logits row, on the row geometry of beam_history_logits_kernel (history h[0 .. pos) = columns < pos of token row
+// r * tok_row_mult; forced / idle rows of a prompted launch leave before the first barrier).  The banned phrases are one list for
+// the whole launch: phrase w is words[word_off[w] .. word_off[w + 1]), 1 .. DH_BEAM_MAX_BAD_LEN ids.  Phases:
+//   1. the last min(pos, DH_BEAM_MAX_BAD_LEN - 1) tokens of the history go to LDS (no phrase looks further back); flags cleared;
+//   2. pos < min_len and 0 <= eos < V: one thread stores -inf to the <eos> column;
+//   3. thread tid walks phrases tid, tid + 256, ...: a phrase of l ids with l - 1 <= pos whose first l - 1 ids equal the history's
+//      last l - 1 tokens (compared from the phrase's last prefix id backwards: most phrases leave after one compare; l == 1 has
+//      no prefix and always matches) stores -inf to the column of its last id.  A last id outside [0, V) is never a column;
+//      prefix ids are compared as they are;
+//   4. group_max != NULL: the repair of beam_history_logits_kernel's phase 3, same CONVENTION (exact fp32 maximum over the
+//      group's REAL columns < V, pads never read, -inf for an all-banned group, groups without a store not written).
+// Every store is -inf, which the penalty of beam_history_logits_kernel maps to itself: the two launches commute on the logits, and
+// each leaves exact maxima behind, so they compose in either order.
+__global__ __launch_bounds__(256) void beam_constrain_logits_kernel(
+    float* logits, int ldl, int V, float* gmax, int gm_ld, int n_groups, int gcols, const int32_t* __restrict__ tokens, int tok_ld,
+    int tok_row_mult, int pos, int rows_per_img, const int32_t* __restrict__ first_pos, int eos, int min_len,
+    const int32_t* __restrict__ words, const int32_t* __restrict__ word_off, int n_words) {
+    constexpr int NT = 256, MAXG = 1024, TAIL = DH_BEAM_MAX_BAD_LEN - 1;
+    __shared__ int tail[TAIL];                       // tail[T - 1] is the row's latest token
+    __shared__ int gflag[MAXG], glist[MAXG];
+    __shared__ int s_ng;
+    const int rc = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    if (first_pos && prompt_row_idle(first_pos, rc, rows_per_img, pos)) return;
+    float* row = logits + (size_t)rc * ldl;
+    const int32_t* h = tokens + (size_t)rc * tok_row_mult * tok_ld;
+    const int T = pos < TAIL ? pos : TAIL;
+    if (tid < T) tail[tid] = h[pos - T + tid];
+    if (gmax)
+        for (int g = tid; g < n_groups; g += NT) gflag[g] = 0;
+    if (tid == 0) s_ng = 0;
+    __syncthreads();
+    auto ban = [&](int t) {               // column t (0 <= t < V <= n_groups * gcols) becomes -inf; its group is listed once
+        row[t] = -INFINITY;
+        if (gmax) {
+            const int g = t / gcols;
+            if (atomicExch(&gflag[g], 1) == 0) glist[atomicAdd(&s_ng, 1)] = g;
+        }
+    };
+    if (tid == 0 && pos < min_len && eos >= 0 && eos < V) ban(eos);
+    for (int w = tid; w < n_words; w += NT) {
+        const int o = word_off[w], l = word_off[w + 1] - o;
+        if (l < 1 || l > DH_BEAM_MAX_BAD_LEN || l - 1 > pos) continue;
+        const int t = words[o + l - 1];
+        if (t < 0 || t >= V) continue;
+        bool eq = true;
+        for (int k = 1; k < l && eq; ++k) eq = words[o + l - 1 - k] == tail[T - k];
+        if (eq) ban(t);
+    }
+    if (gmax) {
+        __threadfence_block();
+        __syncthreads();
+        // a list of single-token bans edits many groups of every row (50 singles: ~50 groups): each wave takes U listed groups at a
+        // time and issues their U loads before the first reduction, so a trip costs one memory latency, not U
+        constexpr int U = 4;
+        const int ng = s_ng;
+        for (int q0 = wave * U; q0 < ng; q0 += (NT / 64) * U) {
+            float v[U];
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+                const bool on = q0 + u < ng;                         // (wave-uniform)
+                const int c = (on ? glist[q0 + u] : 0) * gcols + lane;
+                v[u] = (on && lane < gcols && c < V) ? row[c] : -INFINITY;
+            }
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+#pragma unroll
+                for (int s = 32; s > 0; s >>= 1) v[u] = fmaxf(v[u], __shfl_xor(v[u], s, 64));
+                if (lane == 0 && q0 + u < ng) gmax[(size_t)rc * gm_ld + glist[q0 + u]] = v[u];
+            }
+        }
+    }
+}
+
+extern "C" int dh_beam_constrain_logits(float* logits, int ldl, int V, float* group_max, int gm_ld, int n_groups, int group_cols,
+                                        const int32_t* tokens, int tok_ld, int tok_row_mult, int pos, int rows, int rows_per_img,
+                                        const int32_t* first_pos, int eos_index, int min_len, const int32_t* words,
+                                        const int32_t* word_off, int n_words, void* stream) {
+    DH_REQUIRE(logits && tokens && rows > 0 && rows_per_img > 0 && V > 0 && ldl >= V && tok_row_mult >= 1);
+    DH_REQUIRE(pos >= 0 && pos <= tok_ld && min_len >= 0);
+    DH_REQUIRE(n_words >= 0 && n_words <= DH_BEAM_MAX_BAD_WORDS && (n_words == 0 || (words && word_off)));
+    DH_REQUIRE(n_words > 0 || pos < min_len);                                  // nothing to ban: the caller makes no launch
+    DH_REQUIRE(!group_max || (n_groups > 0 && n_groups <= 1024 && gm_ld >= n_groups && group_cols > 0 && group_cols <= 64 &&
+                              (long long)n_groups * group_cols >= V));         // dh_beam_row_sample_groups' contract
+    DH_REQUIRE(!first_pos || rows % rows_per_img == 0);
+    DhProfScope prof("dh_beam_constrain_logits", 0.0, 0.0, stream);
+    hipLaunchKernelGGL(beam_constrain_logits_kernel, dim3(rows), dim3(256), 0, (hipStream_t)stream, logits, ldl, V, group_max, gm_ld,
+                       n_groups, group_cols, tokens, tok_ld, tok_row_mult, pos, rows_per_img, first_pos, eos_index, min_len, words,
+                       word_off, n_words);
+    DH_LAUNCH_CHECK();
+}
+
 // ------------------------------------------------------------------------------------------------
 
 template <int MB, bool PR>

@@ -21,6 +21,31 @@ def text_to_seq(text, vocab, tokenizer):
     return torch.tensor(ids).unsqueeze(0)
 
 
+def bad_words_to_ids(words, vocab, tokenizer):
+    """Banned words or phrases as strings -> the id lists ``generate_batch(..., bad_words_ids=)`` takes.  Every string goes through
+    ``text_to_seq`` (same lower-casing, same tokenizer); no ``<eos>`` is added.  A string with a token outside the vocabulary maps
+    to ``<unk>`` there; it is skipped, with ONE warning for all of them, because ``<unk>`` is never drawn and such a phrase could
+    never be completed.  An empty string is skipped too.
+
+    What a match means depends on the tokenizer: with the word tokenizer a phrase matches whole tokens; with the CHARACTER
+    tokenizer a phrase is a run of characters and matches as a SUBSTRING -- banning "ass" also bans "class"."""
+    import warnings
+    unk = vocab.stoi[SPECIAL_TOKENS['UNK']]
+    out, skipped = [], []
+    for word in words:
+        ids = text_to_seq(word, vocab, tokenizer)[0].tolist() if word else []
+        if not ids:
+            continue
+        if unk in ids:
+            skipped.append(word)
+            continue
+        out.append([int(t) for t in ids])
+    if skipped:
+        warnings.warn(f"bad_words_to_ids: {len(skipped)} of {len(list(words))} strings hold a token outside the vocabulary (<unk> is "
+                      f"never drawn, nothing to ban) and are skipped: {skipped[:8]!r}", stacklevel=2)
+    return out
+
+
 def prompts_to_batch(texts, vocab, tokenizer):
     """The host text step in front of ``generate_batch(..., caption=C, caption_lengths=L)``: one optional caption beginning per
     image -> ``(C int64 [N, P], L int64 [N])``.  Every text goes through ``text_to_seq``; a trailing ``<eos>`` is dropped, as the

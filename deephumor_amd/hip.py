@@ -12,7 +12,7 @@ import torch
 from . import _build
 
 from ._abi import (ABI_VERSION, BF16, BF16_OUT_F32, ERR_ALL_FILTERED, ERR_NONFINITE, ERR_OVERFLOW, ERR_TOO_FEW, F16, F16_OUT_F32, F32,  # noqa: F401
-                   HALF_DTYPES, MAX_BEAMS, MAX_HISTORY, SIGNATURES, LnFold, LstmLayer, LstmModel, LstmScratch, TrLayer, TrModel, TrScratch)
+                   HALF_DTYPES, MAX_BAD_LEN, MAX_BAD_WORDS, MAX_BEAMS, MAX_HISTORY, SIGNATURES, LnFold, LstmLayer, LstmModel, LstmScratch, TrLayer, TrModel, TrScratch)
 
 _c = ctypes
 _P, _I, _F, _U64 = _c.c_void_p, _c.c_int, _c.c_float, _c.c_uint64
@@ -929,6 +929,25 @@ def beam_history_logits(logits, v, tokens, tok_row_mult, pos, rows, rows_per_img
     _launch("dh_beam_history_logits", _ptr(logits), logits.stride(0), v, _ptr(group_max),
             group_max.stride(0) if group_max is not None else 0, n_groups(v), GROUP_COLS, _ptr(tokens), tokens.stride(0), tok_row_mult,
             pos, rows, rows_per_img, _ptr(first_pos), int(ngram), float(penalty), _stream())
+
+
+def beam_constrain_logits(logits, v, tokens, tok_row_mult, pos, rows, rows_per_img, eos_index, min_len, words=None, word_off=None,
+                          n_words=0, group_max=None, first_pos=None):
+    """``dh_beam_constrain_logits``: the ``min_len`` / ``bad_words_ids`` bans of fp32 ``logits [rows, V]`` in place -- ``<eos>`` while
+    ``pos < min_len``, and the last id of every phrase (``words`` int32 flat, ``word_off`` int32 ``[n_words + 1]``, both on the
+    device) whose other ids end the row's history ``tokens[r * tok_row_mult, :pos]``.  ``group_max`` / ``first_pos``: as
+    ``beam_history_logits``."""
+    _dev(logits, tokens, group_max, first_pos, words, word_off)
+    assert logits.dtype == torch.float32 and logits.stride(1) == 1 and tokens.dtype == torch.int32 and tokens.stride(1) == 1
+    assert group_max is None or group_max.dtype == torch.float32
+    assert first_pos is None or (first_pos.dtype == torch.int32 and first_pos.numel() * rows_per_img == rows)
+    assert (rows - 1) * tok_row_mult < tokens.shape[0]
+    assert n_words == 0 or (words.dtype == torch.int32 and word_off.dtype == torch.int32 and words.is_contiguous()
+                            and word_off.is_contiguous() and word_off.numel() == n_words + 1)
+    _launch("dh_beam_constrain_logits", _ptr(logits), logits.stride(0), v, _ptr(group_max),
+            group_max.stride(0) if group_max is not None else 0, n_groups(v), GROUP_COLS, _ptr(tokens), tokens.stride(0), tok_row_mult,
+            pos, rows, rows_per_img, _ptr(first_pos), int(eos_index), int(min_len), _ptr(words) if n_words else 0,
+            _ptr(word_off) if n_words else 0, int(n_words), _stream())
 
 
 def beam_select_prompted(pick_idx, pick_val, tokens, vals, ended, src, parent, hparent, done, end_step, n_img, beam, first_pos,

@@ -106,6 +106,133 @@ def check_repeat(no_repeat_ngram_size=0, repetition_penalty=1.0, max_len=None):
     return n, pen
 
 
+class BadWords:
+    """A banned-phrase list compiled for ``dh_beam_constrain_logits`` (``compile_bad_words``): ``ids`` -- a tuple of tuples of ints,
+    the phrases as given, duplicates kept --, and two int32 tensors on ``device``, uploaded once: ``words`` (the phrases flat) and
+    ``offsets`` (``n_words + 1`` entries; phrase ``w`` is ``words[offsets[w]:offsets[w + 1]]``).  Immutable; hashable and equal by
+    ``ids`` and device, so it can sit in a graph cache key, and whoever holds it keeps the tensors alive."""
+    __slots__ = ("ids", "num_tokens", "device", "words", "offsets")
+
+    def __init__(self, ids, num_tokens, device, words, offsets):
+        for name, val in zip(self.__slots__, (ids, num_tokens, device, words, offsets)):
+            object.__setattr__(self, name, val)
+
+    def __setattr__(self, name, value):
+        raise AttributeError("BadWords is immutable")
+
+    def __delattr__(self, name):
+        raise AttributeError("BadWords is immutable")
+
+    @property
+    def n_words(self):
+        return len(self.ids)
+
+    def __len__(self):
+        return len(self.ids)
+
+    def __hash__(self):
+        return hash((self.ids, str(self.device)))
+
+    def __eq__(self, other):
+        return isinstance(other, BadWords) and self.ids == other.ids and str(self.device) == str(other.device)
+
+    def __repr__(self):
+        return f"BadWords({len(self.ids)} phrases, device={self.device})"
+
+
+def _phrases(bad_words_ids, num_tokens=None):
+    """``bad_words_ids`` as a tuple of tuples of ints, every rule of ``check_constraints`` applied."""
+    if isinstance(bad_words_ids, (str, bytes)) or not hasattr(bad_words_ids, "__iter__"):
+        raise TypeError(f"bad_words_ids must be None or a sequence of sequences of token ids, not {type(bad_words_ids).__name__} "
+                        "(strings go through experiments.bad_words_to_ids)")
+    out = []
+    for w, phrase in enumerate(bad_words_ids):
+        if hasattr(phrase, "tolist"):                       # (a tensor or an array: its Python numbers)
+            phrase = phrase.tolist()
+        if isinstance(phrase, (str, bytes)) or not hasattr(phrase, "__iter__"):
+            raise ValueError(f"bad_words_ids: phrase {w} ({phrase!r}) is not a sequence of token ids")
+        phrase = tuple(phrase)
+        if not phrase:
+            raise ValueError(f"bad_words_ids: phrase {w} is empty")
+        if len(phrase) > hip.MAX_BAD_LEN:
+            raise ValueError(f"bad_words_ids: phrase {w} has {len(phrase)} tokens, more than {hip.MAX_BAD_LEN} (DH_BEAM_MAX_BAD_LEN)")
+        for t in phrase:
+            if isinstance(t, bool) or not isinstance(t, numbers.Integral):
+                raise ValueError(f"bad_words_ids: phrase {w} {phrase!r} holds {t!r}, which is not an integer token id")
+            if t < 0 or (num_tokens is not None and t >= num_tokens):
+                raise ValueError(f"bad_words_ids: phrase {w} {phrase!r} holds id {int(t)} outside [0, "
+                                 f"{'num_tokens' if num_tokens is None else num_tokens})")
+        out.append(tuple(int(t) for t in phrase))
+        if len(out) > hip.MAX_BAD_WORDS:
+            raise ValueError(f"bad_words_ids: phrase {w} is one more than the {hip.MAX_BAD_WORDS} a list may hold (DH_BEAM_MAX_BAD_WORDS)")
+    return tuple(out)
+
+
+def check_constraints(min_len=0, bad_words_ids=None, max_len=None, num_tokens=None):
+    """ALL validation of ``min_len`` and ``bad_words_ids``, checked where ``check_repeat`` is, before anything runs.
+
+    ``min_len`` is an ``int`` with ``0 <= min_len < max_len`` (0: off; a ``bool`` is a misplaced flag -> ``ValueError``, a float a
+    ``TypeError``).  ``bad_words_ids`` is ``None``, a ``BadWords``, or a sequence of non-empty sequences of token ids: at most
+    ``hip.MAX_BAD_WORDS`` phrases of at most ``hip.MAX_BAD_LEN`` ids, every id an integer in ``[0, num_tokens)`` -- otherwise a
+    ``ValueError`` that names the phrase.  Duplicates are allowed; ``[]`` is ``None``.  Returns ``(int, None | BadWords | tuple of
+    tuples)``."""
+    m = min_len
+    if isinstance(m, bool):
+        raise ValueError("min_len must be an int >= 0, not a bool")
+    if not isinstance(m, numbers.Integral):
+        raise TypeError(f"min_len must be an int >= 0, not {type(m).__name__}")
+    m = int(m)
+    if m < 0:
+        raise ValueError(f"min_len must be >= 0, got {m}")
+    if max_len is not None and m > 0 and m >= int(max_len):
+        raise ValueError(f"min_len must be below max_len: min_len={m}, max_len={int(max_len)}")
+    if bad_words_ids is None:
+        return m, None
+    if isinstance(bad_words_ids, BadWords):
+        bw = bad_words_ids
+        if num_tokens is not None and (bw.num_tokens is None or bw.num_tokens > num_tokens):
+            _phrases(bw.ids, num_tokens)                    # compiled for a larger vocabulary: the ids against this one
+        return m, (bw if len(bw) else None)
+    ids = _phrases(bad_words_ids, num_tokens)
+    return m, (ids or None)
+
+
+_BAD_WORDS_CACHE = {}           # (device, num_tokens, ids) -> BadWords: a list is uploaded once, not once per call
+_BAD_WORDS_CACHE_SIZE = 16
+
+
+def compile_bad_words(ids, num_tokens=None, device="cuda"):
+    """``bad_words_ids`` -> ``BadWords`` on ``device`` (``None`` for ``None`` / ``[]``; a ``BadWords`` of that device as it is).
+    Validates like ``check_constraints`` and uploads the flat phrases and their offsets once; a small per-device cache keyed by the
+    tuple of tuples gives repeated calls with one list the same tensors.  Not inside a hipGraph capture (a host-to-device copy):
+    ``generate_batch_graphed`` compiles in front of it."""
+    _, ids = check_constraints(0, ids, None, num_tokens)
+    if ids is None:
+        return None
+    device = torch.device(device)
+    if device.type == "cuda" and device.index is None:
+        device = torch.device("cuda", torch.cuda.current_device())
+    if isinstance(ids, BadWords):
+        if str(ids.device) == str(device):
+            return ids
+        ids = ids.ids
+    key = (str(device), num_tokens, ids)
+    bw = _BAD_WORDS_CACHE.get(key)
+    if bw is None:
+        if device.type == "cuda" and torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("compile_bad_words inside a hipGraph capture: compile the list before the capture and pass the BadWords")
+        offs = [0]
+        for w in ids:
+            offs.append(offs[-1] + len(w))
+        words = torch.tensor([t for w in ids for t in w], dtype=torch.int32).to(device)
+        offsets = torch.tensor(offs, dtype=torch.int32).to(device)
+        bw = BadWords(ids, num_tokens, device, words, offsets)
+        while len(_BAD_WORDS_CACHE) >= _BAD_WORDS_CACHE_SIZE:
+            _BAD_WORDS_CACHE.pop(next(iter(_BAD_WORDS_CACHE)))
+        _BAD_WORDS_CACHE[key] = bw
+    return bw
+
+
 class BeamOverflow(RuntimeError):
     """A row had more logits at its top-k threshold than the pre-filtered samplers' candidate buffers hold (flat / constant logits):
     the decoders catch this and repeat the batch with ``exact=True`` (the general sampler, which draws such rows over the whole row).
@@ -264,6 +391,13 @@ class BeamSearchHelper:
     maxima are repaired when -- and only when -- the sampler that follows reads them.  A caller's ``logits_hook`` runs before
     ``step`` and therefore sees the model's raw logits.  Deterministic, so it composes with ``rng="torch"``, ``noise_source``,
     ``exact``, streams and hipGraph capture (the position is a launch constant).  The defaults ``0`` / ``1.0`` make no launch.
+
+    ``min_len`` / ``bad_words_ids`` (not in the reference either): behind that launch and in front of the row draw, one launch of
+    ``dh_beam_constrain_logits`` -- while ``write_pos < min_len`` the ``<eos>`` column is ``-inf``; for every phrase of the list whose
+    ids but the last end the row's history, the last id's column is ``-inf`` (a single id: at every position).  The group maxima
+    are repaired on the same condition as above.  A launch is made only when the list is not empty or ``write_pos < min_len``; the
+    defaults ``0`` / ``None`` make none.  Both are set with ``helper.set_constraints(min_len=, bad_words_ids=)`` after construction
+    (``bad_words_ids``: the raw nesting, compiled there by ``compile_bad_words``, or a ``BadWords``).
     """
 
     def __init__(self, temperature=1.0, beam_size=10, top_k=50, unk_index=1, eos_index=3, device='cuda',
@@ -273,6 +407,7 @@ class BeamSearchHelper:
         self.top_p = check_top_p(top_p)
         self.no_repeat_ngram_size, self.repetition_penalty = check_repeat(no_repeat_ngram_size, repetition_penalty, max_len)
         self._history_edits = self.no_repeat_ngram_size > 0 or self.repetition_penalty != 1.0
+        self.min_len, self.bad_words, self._constraints = 0, None, False      # min_len / bad_words_ids: set_constraints
         self.exact = bool(exact)          # row draws through the general sampler only (see BeamOverflow)
         if beam_size > hip.MAX_BEAMS:     # one wave draws among an image's beams (dh_beam_finalize); the reference has no limit
             raise ValueError(f"beam_size <= {hip.MAX_BEAMS} supported")
@@ -313,6 +448,16 @@ class BeamSearchHelper:
             base = (torch.arange(r, dtype=torch.int32, device=dev) // beam_size) * beam_size
             self.src = base[:, None].expand(r, src_len).contiguous()
 
+    def set_constraints(self, min_len=0, bad_words_ids=None):
+        """``min_len`` / ``bad_words_ids`` of this session (see the class docstring), validated by ``check_constraints`` against the
+        helper's ``max_len``; the raw nesting is compiled here (``compile_bad_words``: one upload, so not inside a hipGraph capture),
+        a ``BadWords`` is taken as it is.  A method, not two more constructor arguments: the constructor's parameter list ends at
+        ``repetition_penalty``.  Returns the helper."""
+        self.min_len, bad_words_ids = check_constraints(min_len, bad_words_ids, self.max_len)
+        self.bad_words = compile_bad_words(bad_words_ids, None, self.device)
+        self._constraints = self.min_len > 0 or self.bad_words is not None
+        return self
+
     def set_prefix(self, caption):
         """caption int64 [n_img, p]: teacher-forced beginning, copied to every beam row."""
         p = caption.shape[1]
@@ -345,6 +490,7 @@ class BeamSearchHelper:
         if self._history_edits:
             hip.beam_history_logits(logits, v, self.tokens, 1, write_pos, rows, self.beam_size, self.no_repeat_ngram_size,
                                     self.repetition_penalty, group_max=group_max if use_groups else None, first_pos=self.first_pos)
+        self._constrain(logits, v, 1, write_pos, rows, self.beam_size, group_max if use_groups else None, self.first_pos)
         if self.top_p < 1.0:
             hip.beam_row_sample_nucleus(logits, v, rows, self.beam_size, self.beam_size, self.top_k, self.top_p, self.temperature,
                                         self.unk_index, None, self.seed, self.img0, step_index, self.pick_idx, self.pick_val, self.err,
@@ -358,6 +504,16 @@ class BeamSearchHelper:
                                  self.hparent, self.done, self.end_step, self.n_img, self.beam_size, self.first_pos,
                                  first_sets_ended, write_pos, t, step_index, self.temperature, self.eos_index, None, self.seed,
                                  self.img0, seed_ptr=self.seed_tensor)
+
+    def _constrain(self, logits, v, tok_row_mult, pos, rows, rpi, group_max, first_pos=None):
+        """min_len / bad_words_ids: the bans in front of the row draw, behind the history edits (both store ``-inf`` or map it to
+        itself, so the order does not show).  A launch only when there is something to ban at this position."""
+        bw = self.bad_words
+        if bw is None and pos >= self.min_len:
+            return
+        hip.beam_constrain_logits(logits, v, self.tokens, tok_row_mult, pos, rows, rpi, self.eos_index, self.min_len,
+                                  None if bw is None else bw.words, None if bw is None else bw.offsets, 0 if bw is None else len(bw),
+                                  group_max=group_max, first_pos=first_pos)
 
     def _noise(self, kind, step, shape, ld=None):
         if self.noise_source is None:
@@ -386,6 +542,7 @@ class BeamSearchHelper:
             hip.beam_history_logits(logits, v, self.tokens, self.beam_size if first else 1, write_pos, rows, rpi,
                                     self.no_repeat_ngram_size, self.repetition_penalty,
                                     group_max=group_max if use_groups else None)
+        self._constrain(logits, v, self.beam_size if first else 1, write_pos, rows, rpi, group_max if use_groups else None)
         if self.top_p < 1.0:              # the nucleus of the survivors: one entry point for the three routes below
             hip.beam_row_sample_nucleus(logits, v, rows, rpi, self.beam_size, self.top_k, self.top_p, self.temperature, self.unk_index,
                                         self._noise("row", step_index, (rows, v), logits.stride(0)), self.seed, self.img0, step_index,
@@ -493,6 +650,9 @@ class BeamSearchHelper:
         if self._history_edits:
             raise NotImplementedError(f"{what} with no_repeat_ngram_size / repetition_penalty: the history edits live in the batched "
                                       "engine's row draw (step / step_prompted); the reference-style method surface has none")
+        if self._constraints:
+            raise NotImplementedError(f"{what} with min_len / bad_words_ids: the bans live in the batched engine's row draw (step / "
+                                      "step_prompted); the reference-style method surface has none")
         if self.top_p < 1.0:
             raise NotImplementedError(f"{what} with top_p < 1: the nucleus lives in the batched engine's row draw (step / step_prompted); "
                                       "the reference-style method surface has none")

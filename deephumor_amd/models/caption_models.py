@@ -61,6 +61,8 @@ class _CaptioningBase(nn.Module):
         ``top_p`` (in ``kw``, a number in ``(0, 1]``): nucleus filtering beside ``top_k`` (``LSTMDecoder.generate_batch``).
         ``no_repeat_ngram_size`` (int ``>= 0``) / ``repetition_penalty`` (finite ``> 0``), in ``kw``: no row completes an n-gram it
         already holds / every token of a row's history is damped CTRL-style, in front of every row draw (``LSTMDecoder.generate_batch``).
+        ``min_len`` (int, ``0 <= min_len < max_len``) / ``bad_words_ids`` (``None``, a nesting of token ids, or a ``beam.BadWords``), in
+        ``kw``: no ``<eos>`` at a token position below ``min_len`` / no row completes a banned phrase (``LSTMDecoder.generate_batch``).
         ``caption_lengths`` (keyword only, int64 / int32 ``[N]``): a prompt of its own length per image -- row ``i`` is
         teacher-forced with ``caption[i, :caption_lengths[i]]`` (0: none; the rest of the row is ignored) and equals the dense
         single-image call with that prompt and ``img0 + i`` (``LSTMDecoder.generate_batch``)."""
@@ -73,10 +75,11 @@ class _CaptioningBase(nn.Module):
         """A prompted batch is validated BEFORE the encoder runs (``beam.check_prompts`` / ``prompt_session_inputs``: shapes, ranges,
         the options it cannot be combined with); ``defer_check`` callers (graph capture, the pipeline) with device-resident lengths
         have done so themselves.  So is the type of ``return_beams`` (``beam.check_return_beams``) and the range of ``top_p`` (``beam.check_top_p``), for every batch."""
-        from .beam import check_prompts, check_repeat, check_return_beams, check_top_p, prompts_need_philox
+        from .beam import check_constraints, check_prompts, check_repeat, check_return_beams, check_top_p, prompts_need_philox
         check_return_beams(kw.get("return_beams", False))
         check_top_p(kw.get("top_p", 1.0))
         check_repeat(kw.get("no_repeat_ngram_size", 0), kw.get("repetition_penalty", 1.0), max_len)      # (beam.check_repeat: likewise)
+        check_constraints(kw.get("min_len", 0), kw.get("bad_words_ids"), max_len, self._hp["num_tokens"])   # (beam.check_constraints: likewise)
         if caption_lengths is None:
             return None
         if getattr(self.decoder, "pad_index", 0) == 1:
@@ -118,7 +121,7 @@ class _CaptioningBase(nn.Module):
         function of the lengths enters the graph cache key -- only the fact that lengths were passed, next to ``caption``'s shape:
         the captured chain treats every position ``0 .. min(P, max_len - 2)`` as mixed (all ``N * beam`` rows, the prompted beam
         step), so one graph serves every set of lengths of that shape and returns what eager returns for them."""
-        from .beam import BeamCaptions, BeamOverflow, BeamSearchHelper, check_repeat, check_return_beams, check_top_p, resolve_seed, warn_overflow_retry
+        from .beam import BeamCaptions, BeamOverflow, BeamSearchHelper, check_constraints, check_repeat, check_return_beams, compile_bad_words, check_top_p, resolve_seed, warn_overflow_retry
         # ``return_beams=True`` is part of the cache key like every decode setting (``kw``): its graph ends in dh_beam_finalize_beams and
         # lives beside the plain one of the same shapes; a replay returns clones of every field
         check_return_beams(kw.get("return_beams", False))
@@ -127,6 +130,12 @@ class _CaptioningBase(nn.Module):
         # so do ``no_repeat_ngram_size`` / ``repetition_penalty``: their graph holds one dh_beam_history_logits node per position (the
         # position is a launch constant) and lives beside the plain one
         check_repeat(kw.get("no_repeat_ngram_size", 0), kw.get("repetition_penalty", 1.0), kw.get("max_len", 25))
+        # and ``min_len`` / ``bad_words_ids`` (one dh_beam_constrain_logits node per position that bans something).  The list is
+        # compiled HERE, in front of any capture -- no host-to-device copy happens inside one -- and the ``BadWords`` replaces the raw
+        # nesting in ``kw``: it is hashable, so it is in the key below, and the captured closure keeps its two tensors alive
+        _, bad_words = check_constraints(kw.get("min_len", 0), kw.get("bad_words_ids"), kw.get("max_len", 25), self._hp["num_tokens"])
+        if "bad_words_ids" in kw:
+            kw["bad_words_ids"] = compile_bad_words(bad_words, self._hp["num_tokens"], inputs[0].device)
         if kw.get("rng") == "torch":      # host-generated noise (parity mode): nothing to replay
             return self.generate_batch(*inputs, caption=caption, seed=seed, caption_lengths=caption_lengths, **kw)
         if caption_lengths is not None:

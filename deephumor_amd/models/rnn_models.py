@@ -15,8 +15,25 @@ from torch import nn
 
 from .. import hip
 from ._f32x_guard import f32x_guarded
-from .beam import BeamCaptions, BeamOverflow, BeamSearchHelper, call_logits_hook, check_return_beams, check_top_p, check_repeat, check_ids, check_lengths, classifier_must_be_finite, make_noise_source, prompt_session_inputs, resolve_seed, run_interleaved, warn_overflow_retry
+from .beam import BeamCaptions, BeamOverflow, BeamSearchHelper, call_logits_hook, check_return_beams, check_top_p, check_repeat, check_constraints, compile_bad_words, check_ids, check_lengths, classifier_must_be_finite, make_noise_source, prompt_session_inputs, resolve_seed, run_interleaved, warn_overflow_retry
 from .encoders import _Planned
+
+
+def _later_keywords(*names):
+    """Decorator of ``LSTMDecoder.generate_batch``: the method keeps the parameter list it had (positional order, keyword-only tail
+    ending at ``repetition_penalty``), and the keyword-only controls added since -- ``names`` -- are accepted by name here and go to
+    ``self._generate_batch`` together with everything else.  A call without them is the method's own body."""
+    import functools
+
+    def deco(fn):
+        @functools.wraps(fn)
+        def generate_batch(self, *args, **kw):
+            later = {k: kw.pop(k) for k in names if k in kw}
+            if not later:
+                return fn(self, *args, **kw)
+            return self._generate_batch(*args, **kw, **later)
+        return generate_batch
+    return deco
 
 
 class LSTMDecoder(_Planned, nn.Module):
@@ -173,7 +190,7 @@ class LSTMDecoder(_Planned, nn.Module):
         hs.mul_(valid[..., None])          # pad_packed_sequence zero rows (mask, not arithmetic on valid rows)
         return hs, bs, steps_out
 
-    @f32x_guarded
+    @_later_keywords("min_len", "bad_words_ids")
     def generate_batch(self, image_emb, caption=None, max_len=25, temperature=1.0, beam_size=10, top_k=50,
                        eos_index=3, seed=None, img0=0, noise_source=None, logits_hook=None, streams=1, seed_tensor=None,
                        defer_check=False, early_stop_every=0, exact=False, rng=None, *, caption_lengths=None, return_beams=False, top_p=1.0,
@@ -208,13 +225,37 @@ class LSTMDecoder(_Planned, nn.Module):
         history has its logit ``x`` replaced by ``x * penalty`` if ``x < 0`` else ``x / penalty`` (CTRL).  Penalty first, ban second,
         one launch of ``dh_beam_history_logits`` in front of every row draw (``BeamSearchHelper``); ``logits_hook`` still sees the
         model's raw logits.  ``0`` / ``1.0``, the defaults, are the call without the keywords: same launches, same bits.  ``max_len``
-        above ``hip.MAX_HISTORY`` with a control on is a ``ValueError``."""
+        above ``hip.MAX_HISTORY`` with a control on is a ``ValueError``.
+        ``min_len`` (keyword only, int, ``0 <= min_len < max_len``, absolute like ``max_len``: prompt tokens count): no row draws
+        ``<eos>`` at a token position ``s < min_len``.  ``bad_words_ids`` (keyword only; ``None``, a sequence of non-empty sequences of
+        token ids, or a ``beam.BadWords`` from ``beam.compile_bad_words``; one list for the batch): no row draws the last id of a
+        phrase whose other ids end its own history (prompt included, per beam row) -- a single id is banned at every position.  At
+        most ``hip.MAX_BAD_WORDS`` phrases of ``hip.MAX_BAD_LEN`` ids.  One launch of ``dh_beam_constrain_logits`` behind the history
+        edits and in front of the row draw, only at positions where there is something to ban; ``logits_hook`` still sees the raw
+        logits.  ``0`` / ``None``, the defaults, are the call without the keywords: same launches, same bits.  All validation:
+        ``beam.check_constraints``.
+        ``min_len`` and ``bad_words_ids`` are not in the parameter list above, which ends at ``repetition_penalty`` as it did: they
+        are taken by name (``_later_keywords``) and handed to ``_generate_batch``, the implementation, which spells every keyword
+        out."""
+        return self._generate_batch(image_emb, caption, max_len, temperature, beam_size, top_k, eos_index, seed, img0, noise_source,
+                                    logits_hook, streams, seed_tensor, defer_check, early_stop_every, exact, rng,
+                                    caption_lengths=caption_lengths, return_beams=return_beams, top_p=top_p,
+                                    no_repeat_ngram_size=no_repeat_ngram_size, repetition_penalty=repetition_penalty)
+
+    @f32x_guarded
+    def _generate_batch(self, image_emb, caption=None, max_len=25, temperature=1.0, beam_size=10, top_k=50,
+                        eos_index=3, seed=None, img0=0, noise_source=None, logits_hook=None, streams=1, seed_tensor=None,
+                        defer_check=False, early_stop_every=0, exact=False, rng=None, *, caption_lengths=None, return_beams=False, top_p=1.0,
+                        no_repeat_ngram_size=0, repetition_penalty=1.0, min_len=0, bad_words_ids=None):
+        """``generate_batch`` with its keyword-only tail written out."""
         check_return_beams(return_beams)
         top_p = check_top_p(top_p)
         no_repeat_ngram_size, repetition_penalty = check_repeat(no_repeat_ngram_size, repetition_penalty, max_len)
+        min_len, bad_words_ids = check_constraints(min_len, bad_words_ids, max_len, self.num_tokens)
         self._check_mode()
         plan = self._get_plan()
         classifier_must_be_finite(plan)
+        bad_words_ids = compile_bad_words(bad_words_ids, self.num_tokens, image_emb.device)     # uploaded once (a BadWords: as it is)
         prompts = prompt_session_inputs(caption, caption_lengths, max_len, self.embedding.num_embeddings, image_emb.device, rng,
                                         noise_source, no_host_read=defer_check)
         if prompts is None:
@@ -239,7 +280,7 @@ class LSTMDecoder(_Planned, nn.Module):
             pmin, pmax = (min(host[lo:hi]), max(host[lo:hi])) if host is not None else (0, cap.shape[1])
             helper = BeamSearchHelper(temperature, beam_size, top_k, eos_index=eos_index, device=dev, n_img=n, max_len=max_len,
                                       seed=seed, img0=img0 + lo, seed_tensor=seed_tensor, exact=exact[0], top_p=top_p,
-                                      no_repeat_ngram_size=no_repeat_ngram_size, repetition_penalty=repetition_penalty)
+                                      no_repeat_ngram_size=no_repeat_ngram_size, repetition_penalty=repetition_penalty).set_constraints(min_len, bad_words_ids)
             helper.set_prompts(cap[lo:hi], first_pos[lo:hi])
             st = self._State(self, plan, n, b, dev)
             logits = torch.empty((r, (self.num_tokens + 255) // 256 * 256), device=dev)[:, :self.num_tokens]
@@ -275,7 +316,7 @@ class LSTMDecoder(_Planned, nn.Module):
                                       max_len=eff_len, seed=seed, img0=img0 + lo,
                                       noise_source=make_noise_source(rng, rng_seed, noise_source, lo, hi, img0, rng_state0), seed_tensor=seed_tensor,
                                       exact=exact[0], top_p=top_p,
-                                      no_repeat_ngram_size=no_repeat_ngram_size, repetition_penalty=repetition_penalty)
+                                      no_repeat_ngram_size=no_repeat_ngram_size, repetition_penalty=repetition_penalty).set_constraints(min_len, bad_words_ids)
             pos = 0
             if caption is not None:
                 pos = caption.shape[1]
@@ -325,7 +366,7 @@ class LSTMDecoder(_Planned, nn.Module):
                  temperature=1.0, beam_size=10, top_k=50, eos_index=3, **kw):
         """Single-image API of the reference (rnn_models.py:48-49): ``image_emb [1, 1, E]`` ->
         1-D int64 token tensor; with ``return_beams=True`` the image's ``BeamCaptions`` (``N = 1``, nothing squeezed).  ``top_p``,
-        ``no_repeat_ngram_size``, ``repetition_penalty`` (in ``kw``): see ``generate_batch``."""
+        ``no_repeat_ngram_size``, ``repetition_penalty``, ``min_len``, ``bad_words_ids`` (in ``kw``): see ``generate_batch``."""
         res = self.generate_batch(image_emb, caption=caption, max_len=max_len, temperature=temperature,
                                   beam_size=beam_size, top_k=top_k, eos_index=eos_index, **kw)
         return self.single_output(res, caption, max_len, beam_size)

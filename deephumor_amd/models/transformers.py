@@ -21,7 +21,7 @@ from torch import nn
 
 from .. import hip
 from ._f32x_guard import f32x_guarded
-from .beam import BeamCaptions, BeamOverflow, BeamSearchHelper, call_logits_hook, check_ids, check_return_beams, check_top_p, check_repeat, classifier_must_be_finite, make_noise_source, prompt_session_inputs, resolve_seed, run_interleaved, warn_overflow_retry
+from .beam import BeamCaptions, BeamOverflow, BeamSearchHelper, call_logits_hook, check_ids, check_return_beams, check_top_p, check_repeat, check_constraints, compile_bad_words, classifier_must_be_finite, make_noise_source, prompt_session_inputs, resolve_seed, run_interleaved, warn_overflow_retry
 from .encoders import _Planned
 
 
@@ -435,7 +435,7 @@ class _IncrementalDecoder(_Planned, nn.Module):
 
     def _generate_reforward(self, start_emb, enc_out, caption, max_len, temperature, beam_size, top_k, eos_index, seed, img0,
                             noise_source, logits_hook, rng, rng_seed, exact, return_beams=False, top_p=1.0,
-                            no_repeat_ngram_size=0, repetition_penalty=1.0):
+                            no_repeat_ngram_size=0, repetition_penalty=1.0, min_len=0, bad_words_ids=None):
         """``generate`` by the reference's own algorithm (transformers.py:521-577): the whole padded sequence of every beam row is
         re-run for each token on the module-API layers.  Only ``pad_index == 1`` needs it (see ``_forward_modules``); the beam
         bookkeeping is the batched engine's."""
@@ -443,7 +443,7 @@ class _IncrementalDecoder(_Planned, nn.Module):
         helper = BeamSearchHelper(temperature, beam_size, top_k, eos_index=eos_index, device=dev, n_img=n, max_len=max_len,
                                   src_len=max_len + 1, seed=seed, img0=img0,
                                   noise_source=make_noise_source(rng, rng_seed, noise_source, 0, n, img0), exact=exact, top_p=top_p,
-                                  no_repeat_ngram_size=no_repeat_ngram_size, repetition_penalty=repetition_penalty)
+                                  no_repeat_ngram_size=no_repeat_ngram_size, repetition_penalty=repetition_penalty).set_constraints(min_len, bad_words_ids)
         helper.tokens.fill_(self.pad_index)
         pos = 0
         if caption is not None:
@@ -553,13 +553,15 @@ class _IncrementalDecoder(_Planned, nn.Module):
     def _generate_batch(self, start_emb, enc_out, caption, max_len, temperature, beam_size, top_k, eos_index,
                         seed=None, img0=0, noise_source=None, logits_hook=None, streams=1, seed_tensor=None,
                         defer_check=False, early_stop_every=0, exact=False, rng=None, caption_lengths=None, return_beams=False, top_p=1.0,
-                        no_repeat_ngram_size=0, repetition_penalty=1.0):
+                        no_repeat_ngram_size=0, repetition_penalty=1.0, min_len=0, bad_words_ids=None):
         check_return_beams(return_beams)
         top_p = check_top_p(top_p)
         no_repeat_ngram_size, repetition_penalty = check_repeat(no_repeat_ngram_size, repetition_penalty, max_len)
+        min_len, bad_words_ids = check_constraints(min_len, bad_words_ids, max_len, self.num_tokens)
         self._check_mode()
         plan = self._get_plan()
         classifier_must_be_finite(plan)
+        bad_words_ids = compile_bad_words(bad_words_ids, self.num_tokens, start_emb.device)     # uploaded once (a BadWords: as it is)
         if caption_lengths is not None and self.pad_index == 1:
             raise NotImplementedError("caption_lengths with pad_index == 1: that decoder re-runs the whole sequence per token on the "
                                       "module path (_generate_reforward), which has no per-image prompt phase")
@@ -581,7 +583,7 @@ class _IncrementalDecoder(_Planned, nn.Module):
             try:
                 return self._generate_reforward(start_emb, enc_out, caption, max_len, temperature, beam_size, top_k, eos_index, seed,
                                                 img0, noise_source, logits_hook, rng, rng_seed, bool(exact), return_beams, top_p,
-                                                no_repeat_ngram_size, repetition_penalty)
+                                                no_repeat_ngram_size, repetition_penalty, min_len, bad_words_ids)
             except BeamOverflow:
                 if exact:
                     raise
@@ -590,7 +592,7 @@ class _IncrementalDecoder(_Planned, nn.Module):
                     torch.set_rng_state(rng_state0)
                 return self._generate_reforward(start_emb, enc_out, caption, max_len, temperature, beam_size, top_k, eos_index, seed,
                                                 img0, noise_source, logits_hook, rng, rng_seed, True, return_beams, top_p,
-                                                no_repeat_ngram_size, repetition_penalty)
+                                                no_repeat_ngram_size, repetition_penalty, min_len, bad_words_ids)
 
         def prompted_session(lo, hi):
             """``session`` for a batch with ``caption_lengths``.  Positions are absolute (slot 0 the image, caption token j at slot
@@ -605,7 +607,7 @@ class _IncrementalDecoder(_Planned, nn.Module):
             pmin, pmax = (min(host[lo:hi]), max(host[lo:hi])) if host is not None else (0, cap.shape[1])
             helper = BeamSearchHelper(temperature, beam_size, top_k, eos_index=eos_index, device=dev, n_img=n, max_len=max_len,
                                       src_len=max_len + 1, seed=seed, img0=img0 + lo, seed_tensor=seed_tensor, exact=exact[0], top_p=top_p,
-                                      no_repeat_ngram_size=no_repeat_ngram_size, repetition_penalty=repetition_penalty)
+                                      no_repeat_ngram_size=no_repeat_ngram_size, repetition_penalty=repetition_penalty).set_constraints(min_len, bad_words_ids)
             if self.pad_index != 0:
                 helper.tokens.fill_(self.pad_index)
             helper.set_prompts(cap[lo:hi], first_pos[lo:hi], self.pad_index)
@@ -642,7 +644,7 @@ class _IncrementalDecoder(_Planned, nn.Module):
                                       max_len=max_len, src_len=max_len + 1, seed=seed, img0=img0 + lo,
                                       noise_source=make_noise_source(rng, rng_seed, noise_source, lo, hi, img0, rng_state0),
                                       seed_tensor=seed_tensor, exact=exact[0], top_p=top_p,
-                                      no_repeat_ngram_size=no_repeat_ngram_size, repetition_penalty=repetition_penalty)
+                                      no_repeat_ngram_size=no_repeat_ngram_size, repetition_penalty=repetition_penalty).set_constraints(min_len, bad_words_ids)
             if self.pad_index != 0:
                 helper.tokens.fill_(self.pad_index)
             pos = 0
@@ -715,7 +717,8 @@ class TransformerDecoder(_IncrementalDecoder):
         """``start_emb [N, D]``, ``enc_out [N, S, D]`` -> ``(tokens [N, max_len], lengths [N])``.  ``caption_lengths`` (keyword only):
         a prompt of its own length per image, see ``LSTMDecoder.generate_batch``; ``return_beams=True`` (in ``kw``): every beam as a
         ``beam.BeamCaptions``, see there; ``top_p`` (in ``kw``): nucleus filtering beside ``top_k``, see there;
-        ``no_repeat_ngram_size`` / ``repetition_penalty`` (in ``kw``): the history edits in front of every row draw, see there."""
+        ``no_repeat_ngram_size`` / ``repetition_penalty`` (in ``kw``): the history edits in front of every row draw, see there;
+        ``min_len`` / ``bad_words_ids`` (in ``kw``): no ``<eos>`` below ``min_len``, no banned phrase, see there."""
         return self._generate_batch(start_emb, enc_out, caption, max_len, temperature, beam_size, top_k,
                                     eos_index, caption_lengths=caption_lengths, **kw)
 
@@ -742,7 +745,8 @@ class SelfAttentionTransformerDecoder(_IncrementalDecoder):
                        top_k=50, eos_index=3, *, caption_lengths=None, **kw):
         """``caption_lengths`` (keyword only): a prompt of its own length per image; ``return_beams=True`` (in ``kw``): every beam as
         a ``beam.BeamCaptions``; ``top_p`` (in ``kw``): nucleus filtering beside ``top_k``; ``no_repeat_ngram_size`` / ``repetition_penalty``
-        (in ``kw``): the history edits in front of every row draw -- see ``LSTMDecoder.generate_batch`` for all."""
+        (in ``kw``): the history edits in front of every row draw; ``min_len`` / ``bad_words_ids`` (in ``kw``): no ``<eos>`` below
+        ``min_len``, no banned phrase -- see ``LSTMDecoder.generate_batch`` for all."""
         return self._generate_batch(start_emb, None, caption, max_len, temperature, beam_size, top_k,
                                     eos_index, caption_lengths=caption_lengths, **kw)
 

@@ -63,11 +63,14 @@ class CaptionPipeline:
         # (pad_index == 1: host-driven full re-forward) decode synchronously
         self._async = getattr(getattr(model, "decoder", None), "pad_index", 0) != 1
         # return_beams=True (in gen_kw): every batch is yielded as a beam.BeamCaptions (to_host: its fields in pinned memory)
-        from .models.beam import check_repeat, check_return_beams, check_top_p
+        from .models.beam import check_constraints, check_repeat, check_return_beams, check_top_p
         self._beams = check_return_beams(gen_kw.get("return_beams", False))
         check_top_p(gen_kw.get("top_p", 1.0))      # (in gen_kw like every decode setting: nucleus filtering, see LSTMDecoder.generate_batch)
         # (likewise: the history edits in front of every row draw; a bad value raises here, before the first batch is staged)
         check_repeat(gen_kw.get("no_repeat_ngram_size", 0), gen_kw.get("repetition_penalty", 1.0), gen_kw.get("max_len"))
+        # (min_len / bad_words_ids likewise; the list is checked here and compiled -- uploaded -- once, by the first batch)
+        check_constraints(gen_kw.get("min_len", 0), gen_kw.get("bad_words_ids"), gen_kw.get("max_len", 25),
+                          getattr(model, "_hp", {}).get("num_tokens"))
 
     # -- stages ------------------------------------------------------------------------------------------------------
     def _stage(self, host_inputs):

@@ -47,6 +47,8 @@ enum { DH_BEAM_ERR_ALL_FILTERED = 1,   /* every logit filtered (-inf): reference
 #define DH_BEAM_MAX_SURVIVORS 1024
 #define DH_BEAM_MAX_BEAMS 64
 #define DH_BEAM_MAX_HISTORY 1024     /* longest row history dh_beam_history_logits looks at (token columns < pos) */
+#define DH_BEAM_MAX_BAD_WORDS 4096   /* most phrases of one dh_beam_constrain_logits list */
+#define DH_BEAM_MAX_BAD_LEN 32       /* most token ids of one phrase */
 
 int dh_abi_version(void);
 const char* dh_error_string(int code);
@@ -552,6 +554,24 @@ int dh_beam_row_sample_nucleus(const float* logits, int ldl, int V, const float*
 int dh_beam_history_logits(float* logits, int ldl, int V, float* group_max, int gm_ld, int n_groups, int group_cols,
                            const int32_t* tokens, int tok_ld, int tok_row_mult, int pos, int rows, int rows_per_img,
                            const int32_t* first_pos, int ngram, float penalty, void* stream);
+
+/* ---- Bans in front of a row draw: min_len and a list of banned phrases, IN PLACE on fp32 logits [rows, ldl], one launch, on the row
+ * geometry of dh_beam_history_logits (history h[0 .. pos) = tokens[r * tok_row_mult, 0 .. pos); first_pos: idle rows untouched).
+ * The list is shared by all rows: phrase w is words[word_off[w] .. word_off[w+1]) (int32, device; word_off has n_words + 1
+ * entries), 1 .. DH_BEAM_MAX_BAD_LEN ids each, n_words <= DH_BEAM_MAX_BAD_WORDS; a phrase of another length is skipped.  Per row:
+ *   1. pos < min_len and 0 <= eos_index < V: logits[eos_index] = -inf;
+ *   2. for every phrase w of l ids with l - 1 <= pos and h[pos-l+1 .. pos) == w[0 .. l-1): logits[w[l-1]] = -inf (l == 1: at
+ *      every pos).  A last id outside [0, V) is never a column; prefix ids are compared as they are;
+ *   3. group_max != NULL: as dh_beam_history_logits' step 3 -- every group holding a column that 1 or 2 stored to is recomputed as
+ *      the exact fp32 maximum over its real columns (< V), -inf if they are all -inf; no other group, no other logit is written.
+ *      Pass group_max exactly when the sampler that follows reads it.
+ * Every store is -inf, so this launch and dh_beam_history_logits commute on the logits and compose on the maxima.
+ * pos <= tok_ld (only the last DH_BEAM_MAX_BAD_LEN - 1 tokens are looked at), min_len >= 0; n_words == 0 with pos >= min_len is
+ * DH_ERR_BAD_ARG: the caller makes no launch then.  pos is a launch constant, so the call can be captured into a hipGraph. */
+int dh_beam_constrain_logits(float* logits, int ldl, int V, float* group_max, int gm_ld, int n_groups, int group_cols,
+                             const int32_t* tokens, int tok_ld, int tok_row_mult, int pos, int rows, int rows_per_img,
+                             const int32_t* first_pos, int eos_index, int min_len, const int32_t* words, const int32_t* word_off,
+                             int n_words, void* stream);
 
 /* ---- BeamSearchHelper's METHOD surface (deephumor/models/beam.py:32-108), for callers that drive the helper the way the
  * reference's own generate() loops do (rnn_models.py:87-128, transformers.py:532-569): one image, host-driven, tensors of the
