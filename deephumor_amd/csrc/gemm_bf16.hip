@@ -400,7 +400,9 @@ __global__ __launch_bounds__(64 * NW) void gemm_bf16_kernel(GemmBf16Params p) {
     // bf16 output with a residual: this thread's residual chunks (one 16-byte chunk per epilogue iteration) are requested
     // NOW, so they are in flight while the tile is staged through LDS -- loaded inside the loop below each of them
     // cost a full memory round trip (load, wait, add, store, next)
-    const bool fast = ((p.ldc & 7) == 0) && (!p.res || (p.ldres & 7) == 0);
+    // (`fast`: the 16-byte row accesses need 16-byte rows AND 16-byte bases -- out / residual may be column slices that start
+    //  mid-chunk; wave-uniform, so such a call takes the element-wise path below as a whole)
+    const bool fast = ((p.ldc & 7) == 0) && (!p.res || (p.ldres & 7) == 0) && ((((uintptr_t)p.C) | ((uintptr_t)p.res)) & 15) == 0;
     float a_mu[TM], a_rs[TM], r_mu[EP_IT], r_rs[EP_IT];
     if constexpr (AFX) {
 #pragma unroll
