@@ -103,6 +103,7 @@ SIGNATURES = {
     "dh_add_layernorm": [_P, _P, _P, _P, _P, _I, _I, _F, _I, _P],
     "dh_attn_self_decode": [_P, _P, _P, _P, _I, _P, _I, _P, _I, _I, _I, _I, _I, _I, _I, _F, _I, _I, _P],
     "dh_attn_cross_decode": [_P, _I, _P, _P, _P, _I, _I, _I, _I, _I, _F, _I, _P],
+    "dh_attn_cross_weights": [_P, _I, _P, _P, _P, _I, _I, _I, _I, _I, _I, _F, _I, _P],
     "dh_enc_key_mask": [_P, _P, _I, _I, _I, _P],
     "dh_pad_mask": [_P, _P, _I, _I, _I, _c.c_longlong, _P],
     "dh_autoregressive_mask": [_P, _I, _I, _P],
@@ -137,6 +138,8 @@ SIGNATURES = {
     "dh_decode_layers": [_c.POINTER(TrModel), _c.POINTER(TrScratch), _P, _P, _I, _P, _I, _I, _I, _I, _I, _I, _P, _P],
     "dh_transformer_decode_position": [_c.POINTER(TrModel), _c.POINTER(TrScratch), _P, _P, _I, _P, _I, _I, _I, _I, _I, _I,
                                        _P, _P, _I, _P, _I, _P],
+    "dh_transformer_decode_position_attn": [_c.POINTER(TrModel), _c.POINTER(TrScratch), _P, _P, _I, _P, _I, _I, _I, _I, _I, _I,
+                                            _P, _P, _I, _P, _I, _P, _I, _P],
     "dh_lstm_decode_step": [_c.POINTER(LstmModel), _c.POINTER(LstmScratch), _P, _P, _I, _I, _P, _I, _I, _I, _I, _I, _P,
                             _I, _P, _I, _P, _I, _P],
     "dh_vocab_logprob": [_P, _I, _P, _I, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P],
@@ -155,6 +158,7 @@ SIGNATURES = {
     "dh_beam_finalize": [_P, _I, _P, _P, _P, _P, _I, _P, _I, _I, _I, _I, _I, _F, _P, _U64, _P, _I, _P],
     "dh_beam_finalize_beams": [_P, _I, _P, _P, _P, _P, _I, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P, _F, _P, _U64, _P,
                                _I, _P],
+    "dh_beam_gather_attention": [_P, _P, _I, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P],
     "dh_beam_filter_top_k": [_P, _I, _I, _I, _I, _I, _P],
     "dh_beam_sample_k": [_P, _I, _I, _I, _I, _F, _P, _I, _U64, _P, _I, _I, _P, _P, _P],
     "dh_beam_gather": [_P, _I, _I, _P, _I, _P, _I, _P, _P],

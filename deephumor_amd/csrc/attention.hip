@@ -890,3 +890,90 @@ extern "C" int dh_attn_cross_prefill_packed(const void* q, int ldq, const void* 
     }
     DH_LAUNCH_CHECK();
 }
+
+
+// ---- head-mean attention weights of one decode position (generate_batch(..., return_attention=True)) --------------------------
+// out[rl, j] = mean over heads of softmax_j(q_h . k_{h,j} / scale) for the compact row rc = img * rows_per_img + w, written at its
+// LOGICAL row rl = rc * row_mult (the mapping dh_attn_self_decode uses for its cache).  A side launch next to the cross-attention
+// kernels above, which keep their weights in registers and never hold the heads of a row in one workgroup.
+// Workgroup = one row, wave = one head (wave wl takes heads wl, wl + nw, ...: nw = min(H, 16) waves), lane = key j (+ 64 per
+// round).  Scores, softmax and the head sum are fp32 with the exact division and expf whatever the storage type.  Every wave adds
+// its heads' weights into its own LDS strip -- slot j of a wave's two strips (this head's exp, its running sum) is only ever
+// touched by lane j % 64 --, and behind ONE barrier the strips are summed in wave order: a fixed order, no atomics, so a row's map
+// does not depend on the batch it is computed in.  (A first form walked the heads of a row in one wave: 24 us per launch at C3,
+// eight dependent load -> reduce -> exp -> reduce chains in a row; a wave per head makes it one.)  Masked keys get -1e8 as
+// masked_fill does (transformers.py:110-111): weight exactly 0 next to a live key, 1 / S when every key is masked.
+template <typename T>
+__global__ __launch_bounds__(1024) void attn_cross_weights_kernel(const T* __restrict__ q, int ldq, const T* __restrict__ kv,
+                                                                   const uint8_t* __restrict__ keymask, float* __restrict__ out,
+                                                                   int rows_per_img, int row_mult, int S, int D, int H, float scale) {
+    constexpr int VN = Vec16<T>::N;
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    const int img = blockIdx.x, w = blockIdx.y, wl = threadIdx.x >> 6, lane = threadIdx.x & 63, nw = blockDim.x >> 6;
+    const int dh = D / H, rc = img * rows_per_img + w;
+    float* ex = smem + (size_t)wl * 2 * S;
+    float* acc = ex + S;
+    for (int j = lane; j < S; j += 64) acc[j] = 0.f;
+    const T* qrow = q + (size_t)rc * ldq;
+    const T* kimg = kv + (size_t)img * S * (2 * D);
+    const uint8_t* mimg = keymask + (size_t)img * S;
+    for (int h = wl; h < H; h += nw) {                              // (wave-uniform trip count)
+        const T* qh = qrow + h * dh;
+        float mx = -INFINITY;
+        for (int j = lane; j < S; j += 64) {
+            float e = -1e8f;
+            if (mimg[j] == 0) {
+                const T* kp = kimg + (size_t)j * (2 * D) + h * dh;
+                float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f;
+                for (int d = 0; d < dh; d += VN) {
+                    float kk[VN], qq[VN];
+                    load16(kp + d, kk);
+                    load16(qh + d, qq);                             // the same 16 bytes for every lane: one broadcast fetch
+#pragma unroll
+                    for (int u = 0; u < VN; u += 4) {
+                        a0 = fmaf(kk[u], qq[u], a0); a1 = fmaf(kk[u + 1], qq[u + 1], a1);
+                        a2 = fmaf(kk[u + 2], qq[u + 2], a2); a3 = fmaf(kk[u + 3], qq[u + 3], a3);
+                    }
+                }
+                e = ((a0 + a1) + (a2 + a3)) / scale;
+            }
+            ex[j] = e;
+            mx = fmaxf(mx, e);
+        }
+        mx = wave_max(mx);
+        float sum = 0.f;
+        for (int j = lane; j < S; j += 64) {
+            const float e = expf(ex[j] - mx);
+            ex[j] = e;
+            sum += e;
+        }
+        sum = wave_sum(sum);
+        for (int j = lane; j < S; j += 64) acc[j] += ex[j] / sum;   // as torch.softmax, then this wave's heads in head order
+    }
+    __syncthreads();
+    float* orow = out + (size_t)rc * row_mult * S;
+    for (int j = threadIdx.x; j < S; j += blockDim.x) {
+        float s = 0.f;
+        for (int wv = 0; wv < nw; ++wv) s += smem[(size_t)(2 * wv + 1) * S + j];      // the waves' strips in wave order
+        orow[j] = s / (float)H;
+    }
+}
+
+extern "C" int dh_attn_cross_weights(const void* q, int ldq, const void* kv, const uint8_t* keymask, float* out, int n_img,
+                                     int rows_per_img, int row_mult, int S, int D, int n_heads, float scale, int dtype, void* stream) {
+    DH_REQUIRE(q && kv && keymask && out && n_img > 0 && rows_per_img > 0 && rows_per_img <= DH_BEAM_MAX_BEAMS && row_mult > 0);
+    DH_REQUIRE(S > 0 && n_heads > 0 && D > 0 && D % n_heads == 0 && ((D / n_heads) % 8) == 0 && ldq >= D && (ldq % 8) == 0);
+    DH_REQUIRE(((uintptr_t)q % 16) == 0 && ((uintptr_t)kv % 16) == 0 && scale != 0.f);
+    // two fp32 strips of S per wave; one wave per head up to 16 (1,024 threads), fewer when S is long
+    const size_t per_wave = (size_t)2 * S * sizeof(float);
+    if (per_wave > 65536) return DH_ERR_UNSUPPORTED;
+    int nw = n_heads < 16 ? n_heads : 16;
+    while ((size_t)nw * per_wave > 65536) nw >>= 1;
+    const double esz_ = dtype == DH_F32 ? 4.0 : 2.0;
+    DhProfScope prof("dh_attn_cross_weights", 2.0 * n_img * rows_per_img * S * D,
+                     esz_ * n_img * (S * 1.0 * D + rows_per_img * 1.0 * D) + 4.0 * n_img * rows_per_img * S, stream);
+    const dim3 grid(n_img, rows_per_img), block(64 * nw);
+    DH_DISPATCH_T(dtype, hipLaunchKernelGGL(attn_cross_weights_kernel<T>, grid, block, (size_t)nw * per_wave, (hipStream_t)stream,
+                                            (const T*)q, ldq, (const T*)kv, keymask, out, rows_per_img, row_mult, S, D, n_heads, scale));
+    DH_LAUNCH_CHECK();
+}

@@ -1480,3 +1480,34 @@ extern "C" int dh_beam_finalize_beams(const int32_t* tokens, int tok_ld, const f
                        len_bias_done, full_len, pad_index, eos_index, pos, first_pos, temperature, noise, seed, seed_ptr, img0);
     DH_LAUNCH_CHECK();
 }
+
+// ---- return_attention: every kept beam's attention maps, through the ancestor table ----------------------------------------------
+// out[i, j, c, :] = attn_w[c, src[i * beam + index[i, j], c], :] for c < len[i, j], else 0: slot j of image i holds engine beam
+// index[i, j] (dh_beam_finalize_beams' out_index / out_len), and position c of that beam's history was computed by the logical row
+// its src row names -- the indirection the KV cache is read through, so no map is ever copied when beams are shuffled.
+// One workgroup of 64 lanes per (slot, column c); a src entry outside [0, rows_total) gives a zero row, never a foreign read.
+__global__ __launch_bounds__(64) void beam_gather_attention_kernel(const float* __restrict__ attn_w, const int32_t* __restrict__ src, int src_ld,
+                                                                    const int32_t* __restrict__ index, const int32_t* __restrict__ len,
+                                                                    float* __restrict__ out, int beam, int T, int rows_total, int S) {
+    const int slot = blockIdx.x, c = blockIdx.y, img = slot / beam, lane = threadIdx.x;
+    float* dst = out + ((size_t)slot * T + c) * S;
+    const int b = index[slot];
+    int row = -1;
+    if (c < len[slot] && b >= 0 && b < beam) row = src[(size_t)(img * beam + b) * src_ld + c];
+    if (row < 0 || row >= rows_total) {
+        for (int s = lane; s < S; s += 64) dst[s] = 0.f;
+        return;
+    }
+    const float* from = attn_w + ((size_t)c * rows_total + row) * S;
+    for (int s = lane; s < S; s += 64) dst[s] = from[s];
+}
+
+extern "C" int dh_beam_gather_attention(const float* attn_w, const int32_t* src, int src_ld, const int32_t* index, const int32_t* len,
+                                        float* out, int n_img, int beam, int T, int n_pos, int rows_total, int S, void* stream) {
+    DH_REQUIRE(attn_w && src && index && len && out && n_img > 0 && beam >= 1 && beam <= DH_BEAM_MAX_BEAMS);
+    DH_REQUIRE(T > 0 && T <= n_pos && src_ld >= T && S > 0 && rows_total >= n_img * beam && T <= 65535);
+    DhProfScope prof("dh_beam_gather_attention", 0.0, 8.0 * n_img * beam * T * S, stream);
+    hipLaunchKernelGGL(beam_gather_attention_kernel, dim3(n_img * beam, T), dim3(64), 0, (hipStream_t)stream, attn_w, src, src_ld, index, len,
+                       out, beam, T, rows_total, S);
+    DH_LAUNCH_CHECK();
+}

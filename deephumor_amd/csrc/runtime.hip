@@ -18,6 +18,17 @@ static int cross_attention(const dh_tr_model_t* m, const dh_tr_layer_t& L, const
     return dh_attn_cross_decode(q, m->D, L.kv, m->keymask, att, n_img, rows_per_img, m->S, m->D, m->n_heads, L.ea_scale, dt, stream);
 }
 
+// return_attention: the head-mean softmax weights of layer `attn_layer`'s encoder attention at this position, from the queries its
+// fc_q GEMM has just left in sc->q (natural layout on every chain) and the layer's unpacked K -> slab t of attn_w [n_pos][rows_total][S],
+// at the rows' logical slots like the KV cache.  A launch of its own: the cross-attention kernels are untouched.
+struct AttnTap { float* w; int layer; };
+static int attention_tap(const dh_tr_model_t* m, const dh_tr_layer_t& L, int l, const AttnTap& tap, const void* q, int n_img, int rows_per_img,
+                         int row_mult, int rows_total, int t, int dt, void* stream) {
+    if (!tap.w || l != tap.layer) return DH_OK;
+    return dh_attn_cross_weights(q, m->D, L.kv, m->keymask, tap.w + (size_t)t * rows_total * m->S, n_img, rows_per_img, row_mult, m->S, m->D,
+                                 m->n_heads, L.ea_scale, dt, stream);
+}
+
 // The classifier of a beam-search step with group maxima: the register-streamed kernel (csrc/vocab_wreg.hip; bit-identical) when the model
 // carries its operands and it takes the shape, else dh_vocab_logits.  Option "vocab_wreg" = 0 switches it off (A/B runs).
 static int classifier_groups(const void* A, int lda, const void* W, const float* bias, const void* W_pk, const float* bias_pad, float* logits,
@@ -67,11 +78,11 @@ static int plain_linear(const void* A, int lda, const void* W, const void* W_x, 
 // mean / rstd on the accumulators) and onto the residual operand of the next output projection (transformers.py:356-375).
 static int decode_position_deferred(const dh_tr_model_t* m, const dh_tr_scratch_t* sc, const int32_t* tokens, int tok_ld,
                                     const int32_t* src, int src_ld, int n_img, int rows_per_img, int row_mult, int rows_total,
-                                    int t, void* x_final, void* stream) {
+                                    int t, void* x_final, const AttnTap& tap, void* stream) {
     const int rows = n_img * rows_per_img, D = m->D, PF = m->pf_dim, dt = m->dtype, nt = D / 64;
     // Option "decode_layers": every layer of the position as ONE persistent launch (csrc/decode_layers.hip; clusters of 8 workgroups own
     // 40 rows through all layers; bit-identical to the launches below)
-    const bool layers = dh_opt(DH_OPT_DECODE_LAYERS) && m->layers_table && m->layers_sync && dh_opt(DH_OPT_DECODE_WREG) &&
+    const bool layers = !tap.w && dh_opt(DH_OPT_DECODE_LAYERS) && m->layers_table && m->layers_sync && dh_opt(DH_OPT_DECODE_WREG) &&
                         dh_decode_layers_supported(m, rows_per_img, t);
     if (layers) {
         DH_TRY(dh_decode_layers(m, sc, m->layers_table, tokens, tok_ld, src, src_ld, n_img, rows_per_img, row_mult, rows_total, t, m->layers_sync, stream));
@@ -102,6 +113,7 @@ static int decode_position_deferred(const dh_tr_model_t* m, const dh_tr_scratch_
             f.a_stats = sc->st1; f.a_tiles = nt; f.a_eps = L.ln1_eps; f.a_colsum = L.cs_q;
             dh_prof_set_tag("proj");
             DH_TRY(chain_linear(sc->o, D, L.wq_f, L.wq_pk, L.bq_f, nullptr, 0, sc->q, D, rows, D, D, 0, &f, dt, stream));
+            DH_TRY(attention_tap(m, L, l, tap, sc->q, n_img, rows_per_img, row_mult, rows_total, t, dt, stream));
             DH_TRY(cross_attention(m, L, sc->q, sc->att, n_img, rows_per_img, dt, stream));
             // 4. Y2 = LN1(Y1) + att Weo^T + beo, statistics -> st2
             f = dh_ln_fold_t{};
@@ -145,7 +157,7 @@ static bool f32xp_ready(const dh_tr_model_t* m, const dh_tr_scratch_t* sc, int r
 
 static int decode_position_f32xp(const dh_tr_model_t* m, const dh_tr_scratch_t* sc, const int32_t* tokens, int tok_ld, const int32_t* src,
                                  int src_ld, int n_img, int rows_per_img, int row_mult, int rows_total, int t, void* x_out, float* logits,
-                                 int ldl, float* group_max, int gm_ld, void* stream) {
+                                 int ldl, float* group_max, int gm_ld, const AttnTap& tap, void* stream) {
     const int rows = n_img * rows_per_img, D = m->D, PF = m->pf_dim;
     float *x = (float*)sc->x, *o = (float*)sc->o;
     for (int l = 0; l < m->n_layers; ++l) {
@@ -164,6 +176,7 @@ static int decode_position_f32xp(const dh_tr_model_t* m, const dh_tr_scratch_t* 
         if (m->cross) {
             dh_prof_set_tag("proj");
             DH_TRY(dh_linear_f32xp_wreg(sc->xp, L.wq_xp, L.bq, nullptr, 0, (float*)sc->q, D, nullptr, rows, D, D, 0, stream));
+            DH_TRY(attention_tap(m, L, l, tap, sc->q, n_img, rows_per_img, row_mult, rows_total, t, DH_F32, stream));
             DH_TRY(dh_attn_cross_decode(sc->q, D, L.kv, m->keymask, sc->attp, n_img, rows_per_img, m->S, D, m->n_heads, L.ea_scale,
                                         DH_F32_OUT_PLANES, stream));
             dh_prof_set_tag("proj");
@@ -185,12 +198,14 @@ static int decode_position_f32xp(const dh_tr_model_t* m, const dh_tr_scratch_t* 
     return DH_OK;
 }
 
-extern "C" int dh_transformer_decode_position(const dh_tr_model_t* m, const dh_tr_scratch_t* sc,
-                                              const void* start_emb, const int32_t* tokens, int tok_ld,
-                                              const int32_t* src, int src_ld, int n_img, int rows_per_img,
-                                              int row_mult, int rows_total, int t, void* x_out, float* logits,
-                                              int ldl, float* group_max, int gm_ld, void* stream) {
+static int decode_position(const dh_tr_model_t* m, const dh_tr_scratch_t* sc, const void* start_emb, const int32_t* tokens, int tok_ld,
+                           const int32_t* src, int src_ld, int n_img, int rows_per_img, int row_mult, int rows_total, int t, void* x_out,
+                           float* logits, int ldl, float* group_max, int gm_ld, const AttnTap& tap, void* stream) {
     DH_REQUIRE(m && sc && m->layers && n_img > 0 && rows_per_img > 0 && t >= 0 && (!logits || ldl >= m->V));
+    if (tap.w) {
+        DH_REQUIRE(m->cross && m->S > 0 && m->keymask && sc->q && tap.layer >= 0 && tap.layer < m->n_layers && m->layers[tap.layer].kv);
+        DH_REQUIRE(row_mult > 0 && (long long)n_img * rows_per_img * row_mult <= rows_total);
+    }
     const int rows = n_img * rows_per_img, D = m->D, dt = m->dtype;
     const size_t esz = dt == DH_F32 ? 4 : 2;
     DH_TRY(dh_embed_rows(m->tok_emb, m->pos_emb, start_emb, tokens, tok_ld, sc->x, rows, rows_per_img, row_mult, t,
@@ -203,7 +218,7 @@ extern "C" int dh_transformer_decode_position(const dh_tr_model_t* m, const dh_t
     }
     if (deferred) {
         void* xf = x_out ? x_out : sc->att;          // the final LayerNorm's output feeds the classifier (att is free by then)
-        DH_TRY(decode_position_deferred(m, sc, tokens, tok_ld, src, src_ld, n_img, rows_per_img, row_mult, rows_total, t, xf, stream));
+        DH_TRY(decode_position_deferred(m, sc, tokens, tok_ld, src, src_ld, n_img, rows_per_img, row_mult, rows_total, t, xf, tap, stream));
         if (logits && group_max) {
             DH_TRY(classifier_groups(xf, D, m->cls_w, m->cls_b, m->cls_w_pk, m->cls_b_pad, logits, ldl, group_max, gm_ld, rows, m->V, D, dt, stream));
         } else if (logits) {
@@ -215,7 +230,7 @@ extern "C" int dh_transformer_decode_position(const dh_tr_model_t* m, const dh_t
     }
     if (f32xp_ready(m, sc, rows))
         return decode_position_f32xp(m, sc, tokens, tok_ld, src, src_ld, n_img, rows_per_img, row_mult, rows_total, t, x_out, logits, ldl,
-                                     group_max, gm_ld, stream);
+                                     group_max, gm_ld, tap, stream);
     for (int l = 0; l < m->n_layers; ++l) {
         const dh_tr_layer_t& L = m->layers[l];
         dh_prof_set_tag("qkv");
@@ -228,6 +243,7 @@ extern "C" int dh_transformer_decode_position(const dh_tr_model_t* m, const dh_t
         if (m->cross) {
             dh_prof_set_tag("proj");
             DH_TRY(plain_linear(sc->x, D, L.wq, L.wq_x, L.wq_xp, D, L.bq, sc->q, D, rows, D, D, 0, dt, stream));
+            DH_TRY(attention_tap(m, L, l, tap, sc->q, n_img, rows_per_img, row_mult, rows_total, t, dt, stream));
             DH_TRY(cross_attention(m, L, sc->q, sc->att, n_img, rows_per_img, dt, stream));
             dh_prof_set_tag("proj");
             DH_TRY(plain_linear(sc->att, D, L.weo, L.weo_x, L.weo_xp, D, L.beo, sc->o, D, rows, D, D, 0, dt, stream));
@@ -260,6 +276,26 @@ extern "C" int dh_transformer_decode_position(const dh_tr_model_t* m, const dh_t
         }
     }
     return DH_OK;
+}
+
+extern "C" int dh_transformer_decode_position(const dh_tr_model_t* m, const dh_tr_scratch_t* sc,
+                                              const void* start_emb, const int32_t* tokens, int tok_ld,
+                                              const int32_t* src, int src_ld, int n_img, int rows_per_img,
+                                              int row_mult, int rows_total, int t, void* x_out, float* logits,
+                                              int ldl, float* group_max, int gm_ld, void* stream) {
+    return decode_position(m, sc, start_emb, tokens, tok_ld, src, src_ld, n_img, rows_per_img, row_mult, rows_total, t, x_out, logits, ldl,
+                           group_max, gm_ld, AttnTap{nullptr, 0}, stream);
+}
+
+// The same position with the attention tap on (always the launch chain, never the persistent layer kernel, which leaves no q behind).
+extern "C" int dh_transformer_decode_position_attn(const dh_tr_model_t* m, const dh_tr_scratch_t* sc,
+                                                   const void* start_emb, const int32_t* tokens, int tok_ld,
+                                                   const int32_t* src, int src_ld, int n_img, int rows_per_img,
+                                                   int row_mult, int rows_total, int t, void* x_out, float* logits,
+                                                   int ldl, float* group_max, int gm_ld, float* attn_w, int attn_layer, void* stream) {
+    DH_REQUIRE(attn_w);
+    return decode_position(m, sc, start_emb, tokens, tok_ld, src, src_ld, n_img, rows_per_img, row_mult, rows_total, t, x_out, logits, ldl,
+                           group_max, gm_ld, AttnTap{attn_w, attn_layer}, stream);
 }
 
 extern "C" int dh_lstm_decode_step(const dh_lstm_model_t* m, const dh_lstm_scratch_t* sc, const void* img_emb,

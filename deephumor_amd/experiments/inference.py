@@ -104,6 +104,21 @@ def rank_beams(model, inputs, beams, labels=None):
     return torch.argsort(pp, dim=1, stable=True), pp
 
 
+def attention_to_heatmaps(attention, size=(224, 224), grid=(7, 7)):
+    """``generate_batch(..., return_attention=True)``'s maps as images: ``attention [..., S]`` (weights over the ``grid[0] * grid[1]``
+    image patches in row-major order; keys beyond them -- the padded rows of a ``pad_index >= 2`` decoder -- are dropped) ->
+    fp32 ``[..., H, W]`` by bilinear upsampling (``align_corners=False``: every patch spreads over its own ``H / 7 x W / 7`` cell and
+    blends into its neighbours; for whole multiples of the grid the upsampled map has the patch map's mean).  A row that is all
+    zero -- a column past the caption's length -- stays all zero.  Post-processing for display, on the tensor's own device."""
+    gh, gw = grid
+    if attention.shape[-1] < gh * gw:
+        raise ValueError(f"attention has {attention.shape[-1]} keys, fewer than the {gh} x {gw} grid")
+    lead = attention.shape[:-1]
+    maps = attention[..., :gh * gw].float().reshape(-1, 1, gh, gw)
+    out = torch.nn.functional.interpolate(maps, size=tuple(size), mode="bilinear", align_corners=False)
+    return out.reshape(*lead, *size)
+
+
 def _clean_block(block):
     block = _SPECIAL.sub('', block).strip(' \t\n\r\f\v')
     return _SPACE_BEFORE_PUNCT.sub(r'\2', block)

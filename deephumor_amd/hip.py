@@ -704,6 +704,16 @@ def attn_cross_decode(q, kv, keymask, out, n_img, rows_per_img, s, d, n_heads, s
     return out
 
 
+def attn_cross_weights(q, kv, keymask, out, n_img, rows_per_img, row_mult, s, d, n_heads, scale):
+    """``dh_attn_cross_weights``: the head-mean softmax weights of one cross-attention position -> fp32 ``out[rc * row_mult, :s]``
+    (``out`` viewed as rows of ``s`` floats) for every compact row ``rc``."""
+    _dev(q, kv, keymask, out)
+    assert out.dtype == torch.float32 and out.is_contiguous() and keymask.dtype == torch.uint8
+    _launch("dh_attn_cross_weights", _ptr(q), q.stride(0), _ptr(kv), _ptr(keymask), _ptr(out), n_img, rows_per_img, row_mult, s, d,
+            n_heads, float(scale), _dt(q), _stream())
+    return out
+
+
 def embed_prefill(tok_emb, pos_emb, start_emb, tokens, n_seq, n_pos, scale):
     """Sequence-major rows [n_seq * n_pos, D] of all positions (teacher forcing)."""
     _dev(tok_emb, pos_emb, start_emb, tokens)
@@ -1014,6 +1024,21 @@ def beam_finalize_beams(tokens, vals, done, end_step, out_tokens, out_len, out_s
             _ptr(seed_ptr), img0, _stream())
 
 
+def beam_gather_attention(attn_w, src, index, lengths, out):
+    """``dh_beam_gather_attention``: ``out[i, j, c] = attn_w[c, src[i * beam + index[i, j], c]]`` for ``c < lengths[i, j]``, else 0.
+    ``attn_w`` fp32 ``[n_pos, rows_total, S]``, ``src`` int32 ``[rows_total, >= T]``, ``index`` / ``lengths`` int32 ``[N, B]``,
+    ``out`` fp32 ``[N, B, T, S]``."""
+    _dev(attn_w, src, index, lengths, out)
+    n, b, t, s = out.shape
+    n_pos, rows_total, s_w = attn_w.shape
+    assert s_w == s and attn_w.is_contiguous() and out.is_contiguous() and attn_w.dtype == out.dtype == torch.float32
+    assert src.dtype == index.dtype == lengths.dtype == torch.int32 and src.stride(1) == 1 and src.shape[0] == rows_total
+    assert index.is_contiguous() and lengths.is_contiguous() and index.shape == lengths.shape == (n, b)
+    _launch("dh_beam_gather_attention", _ptr(attn_w), _ptr(src), src.stride(0), _ptr(index), _ptr(lengths), _ptr(out), n, b, t, n_pos,
+            rows_total, s, _stream())
+    return out
+
+
 GROUP_COLS = 64     # column-group width of dh_vocab_logits' group maxima
 
 
@@ -1022,7 +1047,13 @@ def n_groups(v):
 
 
 def transformer_decode_position(model, scratch, start_emb, tokens, src, n_img, rows_per_img, row_mult, rows_total, t,
-                                x_out=None, logits=None, group_max=None):
+                                x_out=None, logits=None, group_max=None, attn_w=None, attn_layer=0):
+    if attn_w is not None:      # return_attention: the same position with the attention tap (dh_transformer_decode_position_attn)
+        _launch("dh_transformer_decode_position_attn", _c.byref(model), _c.byref(scratch), _ptr(start_emb), _ptr(tokens),
+                tokens.stride(0), _ptr(src), src.stride(0), n_img, rows_per_img, row_mult, rows_total, t, _ptr(x_out),
+                _ptr(logits), logits.stride(0) if logits is not None else 0, _ptr(group_max),
+                group_max.stride(0) if group_max is not None else 0, _ptr(attn_w), int(attn_layer), _stream())
+        return
     _launch("dh_transformer_decode_position", _c.byref(model), _c.byref(scratch), _ptr(start_emb), _ptr(tokens),
             tokens.stride(0), _ptr(src), src.stride(0), n_img, rows_per_img, row_mult, rows_total, t, _ptr(x_out),
             _ptr(logits), logits.stride(0) if logits is not None else 0, _ptr(group_max),

@@ -67,6 +67,24 @@ def check_return_beams(return_beams):
     return return_beams
 
 
+def check_return_attention(return_attention, model=None):
+    """``return_attention`` is a plain bool, checked where ``check_return_beams`` is, before anything runs.  With ``model`` (a captioning
+    model or its decoder) and the keyword on: a decoder without encoder attention (the LSTM kinds, ``CaptioningTransformerBase``) has no
+    map to return -- a ``TypeError`` that says so; ``pad_index == 1`` decodes by full re-forward on the module path, which keeps no
+    per-position queries -- ``NotImplementedError``, as ``caption_lengths`` there."""
+    if not isinstance(return_attention, bool):
+        raise TypeError(f"return_attention must be a bool, not {type(return_attention).__name__}")
+    if return_attention and model is not None:
+        dec = getattr(model, "decoder", model)
+        if not getattr(dec, "_cross", False):
+            raise TypeError(f"return_attention: {type(model).__name__} has no encoder attention (only CaptioningTransformer and "
+                            "CaptioningTransformerWithLabels attend over the image features)")
+        if getattr(dec, "pad_index", 0) == 1:
+            raise NotImplementedError("return_attention with pad_index == 1: that decoder re-runs the whole sequence per token on the "
+                                      "module path (_generate_reforward), which keeps no per-position attention weights")
+    return return_attention
+
+
 def check_top_p(top_p):
     """``top_p`` is a real number in ``(0, 1]`` (1.0: no nucleus, today's kernels): checked where ``check_return_beams`` is, before
     anything runs.  A ``bool`` is a misplaced flag, not a probability.  Returns it as a float."""
@@ -563,7 +581,7 @@ class BeamSearchHelper:
                         first_sets_ended, write_pos, t, step_index, self.temperature, self.eos_index, noise,
                         self.seed, self.img0, seed_ptr=self.seed_tensor)
 
-    def finalize(self, len_bias_done, full_len, pad_index=0, defer_check=False, first_beam=False, beams=False, pos=0):
+    def finalize(self, len_bias_done, full_len, pad_index=0, defer_check=False, first_beam=False, beams=False, pos=0, attn_w=None):
         """Final draw among the beams and output copy; returns (tokens int64 [n_img, max_len], lengths).
         ``defer_check``: skip the host read of the device error word (hipGraph capture) -- the caller checks
         ``self.err`` after replay.  ``first_beam``: no draw, beam 0 -- what the reference's final
@@ -571,13 +589,17 @@ class BeamSearchHelper:
         first step (rnn_models.py:93, 140-141: no decode step ran because the prefix already fills ``max_len - 1``).
         ``beams=True``: one launch of ``dh_beam_finalize_beams`` instead -- the same draw, and every beam kept: returns a
         ``BeamCaptions`` (then the error word with ``defer_check``).  ``pos``: the first generated column of a dense session (the
-        prefix length), from where a beam's own ``<eos>`` is looked for; a prompted session's comes from ``self.first_pos``."""
+        prefix length), from where a beam's own ``<eos>`` is looked for; a prompted session's comes from ``self.first_pos``.
+        ``attn_w`` (``return_attention``; fp32 ``[n_pos, rows, S]``, slab ``c`` = the maps position ``c`` wrote at its logical rows):
+        always the ``beams`` launch, and one launch of ``dh_beam_gather_attention`` behind it leaves every kept beam's maps -- read
+        through ``self.src``, for the columns below the beam's own length, zero elsewhere -- in ``self.attention`` fp32
+        ``[n_img, beam, max_len, S]``; the return value is that of ``beams=True``."""
         if first_beam:                 # the kernel's race p / noise with an infinite handicap on every beam but the first
             noise = torch.full((self.n_img, self.beam_size), float("inf"), dtype=torch.float32, device=self.device)
             noise[:, 0] = 1.0
         else:
             noise = self._noise("final", 0, (self.n_img, self.beam_size))
-        if beams:
+        if beams or attn_w is not None:
             n, b, dev = self.n_img, self.beam_size, self.device
             out = torch.empty((n, b, self.max_len), dtype=torch.int32, device=dev)
             ints = torch.empty((2 * n * b + 2 * n,), dtype=torch.int32, device=dev)
@@ -586,6 +608,9 @@ class BeamSearchHelper:
             hip.beam_finalize_beams(self.tokens, self.vals, self.done, self.end_step, out, o_len, o_score, o_idx, o_drawn, o_row, n, b,
                                     len_bias_done, full_len, pad_index, self.eos_index, pos, self.first_pos,
                                     self.temperature, noise, self.seed, self.img0, seed_ptr=self.seed_tensor)
+            if attn_w is not None:
+                self.attention = torch.empty((n, b, self.max_len, attn_w.shape[2]), dtype=torch.float32, device=dev)
+                hip.beam_gather_attention(attn_w, self.src, o_idx, o_len, self.attention)
             res = BeamCaptions(out.long(), o_len.long(), o_score, o_idx.long(), o_drawn.long(), o_row.long())
             if defer_check:
                 return res, self.err

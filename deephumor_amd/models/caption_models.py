@@ -40,10 +40,14 @@ class _CaptioningBase(nn.Module):
 
     @staticmethod
     def _one(res):
-        """``generate``'s result from ``generate_batch``'s for one image: the 1-D caption, or the ``BeamCaptions`` as it is."""
+        """``generate``'s result from ``generate_batch``'s for one image: the 1-D caption, or the ``BeamCaptions`` as it is; with
+        ``return_attention=True`` the pair ``(caption, attention [len, S])``, or ``(BeamCaptions, attention [1, B, T, S])`` as it is."""
         from .beam import BeamCaptions
-        if isinstance(res, BeamCaptions):
+        if isinstance(res, BeamCaptions) or isinstance(res[0], BeamCaptions):
             return res
+        if len(res) == 3:
+            toks, lens, att = res
+            return toks[0, :int(lens[0])].squeeze(), att[0, :int(lens[0])]
         toks, lens = res
         return toks[0, :int(lens[0])].squeeze()
 
@@ -65,7 +69,17 @@ class _CaptioningBase(nn.Module):
         ``kw``: no ``<eos>`` at a token position below ``min_len`` / no row completes a banned phrase (``LSTMDecoder.generate_batch``).
         ``caption_lengths`` (keyword only, int64 / int32 ``[N]``): a prompt of its own length per image -- row ``i`` is
         teacher-forced with ``caption[i, :caption_lengths[i]]`` (0: none; the rest of the row is ignored) and equals the dense
-        single-image call with that prompt and ``img0 + i`` (``LSTMDecoder.generate_batch``)."""
+        single-image call with that prompt and ``img0 + i`` (``LSTMDecoder.generate_batch``).
+        ``return_attention=True`` (in ``kw``, a plain bool; ``CaptioningTransformer`` / ``CaptioningTransformerWithLabels`` only): one
+        more result, an fp32 device tensor that says where the model looked for every token -- ``(tokens, lengths, attention
+        [N, T, S])``, or ``(BeamCaptions, attention [N, B, T, S])`` with ``return_beams=True`` in ``BeamCaptions`` slot order; ``T`` the
+        width of ``tokens``, ``S`` the number of encoder keys (49; ``max(49, max_len + 1)`` with ``pad_index >= 2``, whose padded
+        rows are keys).  ``attention[i, (slot,) c]`` is the mean over heads of the LAST decoder layer's encoder-attention softmax
+        (reference transformers.py:106-115) at decode position ``c`` -- the position whose logits token column ``c`` was drawn from
+        (or teacher-forced past, for prompt columns) -- taken on the row that computed that position of this beam's history.  Rows
+        ``c <`` the beam's own length (``BeamCaptions.lengths``; the drawn beam's for the plain call) are filled and sum to 1; every
+        other element is exactly 0.  A masked key has weight exactly 0 unless every key is masked (uniform ``1 / S``).  It changes
+        no token; the other kinds raise ``TypeError``, ``pad_index == 1`` ``NotImplementedError`` (``beam.check_return_attention``)."""
         if caption_lengths is not None:
             kw["caption_lengths"] = caption_lengths
         return self.decoder.generate_batch(*encoded, caption=caption, max_len=max_len, temperature=temperature,
@@ -75,8 +89,13 @@ class _CaptioningBase(nn.Module):
         """A prompted batch is validated BEFORE the encoder runs (``beam.check_prompts`` / ``prompt_session_inputs``: shapes, ranges,
         the options it cannot be combined with); ``defer_check`` callers (graph capture, the pipeline) with device-resident lengths
         have done so themselves.  So is the type of ``return_beams`` (``beam.check_return_beams``) and the range of ``top_p`` (``beam.check_top_p``), for every batch."""
-        from .beam import check_constraints, check_prompts, check_repeat, check_return_beams, check_top_p, prompts_need_philox
+        from .beam import check_constraints, check_prompts, check_repeat, check_return_attention, check_return_beams, check_top_p, prompts_need_philox
         check_return_beams(kw.get("return_beams", False))
+        if "return_attention" in kw:
+            # (a plain bool; on, it needs a decoder with encoder attention on the KV-cached engine: beam.check_return_attention.  Off, it
+            # is the call without the keyword -- also for the kinds whose decoders do not know it)
+            if not check_return_attention(kw["return_attention"], self) and not getattr(self.decoder, "_cross", False):
+                del kw["return_attention"]
         check_top_p(kw.get("top_p", 1.0))
         check_repeat(kw.get("no_repeat_ngram_size", 0), kw.get("repetition_penalty", 1.0), max_len)      # (beam.check_repeat: likewise)
         check_constraints(kw.get("min_len", 0), kw.get("bad_words_ids"), max_len, self._hp["num_tokens"])   # (beam.check_constraints: likewise)
@@ -125,6 +144,11 @@ class _CaptioningBase(nn.Module):
         # ``return_beams=True`` is part of the cache key like every decode setting (``kw``): its graph ends in dh_beam_finalize_beams and
         # lives beside the plain one of the same shapes; a replay returns clones of every field
         check_return_beams(kw.get("return_beams", False))
+        # ``return_attention=True`` likewise: its graph holds one dh_attn_cross_weights node per position and the gather behind the
+        # final draw, lives beside the plain one of the same shapes, and a replay returns a clone of the maps too
+        from .beam import check_return_attention
+        if not check_return_attention(kw.get("return_attention", False), self):
+            kw.pop("return_attention", None)          # (False is the call without the keyword: the plain graph, not a second one)
         # ``top_p`` rides in ``kw`` too, so it is in the key below: a top_p = 0.8 graph (nucleus row draws) lives beside the plain one
         check_top_p(kw.get("top_p", 1.0))
         # so do ``no_repeat_ngram_size`` / ``repetition_penalty``: their graph holds one dh_beam_history_logits node per position (the
@@ -220,9 +244,10 @@ class _CaptioningBase(nn.Module):
             warn_overflow_retry()         # configuration) eagerly through the general sampler
             eager_keys[key] = self._plan_signature()
             return self.generate_batch(*inputs, caption=caption, seed=seed, exact=True, **lens_kw, **kw)
-        if isinstance(out[0], BeamCaptions):          # (BeamCaptions, error word): clones of every field
-            return out[0].map(torch.Tensor.clone)
-        return out[0].clone(), out[1].clone()
+        if isinstance(out[0], BeamCaptions):          # (BeamCaptions, [attention,] error word): clones of every field
+            beams = out[0].map(torch.Tensor.clone)
+            return (beams, out[1].clone()) if len(out) == 3 else beams
+        return tuple(t.clone() for t in out[:-1])     # (tokens, lengths, [attention,] error word)
 
 
 class CaptioningLSTM(_CaptioningBase):

@@ -21,7 +21,7 @@ from torch import nn
 
 from .. import hip
 from ._f32x_guard import f32x_guarded
-from .beam import BeamCaptions, BeamOverflow, BeamSearchHelper, call_logits_hook, check_ids, check_return_beams, check_top_p, check_repeat, check_constraints, compile_bad_words, classifier_must_be_finite, make_noise_source, prompt_session_inputs, resolve_seed, run_interleaved, warn_overflow_retry
+from .beam import BeamCaptions, BeamOverflow, BeamSearchHelper, call_logits_hook, check_ids, check_return_attention, check_return_beams, check_top_p, check_repeat, check_constraints, compile_bad_words, classifier_must_be_finite, make_noise_source, prompt_session_inputs, resolve_seed, run_interleaved, warn_overflow_retry
 from .encoders import _Planned
 
 
@@ -354,12 +354,14 @@ class _IncrementalDecoder(_Planned, nn.Module):
             return self._scratch[rows]
 
     def _decode_position(self, plan, run, t, rows, rpi, mult, tokens, src, start_emb, x_out=None, logits=None,
-                         group_max=None):
+                         group_max=None, attn_w=None):
         """Hidden state of position ``t`` for ``rows`` compact rows (all layers) [rows, D]; with ``logits``
-        (fp32 [rows, V]) also the classifier -- one native call (``dh_transformer_decode_position``)."""
+        (fp32 [rows, V]) also the classifier -- one native call (``dh_transformer_decode_position``).  ``attn_w`` (``return_attention``;
+        fp32 ``[n_pos, rows_total, S]``): the last layer's head-mean encoder-attention weights of the position go to its slab ``t``."""
         sc = run.scratch(rows)
         hip.transformer_decode_position(run.c_model, sc["c"], start_emb, tokens, src, run.n_img, rpi, mult,
-                                        run.rows_total, t, x_out=x_out, logits=logits, group_max=group_max)
+                                        run.rows_total, t, x_out=x_out, logits=logits, group_max=group_max,
+                                        attn_w=attn_w, attn_layer=len(self.layers) - 1)
         return x_out if x_out is not None else sc["x"]
 
     def _forward(self, x, enc_out, start_emb, num_positions=None, return_hidden=False):
@@ -544,17 +546,22 @@ class _IncrementalDecoder(_Planned, nn.Module):
 
     @staticmethod
     def _one(res):
-        """``generate``'s result from ``_generate_batch``'s for one image: the caption, or the ``BeamCaptions`` (N = 1) as it is."""
-        if isinstance(res, BeamCaptions):
+        """``generate``'s result from ``_generate_batch``'s for one image: the caption, or the ``BeamCaptions`` (N = 1) as it is; with
+        ``return_attention=True`` the pair ``(caption, attention [len, S])``, or ``(BeamCaptions, attention [1, B, T, S])`` as it is."""
+        if isinstance(res, BeamCaptions) or isinstance(res[0], BeamCaptions):
             return res
+        if len(res) == 3:
+            toks, lens, att = res
+            return toks[0, :int(lens[0])].squeeze(), att[0, :int(lens[0])]
         toks, lens = res
         return toks[0, :int(lens[0])].squeeze()
 
     def _generate_batch(self, start_emb, enc_out, caption, max_len, temperature, beam_size, top_k, eos_index,
                         seed=None, img0=0, noise_source=None, logits_hook=None, streams=1, seed_tensor=None,
                         defer_check=False, early_stop_every=0, exact=False, rng=None, caption_lengths=None, return_beams=False, top_p=1.0,
-                        no_repeat_ngram_size=0, repetition_penalty=1.0, min_len=0, bad_words_ids=None):
+                        no_repeat_ngram_size=0, repetition_penalty=1.0, min_len=0, bad_words_ids=None, return_attention=False):
         check_return_beams(return_beams)
+        check_return_attention(return_attention, self)
         top_p = check_top_p(top_p)
         no_repeat_ngram_size, repetition_penalty = check_repeat(no_repeat_ngram_size, repetition_penalty, max_len)
         min_len, bad_words_ids = check_constraints(min_len, bad_words_ids, max_len, self.num_tokens)
@@ -612,15 +619,16 @@ class _IncrementalDecoder(_Planned, nn.Module):
                 helper.tokens.fill_(self.pad_index)
             helper.set_prompts(cap[lo:hi], first_pos[lo:hi], self.pad_index)
             run = self._Run(self, plan, n, b, max_len + 1, None if enc_out is None else enc_out[lo:hi], dev, use_layers=False)
+            attn_w = torch.empty((max_len + 1, r, run.s), device=dev, dtype=torch.float32) if return_attention else None
             semb = start_emb[lo:hi]
             logits = torch.empty((r, (self.num_tokens + 255) // 256 * 256), device=dev)[:, :self.num_tokens]
             gmax = (torch.empty((r, 4 * ((self.num_tokens + 255) // 256)), device=dev)[:, :hip.n_groups(self.num_tokens)]
                     if plan["dtype"] in hip.HALF_DTYPES or plan.get("f32_planes") else None)
             for t in range(pmin):
-                self._decode_position(plan, run, t, n, 1, b, helper.tokens, helper.src, semb)
+                self._decode_position(plan, run, t, n, 1, b, helper.tokens, helper.src, semb, attn_w=attn_w)
                 yield
             for i in range(pmin, max_len + 1):
-                self._decode_position(plan, run, i, r, b, 1, helper.tokens, helper.src, semb, logits=logits, group_max=gmax)
+                self._decode_position(plan, run, i, r, b, 1, helper.tokens, helper.src, semb, logits=logits, group_max=gmax, attn_w=attn_w)
                 if logits_hook is not None:
                     call_logits_hook(logits_hook, i, logits, helper)
                 if i <= pmax:
@@ -630,8 +638,11 @@ class _IncrementalDecoder(_Planned, nn.Module):
                 yield
                 if early_stop_every and i > pmax and (i - pmax) % early_stop_every == 0 and bool(helper.done.all()):
                     break
-            return helper.finalize(len_bias_done=0, full_len=max_len, pad_index=self.pad_index, defer_check=defer_check,
-                                   beams=return_beams)
+            out = helper.finalize(len_bias_done=0, full_len=max_len, pad_index=self.pad_index, defer_check=defer_check,
+                                  beams=return_beams, attn_w=attn_w)
+            if return_attention:
+                maps[lo] = helper.attention
+            return out
 
         def session(lo, hi):
             """Decodes images [lo, hi); yields after every position (see ``run_interleaved``)."""
@@ -651,7 +662,10 @@ class _IncrementalDecoder(_Planned, nn.Module):
             if caption is not None:
                 pos = caption.shape[1]
                 helper.set_prefix(caption[lo:hi])
-            run = self._Run(self, plan, n, b, max_len + 1, None if enc_out is None else enc_out[lo:hi], dev)
+            # (return_attention: always the launch chain -- the persistent layer kernel leaves no q behind)
+            run = self._Run(self, plan, n, b, max_len + 1, None if enc_out is None else enc_out[lo:hi], dev, use_layers=not return_attention)
+            # the positions' maps [position, logical row, key], position-major like the KV cache; beams read them through helper.src
+            attn_w = torch.empty((max_len + 1, r, run.s), device=dev, dtype=torch.float32) if return_attention else None
             semb = start_emb[lo:hi]
             # logits always fp32; row stride padded to 64 floats so rows are 16-byte aligned (vector stores)
             logits = torch.empty((r, (self.num_tokens + 255) // 256 * 256), device=dev)[:, :self.num_tokens]   # whole 256-column chunks (vocab_wreg)
@@ -662,14 +676,14 @@ class _IncrementalDecoder(_Planned, nn.Module):
             lg = logits[:n]
             for t in range(pos + 1):
                 self._decode_position(plan, run, t, n, 1, b, helper.tokens, helper.src, semb,
-                                      logits=lg if t == pos else None, group_max=gm if t == pos else None)
+                                      logits=lg if t == pos else None, group_max=gm if t == pos else None, attn_w=attn_w)
                 yield
             if logits_hook is not None:
                 call_logits_hook(logits_hook, pos, lg, helper)
             helper.step(lg, first=True, write_pos=pos, t=pos, step_index=pos, first_sets_ended=False, group_max=gm)
             for i in range(pos + 1, max_len + 1):
                 self._decode_position(plan, run, i, r, b, 1, helper.tokens, helper.src, semb, logits=logits,
-                                      group_max=gmax)
+                                      group_max=gmax, attn_w=attn_w)
                 if logits_hook is not None:
                     call_logits_hook(logits_hook, i, logits, helper)
                 # at i == max_len nothing is written (transformers.py:557) but beams are still re-drawn
@@ -678,7 +692,9 @@ class _IncrementalDecoder(_Planned, nn.Module):
                 if early_stop_every and (i - pos) % early_stop_every == 0 and bool(helper.done.all()):
                     break                                   # all_ended() break of the reference (transformers.py:585)
             out = helper.finalize(len_bias_done=0, full_len=max_len, pad_index=self.pad_index, defer_check=defer_check,
-                                  beams=return_beams, pos=pos)
+                                  beams=return_beams, pos=pos, attn_w=attn_w)
+            if return_attention:
+                maps[lo] = helper.attention
             if run.layers_sync is not None and not defer_check and int(run.layers_sync[320]) != 0:
                 # a hand-over of the persistent layer kernel timed out (fewer than 256 resident workgroups?): its results are undefined
                 hip.set_option("decode_layers", 0)
@@ -686,15 +702,35 @@ class _IncrementalDecoder(_Planned, nn.Module):
                                    "workgroups; the option has been switched off for this process -- repeat the call")
             return out
 
+        maps = {}                         # return_attention: first image of a session -> its beams' maps [n, B, T, S]
+
+        def with_attention(out):
+            """The sessions ran ``dh_beam_finalize_beams`` (``out``: a ``BeamCaptions``, in front of the error word with
+            ``defer_check``): ``(BeamCaptions, attention [N, B, T, S])`` for ``return_beams``, else the plain pair -- ``best()``, bit
+            for bit -- and the drawn slot's maps ``(tokens, lengths, attention [N, T, S])``."""
+            if not return_attention:
+                return out
+            parts = [maps[lo] for lo in sorted(maps)]
+            for part in parts:
+                part.record_stream(torch.cuda.current_stream())
+            att = parts[0] if len(parts) == 1 else torch.cat(parts, 0)
+            deferred = not isinstance(out, BeamCaptions)
+            bc = out[0] if deferred else out
+            if return_beams:
+                res = (bc, att)
+            else:
+                res = bc.best() + (att[torch.arange(att.shape[0], device=att.device), bc.drawn],)
+            return res + (out[1],) if deferred else res
+
         exact = [bool(exact)]
         try:
-            return run_interleaved(session, start_emb.shape[0], streams)
+            return with_attention(run_interleaved(session, start_emb.shape[0], streams))
         except BeamOverflow:              # flat logits (see LSTMDecoder.generate_batch): once more through the general sampler
             if exact[0]:
                 raise
             exact[0] = True
             warn_overflow_retry()
-            return run_interleaved(session, start_emb.shape[0], streams)
+            return with_attention(run_interleaved(session, start_emb.shape[0], streams))
 
 
 class TransformerDecoder(_IncrementalDecoder):
@@ -718,7 +754,9 @@ class TransformerDecoder(_IncrementalDecoder):
         a prompt of its own length per image, see ``LSTMDecoder.generate_batch``; ``return_beams=True`` (in ``kw``): every beam as a
         ``beam.BeamCaptions``, see there; ``top_p`` (in ``kw``): nucleus filtering beside ``top_k``, see there;
         ``no_repeat_ngram_size`` / ``repetition_penalty`` (in ``kw``): the history edits in front of every row draw, see there;
-        ``min_len`` / ``bad_words_ids`` (in ``kw``): no ``<eos>`` below ``min_len``, no banned phrase, see there."""
+        ``min_len`` / ``bad_words_ids`` (in ``kw``): no ``<eos>`` below ``min_len``, no banned phrase, see there;
+        ``return_attention=True`` (in ``kw``): one more result, the fp32 map of where every token looked -- ``attention [N, T, S]``
+        behind the pair, or ``[N, B, T, S]`` behind the ``BeamCaptions`` -- see ``caption_models._CaptioningBase.decode``."""
         return self._generate_batch(start_emb, enc_out, caption, max_len, temperature, beam_size, top_k,
                                     eos_index, caption_lengths=caption_lengths, **kw)
 

@@ -44,6 +44,11 @@ class CaptionPipeline:
         not per batch, so every batch must have their row count.  Host-resident ``caption_lengths`` are validated with every batch
         (``beam.check_prompts``; like the dense path's id check this reads the range of a device-resident ``caption`` back, one
         host synchronisation per batch); device-resident lengths are not read back here and are the caller's to validate."""
+        from .models.beam import check_return_attention
+        if check_return_attention(gen_kw.get("return_attention", False)):     # (a non-bool: TypeError, as everywhere)
+            raise NotImplementedError("return_attention: CaptionPipeline hands batches over through pinned (tokens, lengths) / BeamCaptions "
+                                      "slots that carry no float payload; call model.generate_batch(..., return_attention=True)")
+        gen_kw.pop("return_attention", None)         # (False: the pipeline without the keyword)
         self.model, self.gen_kw, self.overlap, self.preprocess = model, gen_kw, overlap, preprocess
         self.dev = next(model.parameters()).device
         if overlap:

@@ -357,6 +357,17 @@ int dh_attn_cross_decode(const void* q, int ldq, const void* kv, const uint8_t* 
                          int n_img, int rows_per_img, int S, int D, int n_heads, float scale,
                          int dtype, void* stream);
 
+/* The attention WEIGHTS of that position, averaged over the heads (generate_batch(..., return_attention=True)): for the compact row
+ * rc = img * rows_per_img + w,  out[rc * row_mult, j] = 1 / n_heads * sum_h softmax_j(q[rc, h] . k[img, j, h] / scale), j < S -- the
+ * softmax of transformers.py:106-115 with masked keys at -1e8 (weight exactly 0 beside a live key; 1 / S when every key of the image
+ * is masked).  q, kv (the K half is read) and keymask as for dh_attn_cross_decode, in DH_F32 / DH_BF16 / DH_F16; out fp32, row
+ * stride S, written at the rows' LOGICAL slots (row_mult as in dh_attn_self_decode).  Scores, softmax and the head sum are fp32 with
+ * the exact division and expf for every storage type; one wave per head, the waves' sums added in wave order through LDS (a fixed
+ * order, no atomics).
+ * q and kv 16-byte aligned, ldq % 8 == 0; DH_ERR_UNSUPPORTED beyond S = 8192. */
+int dh_attn_cross_weights(const void* q, int ldq, const void* kv, const uint8_t* keymask, float* out, int n_img,
+                          int rows_per_img, int row_mult, int S, int D, int n_heads, float scale, int dtype, void* stream);
+
 /* The same attention on the matrix cores (16-bit dtypes, head dim 64, S <= 64, rows_per_img <= 16).  dh_attn_cross_pack
  * re-lays kv out ONCE per batch and layer as kp [n_img][n_heads][64 keys][64] and vt [n_img][n_heads][64][64 key slots]
  * (V transposed, key slots permuted into MFMA operand order, keys >= S zero) -- 16 KB per (image, head); dperm != 0
@@ -626,6 +637,14 @@ int dh_beam_finalize_beams(const int32_t* tokens, int tok_ld, const float* vals,
                            int pos, const int32_t* first_pos, float temperature, const float* noise, uint64_t seed,
                            const uint64_t* seed_ptr, int img0, void* stream);
 
+/* The attention maps of the beams dh_beam_finalize_beams kept, one launch behind it:
+ *   out[i, j, c, :] = attn_w[c, src[i * beam + index[i, j], c], :]  for c < len[i, j],  else 0
+ * attn_w fp32 [n_pos, rows_total, S] (slab c = decode position c, dh_transformer_decode_position_attn), src the ancestor table
+ * [rows_total, src_ld] (src[r, c] = the logical row that computed position c of row r's history), index / len = out_index /
+ * out_len [n_img, beam], out fp32 [n_img, beam, T, S] with T <= n_pos, T <= src_ld.  A src entry outside [0, rows_total) gives zeros. */
+int dh_beam_gather_attention(const float* attn_w, const int32_t* src, int src_ld, const int32_t* index, const int32_t* len,
+                             float* out, int n_img, int beam, int T, int n_pos, int rows_total, int S, void* stream);
+
 /* ---------------------------------------------------------------------------------------------
  * Teacher-forced scoring (deephumor/experiments/metrics.py:4-9; call shape trainer.py:69-81)
  * ------------------------------------------------------------------------------------------- */
@@ -725,6 +744,16 @@ int dh_transformer_decode_position(const dh_tr_model_t* m, const dh_tr_scratch_t
                                    const int32_t* src, int src_ld, int n_img, int rows_per_img,
                                    int row_mult, int rows_total, int t, void* x_out, float* logits, int ldl,
                                    float* group_max, int gm_ld, void* stream);
+
+/* dh_transformer_decode_position that also keeps the encoder-attention weights of layer attn_layer: right after that layer's fc_q
+ * GEMM (on each of the three chains) one launch of dh_attn_cross_weights writes slab t of attn_w [n_pos, rows_total, S] at the rows'
+ * logical slots.  Always the launch chain (the persistent layer kernel leaves no q behind).  A new entry point, not new fields of
+ * dh_tr_model_t: no existing prototype or struct changes, so the ABI version stays. */
+int dh_transformer_decode_position_attn(const dh_tr_model_t* m, const dh_tr_scratch_t* sc,
+                                        const void* start_emb, const int32_t* tokens, int tok_ld,
+                                        const int32_t* src, int src_ld, int n_img, int rows_per_img,
+                                        int row_mult, int rows_total, int t, void* x_out, float* logits, int ldl,
+                                        float* group_max, int gm_ld, float* attn_w, int attn_layer, void* stream);
 
 typedef struct dh_lstm_layer {
     const void* w; const float* b;          /* [4Hh, in+Hh] = [W_ih|W_hh], b_ih+b_hh (PyTorch gate order i,f,g,o) */
