@@ -11,6 +11,7 @@ noise either from a counter-based Philox stream keyed by ``(seed, global image i
 token)`` -- results do not depend on batch composition or rank layout -- or, for RNG-replay parity
 tests, from caller-supplied tensors (``noise_source``).
 """
+import dataclasses
 import math
 import numbers
 import os
@@ -249,6 +250,53 @@ def compile_bad_words(ids, num_tokens=None, device="cuda"):
             _BAD_WORDS_CACHE.pop(next(iter(_BAD_WORDS_CACHE)))
         _BAD_WORDS_CACHE[key] = bw
     return bw
+
+
+@dataclasses.dataclass(frozen=True, eq=False)
+class DecodeSettings:
+    """The validated decode settings of one call -- ``return_beams``, ``return_attention``, ``top_p``, ``no_repeat_ngram_size``,
+    ``repetition_penalty``, ``min_len``, ``bad_words_ids`` -- as the ``check_*`` functions return them (``bad_words_ids``: ``None``, a
+    tuple of tuples, or a ``BadWords``), and ``num_tokens``, the vocabulary the list was checked against.  Built by ``from_kw``
+    only.  Immutable; equal and hashed by the settings, the list by its ids whether compiled or not."""
+    return_beams: bool = False
+    return_attention: bool = False
+    top_p: float = 1.0
+    no_repeat_ngram_size: int = 0
+    repetition_penalty: float = 1.0
+    min_len: int = 0
+    bad_words_ids: object = None
+    num_tokens: object = None
+
+    @classmethod
+    def from_kw(cls, kw, max_len, num_tokens=None, model=None):
+        """Reads the seven settings out of the keyword dictionary ``kw`` (which keeps them) and checks them in this order, so a call
+        with two bad values raises for the earlier one; ``model``: see ``check_return_attention``."""
+        return_beams = check_return_beams(kw.get("return_beams", False))
+        return_attention = check_return_attention(kw.get("return_attention", False), model)
+        top_p = check_top_p(kw.get("top_p", 1.0))
+        ngram, penalty = check_repeat(kw.get("no_repeat_ngram_size", 0), kw.get("repetition_penalty", 1.0), max_len)
+        min_len, bad_words = check_constraints(kw.get("min_len", 0), kw.get("bad_words_ids"), max_len, num_tokens)
+        return cls(return_beams, return_attention, top_p, ngram, penalty, min_len, bad_words, num_tokens)
+
+    def _key(self):
+        bw = self.bad_words_ids
+        return (self.return_beams, self.return_attention, self.top_p, self.no_repeat_ngram_size, self.repetition_penalty, self.min_len,
+                bw.ids if isinstance(bw, BadWords) else bw)
+
+    def __eq__(self, other):
+        return isinstance(other, DecodeSettings) and self._key() == other._key()
+
+    def __hash__(self):
+        return hash(self._key())
+
+    def compiled(self, device):
+        """The record with its phrase list uploaded to ``device`` (``compile_bad_words``: once per list, not inside a capture)."""
+        return dataclasses.replace(self, bad_words_ids=compile_bad_words(self.bad_words_ids, self.num_tokens, device))
+
+    def new_helper(self, **engine_args):
+        """The ``BeamSearchHelper`` of one session with every setting applied; ``engine_args``: the constructor's other arguments."""
+        return BeamSearchHelper(top_p=self.top_p, no_repeat_ngram_size=self.no_repeat_ngram_size, repetition_penalty=self.repetition_penalty,
+                                **engine_args).set_constraints(self.min_len, self.bad_words_ids)
 
 
 class BeamOverflow(RuntimeError):
@@ -502,36 +550,8 @@ class BeamSearchHelper:
         """One beam step of a prompted batch from ``logits [n_img*beam, V]`` at absolute position ``step_index``: per image forced
         (``step_index < first_pos``: nothing happens), first (``==``: ``step(first=True)`` from the image's base row) or normal
         (``>``: ``step(first=False)``) -- ``dh_beam_row_sample*_prompted`` + ``dh_beam_select_prompted``.  Philox noise only."""
-        rows, v = logits.shape
-        assert rows == self.n_img * self.beam_size and self.noise_source is None
-        use_groups = group_max is not None and not self.exact and self.top_k <= hip.n_groups(v)
-        if self._history_edits:
-            hip.beam_history_logits(logits, v, self.tokens, 1, write_pos, rows, self.beam_size, self.no_repeat_ngram_size,
-                                    self.repetition_penalty, group_max=group_max if use_groups else None, first_pos=self.first_pos)
-        self._constrain(logits, v, 1, write_pos, rows, self.beam_size, group_max if use_groups else None, self.first_pos)
-        if self.top_p < 1.0:
-            hip.beam_row_sample_nucleus(logits, v, rows, self.beam_size, self.beam_size, self.top_k, self.top_p, self.temperature,
-                                        self.unk_index, None, self.seed, self.img0, step_index, self.pick_idx, self.pick_val, self.err,
-                                        seed_ptr=self.seed_tensor, exact=self.exact, group_max=group_max if use_groups else None,
-                                        first_pos=self.first_pos)
-        else:
-            hip.beam_row_sample_prompted(logits, v, rows, self.beam_size, self.top_k, self.temperature, self.unk_index, None, self.seed,
-                                         self.img0, step_index, self.first_pos, self.pick_idx, self.pick_val, self.err,
-                                         seed_ptr=self.seed_tensor, exact=self.exact, group_max=group_max if use_groups else None)
-        hip.beam_select_prompted(self.pick_idx, self.pick_val, self.tokens, self.vals, self._ended, self.src, self.parent,
-                                 self.hparent, self.done, self.end_step, self.n_img, self.beam_size, self.first_pos,
-                                 first_sets_ended, write_pos, t, step_index, self.temperature, self.eos_index, None, self.seed,
-                                 self.img0, seed_ptr=self.seed_tensor)
-
-    def _constrain(self, logits, v, tok_row_mult, pos, rows, rpi, group_max, first_pos=None):
-        """min_len / bad_words_ids: the bans in front of the row draw, behind the history edits (both store ``-inf`` or map it to
-        itself, so the order does not show).  A launch only when there is something to ban at this position."""
-        bw = self.bad_words
-        if bw is None and pos >= self.min_len:
-            return
-        hip.beam_constrain_logits(logits, v, self.tokens, tok_row_mult, pos, rows, rpi, self.eos_index, self.min_len,
-                                  None if bw is None else bw.words, None if bw is None else bw.offsets, 0 if bw is None else len(bw),
-                                  group_max=group_max, first_pos=first_pos)
+        assert self.noise_source is None
+        self._draw_and_select(logits, False, write_pos, t, step_index, first_sets_ended, group_max, prompted=True)
 
     def _noise(self, kind, step, shape, ld=None):
         if self.noise_source is None:
@@ -549,51 +569,68 @@ class BeamSearchHelper:
     def step(self, logits, first, write_pos, t, step_index, first_sets_ended=False, group_max=None):
         """One beam step from ``logits`` ([n_img, V] if ``first`` else [n_img*beam, V]):
         beam.py:55-108 + the caller-side candidate draw (rnn_models.py:116-128, transformers.py:557-569)."""
-        rows = logits.shape[0]
-        rpi = 1 if first else self.beam_size
+        self._draw_and_select(logits, first, write_pos, t, step_index, first_sets_ended, group_max)
+
+    def _draw_and_select(self, logits, first, write_pos, t, step_index, first_sets_ended, group_max, prompted=False):
+        """``step`` and ``step_prompted``: the history edits, the bans, the row draw and the select, in that order."""
+        rows, v = logits.shape
+        b = self.beam_size
+        rpi = 1 if first else b
         assert rows == self.n_img * rpi
-        v = logits.shape[1]
-        # the general sampler reads the whole row; otherwise k group maxima bound the k-th logit.  Decided ONCE: the history pass
-        # repairs the maxima exactly when the sampler below reads them
-        use_groups = group_max is not None and not self.exact and self.top_k <= hip.n_groups(v)
+        mult = b if first else 1          # the token table's row of logits row r: a first step's compact rows sit at img * beam
+        first_pos = self.first_pos if prompted else None
+        # the general sampler reads the whole row; otherwise k group maxima bound the k-th logit.  Decided ONCE: the history pass and
+        # the bans repair the maxima exactly when the sampler below reads them
+        gm = group_max if (group_max is not None and not self.exact and self.top_k <= hip.n_groups(v)) else None
         if self._history_edits:           # no_repeat_ngram_size / repetition_penalty: the row's own history edits its logits first
-            hip.beam_history_logits(logits, v, self.tokens, self.beam_size if first else 1, write_pos, rows, rpi,
-                                    self.no_repeat_ngram_size, self.repetition_penalty,
-                                    group_max=group_max if use_groups else None)
-        self._constrain(logits, v, self.beam_size if first else 1, write_pos, rows, rpi, group_max if use_groups else None)
+            hip.beam_history_logits(logits, v, self.tokens, mult, write_pos, rows, rpi, self.no_repeat_ngram_size,
+                                    self.repetition_penalty, group_max=gm, first_pos=first_pos)
+        # min_len / bad_words_ids: the bans behind the history edits (both store ``-inf`` or map it to itself, so the order does not
+        # show).  A launch only when there is something to ban at this position
+        bw = self.bad_words
+        if bw is not None or write_pos < self.min_len:
+            hip.beam_constrain_logits(logits, v, self.tokens, mult, write_pos, rows, rpi, self.eos_index, self.min_len,
+                                      None if bw is None else bw.words, None if bw is None else bw.offsets, 0 if bw is None else len(bw),
+                                      group_max=gm, first_pos=first_pos)
+        noise = self._noise("row", step_index, (rows, v), logits.stride(0))       # (None in a prompted session: Philox only)
+        draw = (self.seed, self.img0, step_index, self.pick_idx, self.pick_val, self.err)
         if self.top_p < 1.0:              # the nucleus of the survivors: one entry point for the three routes below
-            hip.beam_row_sample_nucleus(logits, v, rows, rpi, self.beam_size, self.top_k, self.top_p, self.temperature, self.unk_index,
-                                        self._noise("row", step_index, (rows, v), logits.stride(0)), self.seed, self.img0, step_index,
-                                        self.pick_idx, self.pick_val, self.err, seed_ptr=self.seed_tensor, exact=self.exact,
-                                        group_max=group_max if use_groups else None)
-        elif use_groups:
+            hip.beam_row_sample_nucleus(logits, v, rows, rpi, b, self.top_k, self.top_p, self.temperature, self.unk_index, noise, *draw,
+                                        seed_ptr=self.seed_tensor, exact=self.exact, group_max=gm, first_pos=first_pos)
+        elif prompted:
+            hip.beam_row_sample_prompted(logits, v, rows, b, self.top_k, self.temperature, self.unk_index, noise, self.seed, self.img0,
+                                         step_index, first_pos, self.pick_idx, self.pick_val, self.err, seed_ptr=self.seed_tensor,
+                                         exact=self.exact, group_max=gm)
+        elif gm is not None:
             # bf16 path: the vocabulary GEMM left per-row maxima of every 64-column group (dh_vocab_logits)
-            hip.beam_row_sample_groups(logits, v, group_max, rows, rpi, self.beam_size, self.top_k, self.temperature,
-                                       self.unk_index, self._noise("row", step_index, (rows, v), logits.stride(0)), self.seed, self.img0,
-                                       step_index, self.pick_idx, self.pick_val, self.err, seed_ptr=self.seed_tensor)
+            hip.beam_row_sample_groups(logits, v, gm, rows, rpi, b, self.top_k, self.temperature, self.unk_index, noise, *draw,
+                                       seed_ptr=self.seed_tensor)
         else:
-            hip.beam_row_sample(logits, v, rows, rpi, self.beam_size, self.top_k, self.temperature, self.unk_index,
-                                self._noise("row", step_index, (rows, v), logits.stride(0)), self.seed, self.img0, step_index,
-                                self.pick_idx, self.pick_val, self.err, seed_ptr=self.seed_tensor, exact=self.exact)
-        noise = None if first else self._noise("cand", step_index, (self.n_img, self.beam_size ** 2))
-        hip.beam_select(self.pick_idx, self.pick_val, self.tokens, self.vals, self._ended, self.src,
-                        self.parent, self.hparent, self.done, self.end_step, self.n_img, self.beam_size, first,
-                        first_sets_ended, write_pos, t, step_index, self.temperature, self.eos_index, noise,
-                        self.seed, self.img0, seed_ptr=self.seed_tensor)
+            hip.beam_row_sample(logits, v, rows, rpi, b, self.top_k, self.temperature, self.unk_index, noise, *draw,
+                                seed_ptr=self.seed_tensor, exact=self.exact)
+        state = (self.pick_idx, self.pick_val, self.tokens, self.vals, self._ended, self.src, self.parent, self.hparent, self.done,
+                 self.end_step, self.n_img, b)
+        if prompted:
+            hip.beam_select_prompted(*state, first_pos, first_sets_ended, write_pos, t, step_index, self.temperature, self.eos_index,
+                                     None, self.seed, self.img0, seed_ptr=self.seed_tensor)
+        else:
+            noise = None if first else self._noise("cand", step_index, (self.n_img, b ** 2))
+            hip.beam_select(*state, first, first_sets_ended, write_pos, t, step_index, self.temperature, self.eos_index, noise,
+                            self.seed, self.img0, seed_ptr=self.seed_tensor)
 
     def finalize(self, len_bias_done, full_len, pad_index=0, defer_check=False, first_beam=False, beams=False, pos=0, attn_w=None):
-        """Final draw among the beams and output copy; returns (tokens int64 [n_img, max_len], lengths).
-        ``defer_check``: skip the host read of the device error word (hipGraph capture) -- the caller checks
-        ``self.err`` after replay.  ``first_beam``: no draw, beam 0 -- what the reference's final
+        """Final draw among the beams and output copy; returns a ``SessionResult`` whose ``captions`` are ``(tokens int64 [n_img,
+        max_len], lengths)``.  ``defer_check``: skip the host read of the device error word (hipGraph capture) -- the result carries
+        ``self.err`` for the caller to check after replay.  ``first_beam``: no draw, beam 0 -- what the reference's final
         ``sample_k_indices(sample_val, k=1)`` degenerates to when ``sample_val`` is still the ``[beam, 1]`` column of the
         first step (rnn_models.py:93, 140-141: no decode step ran because the prefix already fills ``max_len - 1``).
-        ``beams=True``: one launch of ``dh_beam_finalize_beams`` instead -- the same draw, and every beam kept: returns a
-        ``BeamCaptions`` (then the error word with ``defer_check``).  ``pos``: the first generated column of a dense session (the
+        ``beams=True``: one launch of ``dh_beam_finalize_beams`` instead -- the same draw, and every beam kept: the ``captions`` are a
+        ``BeamCaptions``.  ``pos``: the first generated column of a dense session (the
         prefix length), from where a beam's own ``<eos>`` is looked for; a prompted session's comes from ``self.first_pos``.
         ``attn_w`` (``return_attention``; fp32 ``[n_pos, rows, S]``, slab ``c`` = the maps position ``c`` wrote at its logical rows):
         always the ``beams`` launch, and one launch of ``dh_beam_gather_attention`` behind it leaves every kept beam's maps -- read
-        through ``self.src``, for the columns below the beam's own length, zero elsewhere -- in ``self.attention`` fp32
-        ``[n_img, beam, max_len, S]``; the return value is that of ``beams=True``."""
+        through ``self.src``, for the columns below the beam's own length, zero elsewhere -- in the result's ``attention``, fp32
+        ``[n_img, beam, max_len, S]``; its ``captions`` are those of ``beams=True``."""
         if first_beam:                 # the kernel's race p / noise with an infinite handicap on every beam but the first
             noise = torch.full((self.n_img, self.beam_size), float("inf"), dtype=torch.float32, device=self.device)
             noise[:, 0] = 1.0
@@ -608,23 +645,23 @@ class BeamSearchHelper:
             hip.beam_finalize_beams(self.tokens, self.vals, self.done, self.end_step, out, o_len, o_score, o_idx, o_drawn, o_row, n, b,
                                     len_bias_done, full_len, pad_index, self.eos_index, pos, self.first_pos,
                                     self.temperature, noise, self.seed, self.img0, seed_ptr=self.seed_tensor)
+            attention = None
             if attn_w is not None:
-                self.attention = torch.empty((n, b, self.max_len, attn_w.shape[2]), dtype=torch.float32, device=dev)
-                hip.beam_gather_attention(attn_w, self.src, o_idx, o_len, self.attention)
-            res = BeamCaptions(out.long(), o_len.long(), o_score, o_idx.long(), o_drawn.long(), o_row.long())
-            if defer_check:
-                return res, self.err
-            self.check()
-            return res
-        out = torch.empty((self.n_img, self.max_len), dtype=torch.int32, device=self.device)
-        out_len = torch.empty((self.n_img,), dtype=torch.int32, device=self.device)
-        hip.beam_finalize(self.tokens, self.vals, self.done, self.end_step, out, out_len, self.n_img, self.beam_size,
-                          len_bias_done, full_len, pad_index, self.temperature, noise, self.seed, self.img0,
-                          seed_ptr=self.seed_tensor)
+                attention = torch.empty((n, b, self.max_len, attn_w.shape[2]), dtype=torch.float32, device=dev)
+                hip.beam_gather_attention(attn_w, self.src, o_idx, o_len, attention)
+            captions = BeamCaptions(out.long(), o_len.long(), o_score, o_idx.long(), o_drawn.long(), o_row.long())
+        else:
+            attention = None
+            out = torch.empty((self.n_img, self.max_len), dtype=torch.int32, device=self.device)
+            out_len = torch.empty((self.n_img,), dtype=torch.int32, device=self.device)
+            hip.beam_finalize(self.tokens, self.vals, self.done, self.end_step, out, out_len, self.n_img, self.beam_size,
+                              len_bias_done, full_len, pad_index, self.temperature, noise, self.seed, self.img0,
+                              seed_ptr=self.seed_tensor)
+            captions = (out.long(), out_len.long())
         if defer_check:
-            return out.long(), out_len.long(), self.err
+            return SessionResult(captions, self.err, attention)
         self.check()
-        return out.long(), out_len.long()
+        return SessionResult(captions, None, attention)
 
     def check(self):
         """Raises like the reference does when every logit of a row was filtered (beam.py:46)."""
@@ -884,12 +921,105 @@ def resolve_seed(seed, noise_source=None):
     return int(seed)
 
 
+class SessionResult(NamedTuple):
+    """What a decode session returns (``BeamSearchHelper.finalize``): ``captions`` -- the ``(tokens, lengths)`` pair or a
+    ``BeamCaptions`` --, ``err`` -- the device error word of a ``defer_check`` session, else ``None`` --, and ``attention`` -- the kept
+    beams' maps fp32 ``[n, B, T, S]`` of a ``return_attention`` session (whose ``captions`` are a ``BeamCaptions``), else ``None``."""
+    captions: object
+    err: object = None
+    attention: object = None
+
+    def record_stream(self, stream):
+        for t in (*self.captions, self.err, self.attention):
+            if t is not None:
+                t.record_stream(stream)
+
+    @staticmethod
+    def cat(parts):
+        """The images of several sessions, in order; the error word is the OR of theirs."""
+        first = parts[0]
+        caps = [p.captions for p in parts]
+        caps = BeamCaptions.cat(caps) if isinstance(first.captions, BeamCaptions) else tuple(torch.cat(ts, 0) for ts in zip(*caps))
+        err = None
+        if first.err is not None:
+            err = first.err.clone()
+            for p in parts[1:]:
+                err |= p.err
+        return SessionResult(caps, err, None if first.attention is None else torch.cat([p.attention for p in parts], 0))
+
+    def public(self, return_beams=False):
+        """What ``generate_batch`` returns: the pair or the ``BeamCaptions``; behind it ``attention`` -- ``[N, B, T, S]`` for
+        ``return_beams``, else the drawn slot's maps ``[N, T, S]`` behind ``best()``, the plain pair bit for bit --; behind that the
+        error word of a ``defer_check`` call.  One element alone is returned as it is."""
+        caps, att = self.captions, self.attention
+        if att is not None and not return_beams:
+            caps, att = caps.best(), att[torch.arange(att.shape[0], device=att.device), caps.drawn]
+        out = (caps,) if isinstance(caps, BeamCaptions) else tuple(caps)
+        out += tuple(t for t in (att, self.err) if t is not None)
+        return out[0] if len(out) == 1 else out
+
+
+class DecodeSession:
+    """What every decode session of both decoders sets up around its position loop: the ``helper`` (``settings.new_helper``), the
+    fp32 ``logits [rows, V]`` and -- where the classifier fills them (16-bit paths, f32x planes) -- the 64-column ``group_max``, both
+    padded to whole 256-column chunks (vocab_wreg; rows are 16-byte aligned for vector stores); the teacher-forced beginning
+    (``set_prefix`` / ``set_prompts``: ``pos`` the dense prefix length, ``pmin`` / ``pmax`` the shortest and longest prompt); and the
+    ``early_stop_every`` test.  ``plan=None``: no buffers (the re-forward decoder's logits are the classifier's own output)."""
+
+    def __init__(self, helper, plan=None, num_tokens=0, early_stop_every=0, pad_index=0):
+        self.helper, self.early_stop_every, self.pad_index = helper, early_stop_every, pad_index
+        self.pos = self.pmin = self.pmax = 0
+        self.logits = self.group_max = None
+        if pad_index != 0:
+            helper.tokens.fill_(pad_index)
+        if plan is not None:
+            rows, chunks, dev = helper.n_img * helper.beam_size, (num_tokens + 255) // 256, helper.device
+            self.logits = torch.empty((rows, 256 * chunks), device=dev)[:, :num_tokens]
+            if plan["dtype"] in hip.HALF_DTYPES or plan.get("f32_planes"):
+                self.group_max = torch.empty((rows, 4 * chunks), device=dev)[:, :hip.n_groups(num_tokens)]
+
+    def set_prefix(self, caption, lo, hi):
+        """The dense prefix ``caption[lo:hi]`` (``None``: none) -> ``pos``, the first generated column."""
+        if caption is not None:
+            self.pos = self.pmin = self.pmax = caption.shape[1]
+            self.helper.set_prefix(caption[lo:hi])
+        return self.pos
+
+    def set_prompts(self, prompts, lo, hi):
+        """``prompts``: ``prompt_session_inputs``' triple.  Without host lengths (nothing may be read back) every position the
+        prompts span counts as mixed."""
+        cap, first_pos, host = prompts
+        self.pmin, self.pmax = (min(host[lo:hi]), max(host[lo:hi])) if host is not None else (0, cap.shape[1])
+        self.helper.set_prompts(cap[lo:hi], first_pos[lo:hi], self.pad_index)
+
+    def all_done(self, i):
+        """The reference's ``all_ended()`` break, tested every ``early_stop_every`` positions behind the last forced one (one host
+        sync per test): finished images are frozen by ``dh_beam_select``, so nothing is left to do."""
+        every = self.early_stop_every
+        return bool(every and i > self.pmax and (i - self.pmax) % every == 0 and bool(self.helper.done.all()))
+
+
+def decode_with_overflow_retry(run, exact, rng_state0=None):
+    """``run(exact)``; flat logits -- more ties at a row's top-k threshold than the fast samplers hold (``BeamOverflow``) -- once more
+    with ``exact=True``: every row draw through the general sampler (same seed: same captions where nothing overflowed), torch's
+    default generator put back to ``rng_state0`` first where one is given.  With ``exact`` already on the overflow is the caller's."""
+    try:
+        return run(bool(exact))
+    except BeamOverflow:
+        if exact:
+            raise
+        warn_overflow_retry()
+        if rng_state0 is not None:
+            torch.set_rng_state(rng_state0)
+        return run(True)
+
+
 _STREAMS = {}
 
 
 def run_interleaved(make_session, n_img, n_streams):
     """Runs ``make_session(lo, hi)`` -- a generator that decodes images ``[lo, hi)`` and yields after every
-    position, returning ``(tokens, lengths)`` -- either once, or as ``n_streams`` image sub-batches advanced
+    position, returning a ``SessionResult`` -- either once, or as ``n_streams`` image sub-batches advanced
     round-robin on separate HIP streams.  Decode positions are chains of small, latency-bound kernels
     (a 640-row GEMM fills a fraction of the 256 CUs); two independent chains in flight fill the gaps.
     Captions are unchanged: every image's noise is keyed by its global index (``img0 + lo``)."""
@@ -926,27 +1056,6 @@ def run_interleaved(make_session, n_img, n_streams):
                     alive.discard(i)
     for st in pool[:n_streams]:
         main.wait_stream(st)
-    if isinstance(results[0], BeamCaptions) or isinstance(results[0][0], BeamCaptions):
-        # return_beams sessions: a BeamCaptions, or (BeamCaptions, error word) with defer_check -- every field concatenated
-        deferred = not isinstance(results[0], BeamCaptions)
-        parts = [r[0] if deferred else r for r in results]
-        for part in parts:
-            for t in part:
-                t.record_stream(main)
-        out = BeamCaptions.cat(parts)
-        if not deferred:
-            return out
-        err = results[0][1].clone()
-        for r in results[1:]:
-            err |= r[1]
-        return out, err
     for r in results:
-        for t in r:
-            t.record_stream(main)
-    out = (torch.cat([r[0] for r in results], 0), torch.cat([r[1] for r in results], 0))
-    if len(results[0]) > 2:               # defer_check sessions also return their device error word: OR of the sub-batches' words
-        err = results[0][2].clone()
-        for r in results[1:]:
-            err |= r[2]
-        out += (err,)
-    return out
+        r.record_stream(main)
+    return SessionResult.cat(results)

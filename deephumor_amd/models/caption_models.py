@@ -9,9 +9,12 @@ config 5).
 import torch
 from torch import nn
 
+from .. import hip
+from ._f32x_guard import f32x_guarded
+from .beam import BeamCaptions, BeamOverflow, BeamSearchHelper, DecodeSettings, check_ids, check_prompts, prompts_need_philox, resolve_seed, warn_overflow_retry
 from .encoders import ImageEncoder, ImageLabelEncoder, SpatialImageLabelEncoder, _Planned
 from .rnn_models import LSTMDecoder
-from .transformers import SelfAttentionTransformerDecoder, TransformerDecoder
+from .transformers import SelfAttentionTransformerDecoder, TransformerDecoder, _IncrementalDecoder
 
 
 class _CaptioningBase(nn.Module):
@@ -21,7 +24,6 @@ class _CaptioningBase(nn.Module):
         """Every model's ``forward`` / ``generate_batch`` is the OUTERMOST range-guarded call of the split-operand fp32 path
         (``_f32x_guard.f32x_guarded``: one host read of the stream's overflow word per call, with option ``f32_split`` only)."""
         super().__init_subclass__(**kw)
-        from ._f32x_guard import f32x_guarded
         for name in ("forward", "generate_batch"):
             if name in cls.__dict__:
                 setattr(cls, name, f32x_guarded(cls.__dict__[name]))
@@ -38,18 +40,7 @@ class _CaptioningBase(nn.Module):
         model.load_state_dict(ckpt['model'])
         return model
 
-    @staticmethod
-    def _one(res):
-        """``generate``'s result from ``generate_batch``'s for one image: the 1-D caption, or the ``BeamCaptions`` as it is; with
-        ``return_attention=True`` the pair ``(caption, attention [len, S])``, or ``(BeamCaptions, attention [1, B, T, S])`` as it is."""
-        from .beam import BeamCaptions
-        if isinstance(res, BeamCaptions) or isinstance(res[0], BeamCaptions):
-            return res
-        if len(res) == 3:
-            toks, lens, att = res
-            return toks[0, :int(lens[0])].squeeze(), att[0, :int(lens[0])]
-        toks, lens = res
-        return toks[0, :int(lens[0])].squeeze()
+    _one = staticmethod(_IncrementalDecoder._one)       # ``generate``'s result from ``generate_batch``'s for one image
 
     # ``generate_batch`` = ``decode(encode(...))``.  The two halves are exposed separately so that a serving loop can run
     # the encoder of batch i+1 on one HIP stream while batch i decodes on another (deephumor_amd/pipeline.py): the decode
@@ -62,11 +53,7 @@ class _CaptioningBase(nn.Module):
                caption_lengths=None, **kw):
         """Batched beam-search decoding of ``encode``'s output -> ``(tokens [N, max_len], lengths [N])``, or with
         ``return_beams=True`` every beam of every image as a ``beam.BeamCaptions`` (``LSTMDecoder.generate_batch``).
-        ``top_p`` (in ``kw``, a number in ``(0, 1]``): nucleus filtering beside ``top_k`` (``LSTMDecoder.generate_batch``).
-        ``no_repeat_ngram_size`` (int ``>= 0``) / ``repetition_penalty`` (finite ``> 0``), in ``kw``: no row completes an n-gram it
-        already holds / every token of a row's history is damped CTRL-style, in front of every row draw (``LSTMDecoder.generate_batch``).
-        ``min_len`` (int, ``0 <= min_len < max_len``) / ``bad_words_ids`` (``None``, a nesting of token ids, or a ``beam.BadWords``), in
-        ``kw``: no ``<eos>`` at a token position below ``min_len`` / no row completes a banned phrase (``LSTMDecoder.generate_batch``).
+        ``top_p``, ``no_repeat_ngram_size`` / ``repetition_penalty``, ``min_len`` / ``bad_words_ids`` (in ``kw``): see there.
         ``caption_lengths`` (keyword only, int64 / int32 ``[N]``): a prompt of its own length per image -- row ``i`` is
         teacher-forced with ``caption[i, :caption_lengths[i]]`` (0: none; the rest of the row is ignored) and equals the dense
         single-image call with that prompt and ``img0 + i`` (``LSTMDecoder.generate_batch``).
@@ -88,17 +75,10 @@ class _CaptioningBase(nn.Module):
     def _check_prompts(self, caption, caption_lengths, max_len, kw):
         """A prompted batch is validated BEFORE the encoder runs (``beam.check_prompts`` / ``prompt_session_inputs``: shapes, ranges,
         the options it cannot be combined with); ``defer_check`` callers (graph capture, the pipeline) with device-resident lengths
-        have done so themselves.  So is the type of ``return_beams`` (``beam.check_return_beams``) and the range of ``top_p`` (``beam.check_top_p``), for every batch."""
-        from .beam import check_constraints, check_prompts, check_repeat, check_return_attention, check_return_beams, check_top_p, prompts_need_philox
-        check_return_beams(kw.get("return_beams", False))
-        if "return_attention" in kw:
-            # (a plain bool; on, it needs a decoder with encoder attention on the KV-cached engine: beam.check_return_attention.  Off, it
-            # is the call without the keyword -- also for the kinds whose decoders do not know it)
-            if not check_return_attention(kw["return_attention"], self) and not getattr(self.decoder, "_cross", False):
-                del kw["return_attention"]
-        check_top_p(kw.get("top_p", 1.0))
-        check_repeat(kw.get("no_repeat_ngram_size", 0), kw.get("repetition_penalty", 1.0), max_len)      # (beam.check_repeat: likewise)
-        check_constraints(kw.get("min_len", 0), kw.get("bad_words_ids"), max_len, self._hp["num_tokens"])   # (beam.check_constraints: likewise)
+        have done so themselves.  So are the decode settings in ``kw`` (``beam.DecodeSettings``), for every batch."""
+        settings = DecodeSettings.from_kw(kw, max_len, self._hp["num_tokens"], self)
+        if not settings.return_attention and not getattr(self.decoder, "_cross", False):
+            kw.pop("return_attention", None)      # (off, it is the call without the keyword -- also for the kinds whose decoders do not know it)
         if caption_lengths is None:
             return None
         if getattr(self.decoder, "pad_index", 0) == 1:
@@ -114,7 +94,6 @@ class _CaptioningBase(nn.Module):
         """Identity of everything a captured graph holds raw pointers to or derives constants from: storage pointer and
         in-place version counter of every parameter and buffer of the model."""
         ts = list(self.parameters()) + list(self.buffers())
-        from .. import hip
         return tuple(t.data_ptr() for t in ts), tuple(t._version for t in ts), hip.options_epoch
 
     MAX_GRAPHS = 4      # captured graphs kept per model (one per (input shapes, decode settings))
@@ -140,26 +119,19 @@ class _CaptioningBase(nn.Module):
         function of the lengths enters the graph cache key -- only the fact that lengths were passed, next to ``caption``'s shape:
         the captured chain treats every position ``0 .. min(P, max_len - 2)`` as mixed (all ``N * beam`` rows, the prompted beam
         step), so one graph serves every set of lengths of that shape and returns what eager returns for them."""
-        from .beam import BeamCaptions, BeamOverflow, BeamSearchHelper, check_constraints, check_repeat, check_return_beams, compile_bad_words, check_top_p, resolve_seed, warn_overflow_retry
-        # ``return_beams=True`` is part of the cache key like every decode setting (``kw``): its graph ends in dh_beam_finalize_beams and
-        # lives beside the plain one of the same shapes; a replay returns clones of every field
-        check_return_beams(kw.get("return_beams", False))
-        # ``return_attention=True`` likewise: its graph holds one dh_attn_cross_weights node per position and the gather behind the
-        # final draw, lives beside the plain one of the same shapes, and a replay returns a clone of the maps too
-        from .beam import check_return_attention
-        if not check_return_attention(kw.get("return_attention", False), self):
+        # every decode setting rides in ``kw`` and so is part of the cache key below: the graph of ``return_beams=True`` (it ends in
+        # dh_beam_finalize_beams), of ``return_attention=True`` (one dh_attn_cross_weights node per position and the gather behind the
+        # final draw), of ``top_p < 1`` (nucleus row draws), of the repeat controls and of ``min_len`` / ``bad_words_ids`` (one
+        # dh_beam_history_logits / dh_beam_constrain_logits node per position that edits something; the position is a launch constant)
+        # each lives beside the plain one of the same shapes, and a replay returns clones of every field
+        settings = DecodeSettings.from_kw(kw, kw.get("max_len", 25), self._hp["num_tokens"], self)
+        if not settings.return_attention:
             kw.pop("return_attention", None)          # (False is the call without the keyword: the plain graph, not a second one)
-        # ``top_p`` rides in ``kw`` too, so it is in the key below: a top_p = 0.8 graph (nucleus row draws) lives beside the plain one
-        check_top_p(kw.get("top_p", 1.0))
-        # so do ``no_repeat_ngram_size`` / ``repetition_penalty``: their graph holds one dh_beam_history_logits node per position (the
-        # position is a launch constant) and lives beside the plain one
-        check_repeat(kw.get("no_repeat_ngram_size", 0), kw.get("repetition_penalty", 1.0), kw.get("max_len", 25))
-        # and ``min_len`` / ``bad_words_ids`` (one dh_beam_constrain_logits node per position that bans something).  The list is
-        # compiled HERE, in front of any capture -- no host-to-device copy happens inside one -- and the ``BadWords`` replaces the raw
-        # nesting in ``kw``: it is hashable, so it is in the key below, and the captured closure keeps its two tensors alive
-        _, bad_words = check_constraints(kw.get("min_len", 0), kw.get("bad_words_ids"), kw.get("max_len", 25), self._hp["num_tokens"])
+        # The list is compiled HERE, in front of any capture -- no host-to-device copy happens inside one -- and the ``BadWords``
+        # replaces the raw nesting in ``kw``: it is hashable, so it is in the key below, and the captured closure keeps its two
+        # tensors alive
         if "bad_words_ids" in kw:
-            kw["bad_words_ids"] = compile_bad_words(bad_words, self._hp["num_tokens"], inputs[0].device)
+            kw["bad_words_ids"] = settings.compiled(inputs[0].device).bad_words_ids
         if kw.get("rng") == "torch":      # host-generated noise (parity mode): nothing to replay
             return self.generate_batch(*inputs, caption=caption, seed=seed, caption_lengths=caption_lengths, **kw)
         if caption_lengths is not None:
@@ -169,7 +141,6 @@ class _CaptioningBase(nn.Module):
         seed = resolve_seed(seed)
         # ids are looked up without bounds tests and nothing can be read back inside a capture: the caption prefix and integer inputs
         # (labels) are range-checked here, in front of the capture / replay (beam.check_ids: nn.Embedding's IndexError)
-        from .beam import check_ids
         dec = getattr(self, "decoder", None)
         emb = getattr(dec, "embedding", None) or getattr(dec, "tok_embedding", None)
         if emb is not None and caption_lengths is None:       # (a prompted batch: _check_prompts above looked at the used ids)
@@ -233,7 +204,6 @@ class _CaptioningBase(nn.Module):
             state[7].copy_(caption_lengths)
         seed_t.fill_(int(seed))
         graph.replay()
-        from .. import hip
         if next(self.parameters()).dtype == torch.float32 and hip.option("f32_split") and hip.f32x_take_overflow(inputs[0].device):
             # an activation left the fp16 range of the split-operand path inside the replayed graph: this batch eagerly (the guarded
             # generate_batch repeats itself on the exact-fp32 kernels)

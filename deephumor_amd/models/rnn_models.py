@@ -15,7 +15,7 @@ from torch import nn
 
 from .. import hip
 from ._f32x_guard import f32x_guarded
-from .beam import BeamCaptions, BeamOverflow, BeamSearchHelper, call_logits_hook, check_return_beams, check_top_p, check_repeat, check_constraints, compile_bad_words, check_ids, check_lengths, classifier_must_be_finite, make_noise_source, prompt_session_inputs, resolve_seed, run_interleaved, warn_overflow_retry
+from .beam import BeamCaptions, DecodeSession, DecodeSettings, call_logits_hook, check_ids, check_lengths, classifier_must_be_finite, decode_with_overflow_retry, make_noise_source, prompt_session_inputs, resolve_seed, run_interleaved
 from .encoders import _Planned
 
 
@@ -248,14 +248,13 @@ class LSTMDecoder(_Planned, nn.Module):
                         defer_check=False, early_stop_every=0, exact=False, rng=None, *, caption_lengths=None, return_beams=False, top_p=1.0,
                         no_repeat_ngram_size=0, repetition_penalty=1.0, min_len=0, bad_words_ids=None):
         """``generate_batch`` with its keyword-only tail written out."""
-        check_return_beams(return_beams)
-        top_p = check_top_p(top_p)
-        no_repeat_ngram_size, repetition_penalty = check_repeat(no_repeat_ngram_size, repetition_penalty, max_len)
-        min_len, bad_words_ids = check_constraints(min_len, bad_words_ids, max_len, self.num_tokens)
+        settings = DecodeSettings.from_kw(dict(return_beams=return_beams, top_p=top_p, no_repeat_ngram_size=no_repeat_ngram_size,
+                                               repetition_penalty=repetition_penalty, min_len=min_len, bad_words_ids=bad_words_ids),
+                                          max_len, self.num_tokens)
         self._check_mode()
         plan = self._get_plan()
         classifier_must_be_finite(plan)
-        bad_words_ids = compile_bad_words(bad_words_ids, self.num_tokens, image_emb.device)     # uploaded once (a BadWords: as it is)
+        settings = settings.compiled(image_emb.device)                 # the phrase list uploaded once (a BadWords: as it is)
         prompts = prompt_session_inputs(caption, caption_lengths, max_len, self.embedding.num_embeddings, image_emb.device, rng,
                                         noise_source, no_host_read=defer_check)
         if prompts is None:
@@ -267,7 +266,12 @@ class LSTMDecoder(_Planned, nn.Module):
         rng_state0 = torch.get_rng_state() if (rng == "torch" and rng_seed is None) else None
         image_emb = image_emb.reshape(image_emb.shape[0], -1).to(plan["dtype"]).contiguous()
 
-        def prompted_session(lo, hi):
+        def new_helper(lo, hi, exact, **kw):
+            return settings.new_helper(temperature=temperature, beam_size=beam_size, top_k=top_k, eos_index=eos_index,
+                                       device=image_emb.device, n_img=hi - lo, seed=seed, img0=img0 + lo, seed_tensor=seed_tensor,
+                                       exact=exact, **kw)
+
+        def prompted_session(lo, hi, exact):
             """``session`` for a batch with ``caption_lengths``.  Slot ``s`` consumes the image (s = 0) or token ``s - 1`` and
             predicts token ``s``; image ``i`` makes its first draw at ``s = first_pos[i]``.  Slots below the shortest prompt run
             as the dense prefix does (one compact row per image); from there to the longest prompt all ``n * beam`` rows run and
@@ -275,57 +279,40 @@ class LSTMDecoder(_Planned, nn.Module):
             which ``hparent`` keeps them reading from); past the longest prompt it is the dense loop."""
             n, b = hi - lo, beam_size
             r = n * b
-            dev = image_emb.device
-            cap, first_pos, host = prompts
-            pmin, pmax = (min(host[lo:hi]), max(host[lo:hi])) if host is not None else (0, cap.shape[1])
-            helper = BeamSearchHelper(temperature, beam_size, top_k, eos_index=eos_index, device=dev, n_img=n, max_len=max_len,
-                                      seed=seed, img0=img0 + lo, seed_tensor=seed_tensor, exact=exact[0], top_p=top_p,
-                                      no_repeat_ngram_size=no_repeat_ngram_size, repetition_penalty=repetition_penalty).set_constraints(min_len, bad_words_ids)
-            helper.set_prompts(cap[lo:hi], first_pos[lo:hi])
-            st = self._State(self, plan, n, b, dev)
-            logits = torch.empty((r, (self.num_tokens + 255) // 256 * 256), device=dev)[:, :self.num_tokens]
-            gmax = (torch.empty((r, 4 * ((self.num_tokens + 255) // 256)), device=dev)[:, :hip.n_groups(self.num_tokens)]
-                    if plan["dtype"] in hip.HALF_DTYPES or plan.get("f32_planes") else None)
+            ses = DecodeSession(new_helper(lo, hi, exact, max_len=max_len), plan, self.num_tokens, early_stop_every)
+            ses.set_prompts(prompts, lo, hi)
+            helper, logits, gmax = ses.helper, ses.logits, ses.group_max
+            st = self._State(self, plan, n, b, image_emb.device)
             emb = image_emb[lo:hi]
-            for s in range(pmin):
+            for s in range(ses.pmin):
                 self._step(plan, st, n, 1, b, r, img_emb=emb if s == 0 else None, tokens=None if s == 0 else helper.tokens, tok_pos=s - 1)
-            for s in range(pmin, max_len):
+            for s in range(ses.pmin, max_len):
                 self._step(plan, st, r, b, 1, r, img_emb=emb if s == 0 else None, tokens=None if s == 0 else helper.tokens,
                            tok_pos=s - 1, hparent=helper.hparent, logits=logits, group_max=gmax)
                 if logits_hook is not None:
                     call_logits_hook(logits_hook, s, logits, helper)
-                if s <= pmax:
+                if s <= ses.pmax:
                     helper.step_prompted(logits, write_pos=s, t=0, step_index=s, first_sets_ended=True, group_max=gmax)
                 else:
                     helper.step(logits, first=False, write_pos=s, t=0, step_index=s, group_max=gmax)
                 yield
-                if early_stop_every and s > pmax and (s - pmax) % early_stop_every == 0 and bool(helper.done.all()):
+                if ses.all_done(s):
                     break
             return helper.finalize(len_bias_done=1, full_len=max_len, defer_check=defer_check, beams=return_beams)
 
-        def session(lo, hi):
+        def session(lo, hi, exact):
             if prompts is not None:
-                return (yield from prompted_session(lo, hi))
+                return (yield from prompted_session(lo, hi, exact))
             n, b = hi - lo, beam_size
             r = n * b
-            dev = image_emb.device
             # a prefix of max_len or more tokens: the reference still makes its first draw and returns prefix + 1 tokens -- it never
             # truncates to max_len (rnn_models.py:97-101: the loop simply does not run); the token buffers are that wide then
             eff_len = max(max_len, (0 if caption is None else caption.shape[1]) + 1)
-            helper = BeamSearchHelper(temperature, beam_size, top_k, eos_index=eos_index, device=dev, n_img=n,
-                                      max_len=eff_len, seed=seed, img0=img0 + lo,
-                                      noise_source=make_noise_source(rng, rng_seed, noise_source, lo, hi, img0, rng_state0), seed_tensor=seed_tensor,
-                                      exact=exact[0], top_p=top_p,
-                                      no_repeat_ngram_size=no_repeat_ngram_size, repetition_penalty=repetition_penalty).set_constraints(min_len, bad_words_ids)
-            pos = 0
-            if caption is not None:
-                pos = caption.shape[1]
-                helper.set_prefix(caption[lo:hi])
-            st = self._State(self, plan, n, b, dev)
-            # logits always fp32; row stride padded to 64 floats so rows are 16-byte aligned (vector stores)
-            logits = torch.empty((r, (self.num_tokens + 255) // 256 * 256), device=dev)[:, :self.num_tokens]   # whole 256-column chunks (vocab_wreg)
-            gmax = (torch.empty((r, 4 * ((self.num_tokens + 255) // 256)), device=dev)[:, :hip.n_groups(self.num_tokens)]
-                    if plan["dtype"] in hip.HALF_DTYPES or plan.get("f32_planes") else None)    # column-group maxima (16-bit paths, f32x planes)
+            noise = make_noise_source(rng, rng_seed, noise_source, lo, hi, img0, rng_state0)
+            ses = DecodeSession(new_helper(lo, hi, exact, max_len=eff_len, noise_source=noise), plan, self.num_tokens, early_stop_every)
+            pos = ses.set_prefix(caption, lo, hi)
+            helper, logits, gmax = ses.helper, ses.logits, ses.group_max
+            st = self._State(self, plan, n, b, image_emb.device)
             gm = None if gmax is None else gmax[:n]
             # image slot, then the teacher-forced prefix: one row per image living at logical row img*beam
             lg = logits[:n]
@@ -346,21 +333,15 @@ class LSTMDecoder(_Planned, nn.Module):
                     call_logits_hook(logits_hook, i, logits, helper)
                 helper.step(logits, first=False, write_pos=i, t=0, step_index=i, group_max=gmax)
                 yield
-                if early_stop_every and (i - pos) % early_stop_every == 0 and bool(helper.done.all()):
-                    break                                   # finished images are frozen by dh_beam_select: nothing left to do
+                if ses.all_done(i):
+                    break
             # (no decode step when the prefix fills max_len - 1: the reference then returns beam 0 -- see finalize)
             return helper.finalize(len_bias_done=1, full_len=eff_len, defer_check=defer_check, first_beam=pos + 1 >= max_len,
                                    beams=return_beams, pos=pos)
 
-        exact = [bool(exact)]
-        try:
-            return run_interleaved(session, image_emb.shape[0], streams)
-        except BeamOverflow:              # flat logits: more ties at a row's top-k threshold than the fast samplers hold -- once more,
-            if exact[0]:
-                raise
-            exact[0] = True               # every row draw through the general sampler (same seed: same captions where nothing overflowed)
-            warn_overflow_retry()
-            return run_interleaved(session, image_emb.shape[0], streams)
+        def run(exact):
+            return run_interleaved(lambda lo, hi: session(lo, hi, exact), image_emb.shape[0], streams)
+        return decode_with_overflow_retry(run, exact).public(return_beams)
 
     def generate(self, image_emb, caption=None, max_len=25,
                  temperature=1.0, beam_size=10, top_k=50, eos_index=3, **kw):

@@ -21,7 +21,7 @@ from torch import nn
 
 from .. import hip
 from ._f32x_guard import f32x_guarded
-from .beam import BeamCaptions, BeamOverflow, BeamSearchHelper, call_logits_hook, check_ids, check_return_attention, check_return_beams, check_top_p, check_repeat, check_constraints, compile_bad_words, classifier_must_be_finite, make_noise_source, prompt_session_inputs, resolve_seed, run_interleaved, warn_overflow_retry
+from .beam import BeamCaptions, DecodeSession, DecodeSettings, call_logits_hook, check_ids, classifier_must_be_finite, decode_with_overflow_retry, make_noise_source, prompt_session_inputs, resolve_seed, run_interleaved
 from .encoders import _Planned
 
 
@@ -435,22 +435,12 @@ class _IncrementalDecoder(_Planned, nn.Module):
                          out_dtype=torch.float32, tag="vocab")
         return out.view(bs, seq, -1)
 
-    def _generate_reforward(self, start_emb, enc_out, caption, max_len, temperature, beam_size, top_k, eos_index, seed, img0,
-                            noise_source, logits_hook, rng, rng_seed, exact, return_beams=False, top_p=1.0,
-                            no_repeat_ngram_size=0, repetition_penalty=1.0, min_len=0, bad_words_ids=None):
+    def _generate_reforward(self, helper, start_emb, enc_out, caption, max_len, logits_hook, return_beams=False):
         """``generate`` by the reference's own algorithm (transformers.py:521-577): the whole padded sequence of every beam row is
         re-run for each token on the module-API layers.  Only ``pad_index == 1`` needs it (see ``_forward_modules``); the beam
-        bookkeeping is the batched engine's."""
-        n, b, dev = start_emb.shape[0], beam_size, start_emb.device
-        helper = BeamSearchHelper(temperature, beam_size, top_k, eos_index=eos_index, device=dev, n_img=n, max_len=max_len,
-                                  src_len=max_len + 1, seed=seed, img0=img0,
-                                  noise_source=make_noise_source(rng, rng_seed, noise_source, 0, n, img0), exact=exact, top_p=top_p,
-                                  no_repeat_ngram_size=no_repeat_ngram_size, repetition_penalty=repetition_penalty).set_constraints(min_len, bad_words_ids)
-        helper.tokens.fill_(self.pad_index)
-        pos = 0
-        if caption is not None:
-            pos = caption.shape[1]
-            helper.set_prefix(caption)
+        bookkeeping is the batched engine's (``helper``: one for the whole batch)."""
+        b = helper.beam_size
+        pos = DecodeSession(helper, pad_index=self.pad_index).set_prefix(caption, 0, start_emb.shape[0])
         cls_w, cls_b = self.classifier.weight.detach(), _fp32(self.classifier.bias)
 
         def logits_at(tokens, semb, enc, t):
@@ -560,15 +550,13 @@ class _IncrementalDecoder(_Planned, nn.Module):
                         seed=None, img0=0, noise_source=None, logits_hook=None, streams=1, seed_tensor=None,
                         defer_check=False, early_stop_every=0, exact=False, rng=None, caption_lengths=None, return_beams=False, top_p=1.0,
                         no_repeat_ngram_size=0, repetition_penalty=1.0, min_len=0, bad_words_ids=None, return_attention=False):
-        check_return_beams(return_beams)
-        check_return_attention(return_attention, self)
-        top_p = check_top_p(top_p)
-        no_repeat_ngram_size, repetition_penalty = check_repeat(no_repeat_ngram_size, repetition_penalty, max_len)
-        min_len, bad_words_ids = check_constraints(min_len, bad_words_ids, max_len, self.num_tokens)
+        settings = DecodeSettings.from_kw(dict(return_beams=return_beams, return_attention=return_attention, top_p=top_p,
+                                               no_repeat_ngram_size=no_repeat_ngram_size, repetition_penalty=repetition_penalty,
+                                               min_len=min_len, bad_words_ids=bad_words_ids), max_len, self.num_tokens, self)
         self._check_mode()
         plan = self._get_plan()
         classifier_must_be_finite(plan)
-        bad_words_ids = compile_bad_words(bad_words_ids, self.num_tokens, start_emb.device)     # uploaded once (a BadWords: as it is)
+        settings = settings.compiled(start_emb.device)                 # the phrase list uploaded once (a BadWords: as it is)
         if caption_lengths is not None and self.pad_index == 1:
             raise NotImplementedError("caption_lengths with pad_index == 1: that decoder re-runs the whole sequence per token on the "
                                       "module path (_generate_reforward), which has no per-image prompt phase")
@@ -584,24 +572,22 @@ class _IncrementalDecoder(_Planned, nn.Module):
         if max_len + 1 > self.pos_embedding.num_embeddings:
             raise IndexError("index out of range in self")    # reference: pos_embedding lookup, SURVEY.md section 5
         start_emb = start_emb.to(plan["dtype"]).contiguous()
+        n_img, dev = start_emb.shape[0], start_emb.device
+
+        def new_helper(lo, hi, exact, **kw):
+            return settings.new_helper(temperature=temperature, beam_size=beam_size, top_k=top_k, eos_index=eos_index, device=dev,
+                                       n_img=hi - lo, max_len=max_len, src_len=max_len + 1, seed=seed, img0=img0 + lo, exact=exact, **kw)
+
         if self.pad_index == 1:
             if seed_tensor is not None or defer_check:
                 raise NotImplementedError("pad_index == 1 decodes by full re-forward on the host-driven module path: no hipGraph capture")
-            try:
-                return self._generate_reforward(start_emb, enc_out, caption, max_len, temperature, beam_size, top_k, eos_index, seed,
-                                                img0, noise_source, logits_hook, rng, rng_seed, bool(exact), return_beams, top_p,
-                                                no_repeat_ngram_size, repetition_penalty, min_len, bad_words_ids)
-            except BeamOverflow:
-                if exact:
-                    raise
-                warn_overflow_retry()
-                if rng_state0 is not None:
-                    torch.set_rng_state(rng_state0)
-                return self._generate_reforward(start_emb, enc_out, caption, max_len, temperature, beam_size, top_k, eos_index, seed,
-                                                img0, noise_source, logits_hook, rng, rng_seed, True, return_beams, top_p,
-                                                no_repeat_ngram_size, repetition_penalty, min_len, bad_words_ids)
 
-        def prompted_session(lo, hi):
+            def reforward(exact):
+                helper = new_helper(0, n_img, exact, noise_source=make_noise_source(rng, rng_seed, noise_source, 0, n_img, img0))
+                return self._generate_reforward(helper, start_emb, enc_out, caption, max_len, logits_hook, return_beams)
+            return decode_with_overflow_retry(reforward, exact, rng_state0).public(return_beams)
+
+        def prompted_session(lo, hi, exact):
             """``session`` for a batch with ``caption_lengths``.  Positions are absolute (slot 0 the image, caption token j at slot
             j + 1), so all images walk them together and only the beam step knows each image's phase: positions below the shortest
             prompt run as the dense prefix does (one compact row per image), positions up to the longest prompt run all
@@ -609,68 +595,45 @@ class _IncrementalDecoder(_Planned, nn.Module):
             anybody read -- and the rest is the dense loop.  Always the launch chain (never option ``decode_layers``)."""
             n, b = hi - lo, beam_size
             r = n * b
-            dev = start_emb.device
-            cap, first_pos, host = prompts
-            pmin, pmax = (min(host[lo:hi]), max(host[lo:hi])) if host is not None else (0, cap.shape[1])
-            helper = BeamSearchHelper(temperature, beam_size, top_k, eos_index=eos_index, device=dev, n_img=n, max_len=max_len,
-                                      src_len=max_len + 1, seed=seed, img0=img0 + lo, seed_tensor=seed_tensor, exact=exact[0], top_p=top_p,
-                                      no_repeat_ngram_size=no_repeat_ngram_size, repetition_penalty=repetition_penalty).set_constraints(min_len, bad_words_ids)
-            if self.pad_index != 0:
-                helper.tokens.fill_(self.pad_index)
-            helper.set_prompts(cap[lo:hi], first_pos[lo:hi], self.pad_index)
+            ses = DecodeSession(new_helper(lo, hi, exact, seed_tensor=seed_tensor), plan, self.num_tokens, early_stop_every, self.pad_index)
+            ses.set_prompts(prompts, lo, hi)
+            helper, logits, gmax = ses.helper, ses.logits, ses.group_max
             run = self._Run(self, plan, n, b, max_len + 1, None if enc_out is None else enc_out[lo:hi], dev, use_layers=False)
             attn_w = torch.empty((max_len + 1, r, run.s), device=dev, dtype=torch.float32) if return_attention else None
             semb = start_emb[lo:hi]
-            logits = torch.empty((r, (self.num_tokens + 255) // 256 * 256), device=dev)[:, :self.num_tokens]
-            gmax = (torch.empty((r, 4 * ((self.num_tokens + 255) // 256)), device=dev)[:, :hip.n_groups(self.num_tokens)]
-                    if plan["dtype"] in hip.HALF_DTYPES or plan.get("f32_planes") else None)
-            for t in range(pmin):
+            for t in range(ses.pmin):
                 self._decode_position(plan, run, t, n, 1, b, helper.tokens, helper.src, semb, attn_w=attn_w)
                 yield
-            for i in range(pmin, max_len + 1):
+            for i in range(ses.pmin, max_len + 1):
                 self._decode_position(plan, run, i, r, b, 1, helper.tokens, helper.src, semb, logits=logits, group_max=gmax, attn_w=attn_w)
                 if logits_hook is not None:
                     call_logits_hook(logits_hook, i, logits, helper)
-                if i <= pmax:
+                if i <= ses.pmax:
                     helper.step_prompted(logits, write_pos=i, t=i, step_index=i, first_sets_ended=False, group_max=gmax)
                 else:
                     helper.step(logits, first=False, write_pos=i, t=i, step_index=i, group_max=gmax)
                 yield
-                if early_stop_every and i > pmax and (i - pmax) % early_stop_every == 0 and bool(helper.done.all()):
+                if ses.all_done(i):
                     break
-            out = helper.finalize(len_bias_done=0, full_len=max_len, pad_index=self.pad_index, defer_check=defer_check,
-                                  beams=return_beams, attn_w=attn_w)
-            if return_attention:
-                maps[lo] = helper.attention
-            return out
+            return helper.finalize(len_bias_done=0, full_len=max_len, pad_index=self.pad_index, defer_check=defer_check,
+                                   beams=return_beams, attn_w=attn_w)
 
-        def session(lo, hi):
+        def session(lo, hi, exact):
             """Decodes images [lo, hi); yields after every position (see ``run_interleaved``)."""
             if prompts is not None:
-                return (yield from prompted_session(lo, hi))
+                return (yield from prompted_session(lo, hi, exact))
             n, b = hi - lo, beam_size
             r = n * b
-            dev = start_emb.device
-            helper = BeamSearchHelper(temperature, beam_size, top_k, eos_index=eos_index, device=dev, n_img=n,
-                                      max_len=max_len, src_len=max_len + 1, seed=seed, img0=img0 + lo,
-                                      noise_source=make_noise_source(rng, rng_seed, noise_source, lo, hi, img0, rng_state0),
-                                      seed_tensor=seed_tensor, exact=exact[0], top_p=top_p,
-                                      no_repeat_ngram_size=no_repeat_ngram_size, repetition_penalty=repetition_penalty).set_constraints(min_len, bad_words_ids)
-            if self.pad_index != 0:
-                helper.tokens.fill_(self.pad_index)
-            pos = 0
-            if caption is not None:
-                pos = caption.shape[1]
-                helper.set_prefix(caption[lo:hi])
+            noise = make_noise_source(rng, rng_seed, noise_source, lo, hi, img0, rng_state0)
+            ses = DecodeSession(new_helper(lo, hi, exact, noise_source=noise, seed_tensor=seed_tensor), plan, self.num_tokens,
+                                early_stop_every, self.pad_index)
+            pos = ses.set_prefix(caption, lo, hi)
+            helper, logits, gmax = ses.helper, ses.logits, ses.group_max
             # (return_attention: always the launch chain -- the persistent layer kernel leaves no q behind)
             run = self._Run(self, plan, n, b, max_len + 1, None if enc_out is None else enc_out[lo:hi], dev, use_layers=not return_attention)
             # the positions' maps [position, logical row, key], position-major like the KV cache; beams read them through helper.src
             attn_w = torch.empty((max_len + 1, r, run.s), device=dev, dtype=torch.float32) if return_attention else None
             semb = start_emb[lo:hi]
-            # logits always fp32; row stride padded to 64 floats so rows are 16-byte aligned (vector stores)
-            logits = torch.empty((r, (self.num_tokens + 255) // 256 * 256), device=dev)[:, :self.num_tokens]   # whole 256-column chunks (vocab_wreg)
-            gmax = (torch.empty((r, 4 * ((self.num_tokens + 255) // 256)), device=dev)[:, :hip.n_groups(self.num_tokens)]
-                    if plan["dtype"] in hip.HALF_DTYPES or plan.get("f32_planes") else None)    # column-group maxima (16-bit paths, f32x planes)
             gm = None if gmax is None else gmax[:n]
             # positions 0..pos with ONE row per image (logical row img*beam), sampling at `pos`
             lg = logits[:n]
@@ -689,12 +652,10 @@ class _IncrementalDecoder(_Planned, nn.Module):
                 # at i == max_len nothing is written (transformers.py:557) but beams are still re-drawn
                 helper.step(logits, first=False, write_pos=i, t=i, step_index=i, group_max=gmax)
                 yield
-                if early_stop_every and (i - pos) % early_stop_every == 0 and bool(helper.done.all()):
+                if ses.all_done(i):
                     break                                   # all_ended() break of the reference (transformers.py:585)
             out = helper.finalize(len_bias_done=0, full_len=max_len, pad_index=self.pad_index, defer_check=defer_check,
                                   beams=return_beams, pos=pos, attn_w=attn_w)
-            if return_attention:
-                maps[lo] = helper.attention
             if run.layers_sync is not None and not defer_check and int(run.layers_sync[320]) != 0:
                 # a hand-over of the persistent layer kernel timed out (fewer than 256 resident workgroups?): its results are undefined
                 hip.set_option("decode_layers", 0)
@@ -702,35 +663,9 @@ class _IncrementalDecoder(_Planned, nn.Module):
                                    "workgroups; the option has been switched off for this process -- repeat the call")
             return out
 
-        maps = {}                         # return_attention: first image of a session -> its beams' maps [n, B, T, S]
-
-        def with_attention(out):
-            """The sessions ran ``dh_beam_finalize_beams`` (``out``: a ``BeamCaptions``, in front of the error word with
-            ``defer_check``): ``(BeamCaptions, attention [N, B, T, S])`` for ``return_beams``, else the plain pair -- ``best()``, bit
-            for bit -- and the drawn slot's maps ``(tokens, lengths, attention [N, T, S])``."""
-            if not return_attention:
-                return out
-            parts = [maps[lo] for lo in sorted(maps)]
-            for part in parts:
-                part.record_stream(torch.cuda.current_stream())
-            att = parts[0] if len(parts) == 1 else torch.cat(parts, 0)
-            deferred = not isinstance(out, BeamCaptions)
-            bc = out[0] if deferred else out
-            if return_beams:
-                res = (bc, att)
-            else:
-                res = bc.best() + (att[torch.arange(att.shape[0], device=att.device), bc.drawn],)
-            return res + (out[1],) if deferred else res
-
-        exact = [bool(exact)]
-        try:
-            return with_attention(run_interleaved(session, start_emb.shape[0], streams))
-        except BeamOverflow:              # flat logits (see LSTMDecoder.generate_batch): once more through the general sampler
-            if exact[0]:
-                raise
-            exact[0] = True
-            warn_overflow_retry()
-            return with_attention(run_interleaved(session, start_emb.shape[0], streams))
+        def run(exact):                   # (flat logits: see LSTMDecoder._generate_batch)
+            return run_interleaved(lambda lo, hi: session(lo, hi, exact), n_img, streams)
+        return decode_with_overflow_retry(run, exact).public(return_beams)
 
 
 class TransformerDecoder(_IncrementalDecoder):
@@ -751,10 +686,8 @@ class TransformerDecoder(_IncrementalDecoder):
     def generate_batch(self, start_emb, enc_out, caption=None, max_len=25, temperature=1.0, beam_size=10,
                        top_k=50, eos_index=3, *, caption_lengths=None, **kw):
         """``start_emb [N, D]``, ``enc_out [N, S, D]`` -> ``(tokens [N, max_len], lengths [N])``.  ``caption_lengths`` (keyword only):
-        a prompt of its own length per image, see ``LSTMDecoder.generate_batch``; ``return_beams=True`` (in ``kw``): every beam as a
-        ``beam.BeamCaptions``, see there; ``top_p`` (in ``kw``): nucleus filtering beside ``top_k``, see there;
-        ``no_repeat_ngram_size`` / ``repetition_penalty`` (in ``kw``): the history edits in front of every row draw, see there;
-        ``min_len`` / ``bad_words_ids`` (in ``kw``): no ``<eos>`` below ``min_len``, no banned phrase, see there;
+        a prompt of its own length per image; ``return_beams``, ``top_p``, ``no_repeat_ngram_size`` / ``repetition_penalty``, ``min_len`` /
+        ``bad_words_ids`` (in ``kw``): see ``LSTMDecoder.generate_batch`` for all;
         ``return_attention=True`` (in ``kw``): one more result, the fp32 map of where every token looked -- ``attention [N, T, S]``
         behind the pair, or ``[N, B, T, S]`` behind the ``BeamCaptions`` -- see ``caption_models._CaptioningBase.decode``."""
         return self._generate_batch(start_emb, enc_out, caption, max_len, temperature, beam_size, top_k,
@@ -781,10 +714,7 @@ class SelfAttentionTransformerDecoder(_IncrementalDecoder):
     @f32x_guarded
     def generate_batch(self, start_emb, caption=None, max_len=25, temperature=1.0, beam_size=10,
                        top_k=50, eos_index=3, *, caption_lengths=None, **kw):
-        """``caption_lengths`` (keyword only): a prompt of its own length per image; ``return_beams=True`` (in ``kw``): every beam as
-        a ``beam.BeamCaptions``; ``top_p`` (in ``kw``): nucleus filtering beside ``top_k``; ``no_repeat_ngram_size`` / ``repetition_penalty``
-        (in ``kw``): the history edits in front of every row draw; ``min_len`` / ``bad_words_ids`` (in ``kw``): no ``<eos>`` below
-        ``min_len``, no banned phrase -- see ``LSTMDecoder.generate_batch`` for all."""
+        """``caption_lengths`` (keyword only) and the decode settings in ``kw``: see ``LSTMDecoder.generate_batch``."""
         return self._generate_batch(start_emb, None, caption, max_len, temperature, beam_size, top_k,
                                     eos_index, caption_lengths=caption_lengths, **kw)
 

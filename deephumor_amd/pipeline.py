@@ -16,6 +16,7 @@ work).  Nothing here computes: every operation is a kernel of libdeephumor_hip.s
 import torch
 
 from . import hip
+from .models.beam import BeamOverflow, BeamSearchHelper, DecodeSettings, resolve_seed, warn_overflow_retry
 
 __all__ = ["CaptionPipeline", "u8_preprocess"]
 
@@ -44,8 +45,10 @@ class CaptionPipeline:
         not per batch, so every batch must have their row count.  Host-resident ``caption_lengths`` are validated with every batch
         (``beam.check_prompts``; like the dense path's id check this reads the range of a device-resident ``caption`` back, one
         host synchronisation per batch); device-resident lengths are not read back here and are the caller's to validate."""
-        from .models.beam import check_return_attention
-        if check_return_attention(gen_kw.get("return_attention", False)):     # (a non-bool: TypeError, as everywhere)
+        # every decode setting is in gen_kw (see LSTMDecoder.generate_batch): a bad value raises here, before the first batch is staged;
+        # the phrase list is checked here and compiled -- uploaded -- once, by the first batch
+        settings = DecodeSettings.from_kw(gen_kw, gen_kw.get("max_len", 25), getattr(model, "_hp", {}).get("num_tokens"))
+        if settings.return_attention:
             raise NotImplementedError("return_attention: CaptionPipeline hands batches over through pinned (tokens, lengths) / BeamCaptions "
                                       "slots that carry no float payload; call model.generate_batch(..., return_attention=True)")
         gen_kw.pop("return_attention", None)         # (False: the pipeline without the keyword)
@@ -68,14 +71,7 @@ class CaptionPipeline:
         # (pad_index == 1: host-driven full re-forward) decode synchronously
         self._async = getattr(getattr(model, "decoder", None), "pad_index", 0) != 1
         # return_beams=True (in gen_kw): every batch is yielded as a beam.BeamCaptions (to_host: its fields in pinned memory)
-        from .models.beam import check_constraints, check_repeat, check_return_beams, check_top_p
-        self._beams = check_return_beams(gen_kw.get("return_beams", False))
-        check_top_p(gen_kw.get("top_p", 1.0))      # (in gen_kw like every decode setting: nucleus filtering, see LSTMDecoder.generate_batch)
-        # (likewise: the history edits in front of every row draw; a bad value raises here, before the first batch is staged)
-        check_repeat(gen_kw.get("no_repeat_ngram_size", 0), gen_kw.get("repetition_penalty", 1.0), gen_kw.get("max_len"))
-        # (min_len / bad_words_ids likewise; the list is checked here and compiled -- uploaded -- once, by the first batch)
-        check_constraints(gen_kw.get("min_len", 0), gen_kw.get("bad_words_ids"), gen_kw.get("max_len", 25),
-                          getattr(model, "_hp", {}).get("num_tokens"))
+        self._beams = settings.return_beams
 
     # -- stages ------------------------------------------------------------------------------------------------------
     def _stage(self, host_inputs):
@@ -128,7 +124,6 @@ class CaptionPipeline:
         """Queues the decode of one batch on the decode stream and returns WITHOUT waiting for it: the beam engine's error word is
         not read here (``defer_check``) but copied to pinned memory behind the token ids and examined by ``_finish`` once the
         batch's event has fired."""
-        from .models.beam import resolve_seed
         if self.gen_kw.get("rng") != "torch":
             seed = resolve_seed(seed)                 # fixed now: a repeated decode (BeamOverflow) must draw the same noise
         with torch.cuda.stream(self.dec_s), torch.no_grad():
@@ -167,7 +162,6 @@ class CaptionPipeline:
         """Waits for a queued batch and returns its ``(tokens, lengths)``; reads the deferred error word: flat logits that
         overflowed the pre-filtered samplers (``BeamOverflow``) repeat this batch through the general sampler, anything else raises
         as ``generate_batch`` does."""
-        from .models.beam import BeamOverflow, BeamSearchHelper, warn_overflow_retry
         q["done"].synchronize()
         if q["err"] is not None:
             try:

@@ -1,0 +1,35 @@
+"""Golden G24 replayed on a real MI355X: every route of the Python decode layer (``decode_trace_cases``) makes the launches, in the
+order, and returns the tensors, bit for bit, that ``tools/make_decode_trace_golden.py`` recorded.  No tolerances."""
+import pytest
+import torch
+
+pytestmark = pytest.mark.gpu
+
+import decode_trace_cases as dt  # noqa: E402
+from helpers import golden  # noqa: E402
+
+CASES = [(kind, key) for kind in dt.KINDS for key in dt.cases(kind)]
+
+
+@pytest.fixture(scope="module")
+def thunks():
+    return {kind: dt.cases(kind) for kind in dt.KINDS}
+
+
+def test_the_fixture_holds_exactly_these_cases():
+    for kind in dt.KINDS:
+        recorded = {k.rsplit("/", 1)[0] for k in golden(dt.fixture_name(kind)).files}
+        assert recorded == set(dt.cases(kind)), kind
+
+
+@pytest.mark.parametrize("kind,key", CASES, ids=[f"{kind}-{key}" for kind, key in CASES])
+def test_route_replays_its_recording(kind, key, thunks):
+    g = golden(dt.fixture_name(kind))
+    want = {k[len(key) + 1:]: g[k] for k in g.files if k.rsplit("/", 1)[0] == key}
+    got = thunks[kind][key]()
+    assert got.keys() == want.keys(), (kind, key)
+    if "launches" in want:
+        assert got.pop("launches").tolist() == want.pop("launches").tolist(), (kind, key)
+    for name, arr in want.items():
+        assert got[name].dtype == arr.dtype and got[name].shape == arr.shape, (kind, key, name)
+        assert torch.equal(torch.from_numpy(got[name]), torch.from_numpy(arr)), (kind, key, name)

@@ -1,0 +1,41 @@
+"""Records golden G24 (``tests/golden/g24_decode_trace_<kind>.npz``): the ordered ``hip._launch`` entry-point names and every returned
+tensor, bit for bit, of the decode layer's routes -- ``generate_batch`` with and without every control, prefix, prompts, streams,
+``exact``, the re-forward decoder, ``generate_batch_graphed``, ``CaptionPipeline`` and single-image ``generate``, in bf16 and fp32
+(the cases: ``tests/decode_trace_cases.py``, which ``tests/test_decode_trace_gpu.py`` replays).
+
+Needs the GPU, not the reference: the fixture is what THIS tree does, recorded in front of a change to the Python decode layer that
+must move no launch and no bit.  Every case is run twice here and must repeat itself before it is written.
+
+    python tools/make_decode_trace_golden.py [kind ...]
+"""
+import os
+import sys
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+
+import decode_trace_cases as dt                                            # noqa: E402
+
+OUT = os.path.join(ROOT, "tests", "golden")
+
+
+def main():
+    for kind in (sys.argv[1:] or dt.KINDS):
+        fix = {}
+        for key, thunk in dt.cases(kind).items():
+            got, again = thunk(), thunk()
+            assert got.keys() == again.keys(), key
+            for name, arr in got.items():
+                assert arr.dtype == again[name].dtype and np.array_equal(arr, again[name], equal_nan=arr.dtype.kind == "f"), (key, name)
+                fix[f"{key}/{name}"] = arr
+            print(kind, key, {k: tuple(v.shape) for k, v in got.items()}, flush=True)
+        path = os.path.join(OUT, dt.fixture_name(kind))
+        np.savez_compressed(path, **fix)
+        print(path, os.path.getsize(path), "bytes", flush=True)
+
+
+if __name__ == "__main__":
+    main()
