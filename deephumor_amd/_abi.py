@@ -5,7 +5,7 @@ import ctypes
 import torch
 
 F32, BF16, BF16_OUT_F32, F16, F16_OUT_F32 = 0, 1, 2, 3, 4
-ABI_VERSION = 34
+ABI_VERSION = 35
 HALF_DTYPES = (torch.bfloat16, torch.float16)       # the two 16-bit storage / MFMA operand types
 ERR_ALL_FILTERED, ERR_OVERFLOW, ERR_TOO_FEW, ERR_NONFINITE = 1, 2, 4, 8
 MAX_BEAMS = 64
@@ -30,7 +30,7 @@ class TrLayer(_c.Structure):
 class TrModel(_c.Structure):
     _fields_ = ([(n, _I) for n in ("n_layers", "D", "n_heads", "pf_dim", "V", "pad_index", "cross", "S", "dtype")]
                 + [("emb_scale", _F), ("layers", _c.POINTER(TrLayer))]
-                + [(n, _P) for n in ("tok_emb", "pos_emb", "cls_w", "cls_b", "keymask", "cls_w_pk", "cls_b_pad", "cls_w_x", "layers_table", "layers_sync")])
+                + [(n, _P) for n in ("tok_emb", "pos_emb", "cls_w", "cls_b", "keymask", "cls_w_pk", "cls_b_pad", "cls_w_x")])
 
 
 class TrScratch(_c.Structure):
@@ -132,10 +132,6 @@ SIGNATURES = {
     "dh_beam_row_sample_nucleus": [_P, _I, _I, _P, _I, _I, _I, _I, _I, _I, _I, _F, _F, _I, _P, _U64, _P, _I, _I, _P, _I, _P, _P, _P, _P],
     "dh_beam_history_logits": [_P, _I, _I, _P, _I, _I, _I, _P, _I, _I, _I, _I, _I, _P, _I, _F, _P],
     "dh_beam_constrain_logits": [_P, _I, _I, _P, _I, _I, _I, _P, _I, _I, _I, _I, _I, _P, _I, _I, _P, _P, _I, _P],
-    "dh_decode_layers_supported": [_c.POINTER(TrModel), _I, _I],
-    "dh_decode_layers_table_bytes": [_I],
-    "dh_decode_layers_table": [_c.POINTER(TrModel), _P, _P],
-    "dh_decode_layers": [_c.POINTER(TrModel), _c.POINTER(TrScratch), _P, _P, _I, _P, _I, _I, _I, _I, _I, _I, _P, _P],
     "dh_transformer_decode_position": [_c.POINTER(TrModel), _c.POINTER(TrScratch), _P, _P, _I, _P, _I, _I, _I, _I, _I, _I,
                                        _P, _P, _I, _P, _I, _P],
     "dh_transformer_decode_position_attn": [_c.POINTER(TrModel), _c.POINTER(TrScratch), _P, _P, _I, _P, _I, _I, _I, _I, _I, _I,

@@ -1,6 +1,5 @@
-// Arithmetic shared by the attention kernels of attention.hip and by the attention phases of the persistent decoder-layer kernel
-// (decode_layers.hip): ONE definition of the softmax arithmetic, the cross-lane reductions, the packed-operand helpers and the
-// matrix-core cross-attention core, so that every form stays bit-identical to the others.
+// Arithmetic shared by the attention kernels of attention.hip: ONE definition of the softmax arithmetic, the cross-lane reductions,
+// the packed-operand helpers and the matrix-core cross-attention core, so that every form stays bit-identical to the others.
 #pragma once
 #include "common.h"
 

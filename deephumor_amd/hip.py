@@ -71,10 +71,10 @@ def option(key):
 
 def set_option(key, value):
     """``dh_set_option``: overrides an option from now on.  Dispatch options of the native step drivers (``decode_wreg``,
-    ``decode_wreg_min_rows``, ``qkv_fusion_max_rows``, ``cross_qproj``, ``lstm_wreg``, ``vocab_wreg``, tile choices) take effect at
-    the next launch; the options the Python layer reads while it builds a model's weight plan (``conv1x1_wreg`` ... ``qproj_fusion``,
-    ``f32_split``) are part of every plan's cache key (``options_epoch``): models rebuild their plans -- and re-capture their
-    hipGraphs -- at the next call.  Returns the previous value."""
+    ``decode_wreg_min_rows``, ``lstm_wreg``, ``lstm_wreg_min_rows``, ``vocab_wreg``, ``vocab_areg``) take effect at
+    the next launch; the options the Python layer reads while it builds a model's weight plan (``deferred_ln``, ``packed_cross``,
+    ``encoder_generic``, ``f32_split``) are part of every plan's cache key (``options_epoch``): models rebuild their plans -- and
+    re-capture their hipGraphs -- at the next call.  Returns the previous value."""
     global options_epoch
     old = option(key)
     _check(load().dh_set_option(key.encode(), int(value)), f"dh_set_option({key!r})")
@@ -89,7 +89,7 @@ options_epoch = 0       # bumped by every set_option that changes a value; part 
 
 
 class option_scope:
-    """``with hip.option_scope(decode_wreg=0, s3_tail=0): ...`` -- options set for the block, previous values restored after it
+    """``with hip.option_scope(decode_wreg=0, lstm_wreg=0): ...`` -- options set for the block, previous values restored after it
     (A/B tests of results-identical kernels)."""
 
     def __init__(self, **kv):
@@ -1058,19 +1058,6 @@ def transformer_decode_position(model, scratch, start_emb, tokens, src, n_img, r
             tokens.stride(0), _ptr(src), src.stride(0), n_img, rows_per_img, row_mult, rows_total, t, _ptr(x_out),
             _ptr(logits), logits.stride(0) if logits is not None else 0, _ptr(group_max),
             group_max.stride(0) if group_max is not None else 0, _stream())
-
-
-def decode_layers_supported(model, rows_per_img, t):
-    """``dh_decode_layers_supported`` for a ``TrModel`` description."""
-    return bool(load().dh_decode_layers_supported(_c.byref(model), int(rows_per_img), int(t)))
-
-
-def decode_layers_table(model, device):
-    """The device-resident per-layer table of ``dh_decode_layers`` for this ``TrModel`` description (``dh_decode_layers_table``)."""
-    nbytes = load().dh_decode_layers_table_bytes(model.n_layers)
-    table = torch.empty((nbytes,), dtype=torch.uint8, device=device)
-    _launch("dh_decode_layers_table", _c.byref(model), _ptr(table), _stream())
-    return table
 
 
 def conv1x1_dual_nhwc(y, x, w_cat, shift, stride, relu=True):

@@ -269,7 +269,7 @@ class _IncrementalDecoder(_Planned, nn.Module):
         """KV cache + cross-attention operands + scratch for one batch, described to the native step
         driver (``dh_transformer_decode_position``) through plain C structs."""
 
-        def __init__(self, dec, plan, n_img, beam, n_pos, enc_out, dev, use_layers=True):
+        def __init__(self, dec, plan, n_img, beam, n_pos, enc_out, dev):
             d, nl = dec.hid_dim, len(dec.layers)
             self.n_img, self.beam, self.rows_total, self.n_pos = n_img, beam, n_img * beam, n_pos
             self.dtype = plan["dtype"]
@@ -325,14 +325,6 @@ class _IncrementalDecoder(_Planned, nn.Module):
                 m.cls_w_pk, m.cls_b_pad = P(plan["cls_w_pk"]), P(plan["cls_b_pad"])
             if "cls_w_x" in plan:
                 m.cls_w_x = P(plan["cls_w_x"])
-            # the decoder layers of a position as ONE persistent launch (csrc/decode_layers.hip): a device-resident table of this run's
-            # per-layer pointers + the clusters' hand-over words (zero once; the kernel keeps them consistent from launch to launch)
-            self.layers_table = self.layers_sync = None
-            # (use_layers=False: a prompted batch always takes the launch chain)
-            if use_layers and hip.option("decode_layers") and self.dtype in hip.HALF_DTYPES and hip.decode_layers_supported(m, 1, 0):
-                self.layers_sync = torch.zeros((512,), device=dev, dtype=torch.int32)
-                self.layers_table = hip.decode_layers_table(m, dev)
-                m.layers_table, m.layers_sync = self.layers_table.data_ptr(), self.layers_sync.data_ptr()
 
         def scratch(self, rows):
             if rows not in self._scratch:
@@ -592,13 +584,13 @@ class _IncrementalDecoder(_Planned, nn.Module):
             j + 1), so all images walk them together and only the beam step knows each image's phase: positions below the shortest
             prompt run as the dense prefix does (one compact row per image), positions up to the longest prompt run all
             ``n * beam`` rows -- the rows of a still-forced image recompute copies of its base row, the only one ``src`` lets
-            anybody read -- and the rest is the dense loop.  Always the launch chain (never option ``decode_layers``)."""
+            anybody read -- and the rest is the dense loop."""
             n, b = hi - lo, beam_size
             r = n * b
             ses = DecodeSession(new_helper(lo, hi, exact, seed_tensor=seed_tensor), plan, self.num_tokens, early_stop_every, self.pad_index)
             ses.set_prompts(prompts, lo, hi)
             helper, logits, gmax = ses.helper, ses.logits, ses.group_max
-            run = self._Run(self, plan, n, b, max_len + 1, None if enc_out is None else enc_out[lo:hi], dev, use_layers=False)
+            run = self._Run(self, plan, n, b, max_len + 1, None if enc_out is None else enc_out[lo:hi], dev)
             attn_w = torch.empty((max_len + 1, r, run.s), device=dev, dtype=torch.float32) if return_attention else None
             semb = start_emb[lo:hi]
             for t in range(ses.pmin):
@@ -629,8 +621,7 @@ class _IncrementalDecoder(_Planned, nn.Module):
                                 early_stop_every, self.pad_index)
             pos = ses.set_prefix(caption, lo, hi)
             helper, logits, gmax = ses.helper, ses.logits, ses.group_max
-            # (return_attention: always the launch chain -- the persistent layer kernel leaves no q behind)
-            run = self._Run(self, plan, n, b, max_len + 1, None if enc_out is None else enc_out[lo:hi], dev, use_layers=not return_attention)
+            run = self._Run(self, plan, n, b, max_len + 1, None if enc_out is None else enc_out[lo:hi], dev)
             # the positions' maps [position, logical row, key], position-major like the KV cache; beams read them through helper.src
             attn_w = torch.empty((max_len + 1, r, run.s), device=dev, dtype=torch.float32) if return_attention else None
             semb = start_emb[lo:hi]
@@ -654,14 +645,8 @@ class _IncrementalDecoder(_Planned, nn.Module):
                 yield
                 if ses.all_done(i):
                     break                                   # all_ended() break of the reference (transformers.py:585)
-            out = helper.finalize(len_bias_done=0, full_len=max_len, pad_index=self.pad_index, defer_check=defer_check,
-                                  beams=return_beams, pos=pos, attn_w=attn_w)
-            if run.layers_sync is not None and not defer_check and int(run.layers_sync[320]) != 0:
-                # a hand-over of the persistent layer kernel timed out (fewer than 256 resident workgroups?): its results are undefined
-                hip.set_option("decode_layers", 0)
-                raise RuntimeError("deephumor_amd: the persistent decoder-layer kernel (option decode_layers) timed out waiting for its "
-                                   "workgroups; the option has been switched off for this process -- repeat the call")
-            return out
+            return helper.finalize(len_bias_done=0, full_len=max_len, pad_index=self.pad_index, defer_check=defer_check,
+                                   beams=return_beams, pos=pos, attn_w=attn_w)
 
         def run(exact):                   # (flat logits: see LSTMDecoder._generate_batch)
             return run_interleaved(lambda lo, hi: session(lo, hi, exact), n_img, streams)

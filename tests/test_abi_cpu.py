@@ -95,3 +95,24 @@ def test_option_table():
     assert hip.option("decode_wreg_min_rows") == 123 and hip.option("encoder_generic") == opts["encoder_generic"][0]
     hip.set_option("decode_wreg_min_rows", old)
     assert hip.option("decode_wreg_min_rows") == opts["decode_wreg_min_rows"][0]
+
+
+def test_decode_layers_is_removed_from_library_abi_and_option_table():
+    """The persistent decoder-layer kernel (round 6: bit-identical, 842 us per position against ~400 us for the launch chain) is gone
+    from the shipped library: no exported symbol, no option, and the option table of INTEGRATION.md names exactly the library's options
+    (a table row names one option or a group of related ones, so the options are counted, not the lines)."""
+    from deephumor_amd import _build, hip
+    path = _build.build()
+    image = open(path, "rb").read()                                       # (its dynamic string table holds every exported name)
+    assert b"dh_abi_version\0" in image and b"dh_decode_layers" not in image
+    for name in ("dh_decode_layers", "dh_decode_layers_supported", "dh_decode_layers_table_bytes", "dh_decode_layers_table"):
+        assert not hasattr(ctypes.CDLL(path), name), name
+    assert not [s for s in hip.SIGNATURES if s.startswith("dh_decode_layers")]
+    opts = hip.options()
+    assert "decode_layers" not in opts
+    lib = hip.load()
+    assert lib.dh_set_option(b"decode_layers", 1) == 1                    # DH_ERR_BAD_ARG
+    text = open(os.path.join(ROOT, "INTEGRATION.md")).read()
+    table = text[text.index("| Option (environment default `DH_<KEY>`)"):].split("\n\n")[0].splitlines()[2:]
+    documented = [key for row in table for key in re.findall(r"`(\w+)`", row.split("|")[1])]
+    assert sorted(documented) == sorted(opts) and len(documented) == lib.dh_option_count() == 15

@@ -193,7 +193,7 @@ def test_new_entry_points_are_declared_bound_and_exported():
         assert hasattr(lib, name)
     old, new = _abi.SIGNATURES["dh_transformer_decode_position"], _abi.SIGNATURES["dh_transformer_decode_position_attn"]
     assert new[:len(old) - 1] == old[:-1] and len(old) == 18
-    assert [n for n, _ in _abi.TrModel._fields_][-2:] == ["layers_table", "layers_sync"]
+    assert [n for n, _ in _abi.TrModel._fields_][-2:] == ["cls_b_pad", "cls_w_x"]
     lib.dh_abi_version.restype = ctypes.c_int
     assert lib.dh_abi_version() == _abi.ABI_VERSION == int(re.search(r"#define DH_ABI_VERSION (\d+)", header).group(1))
 

@@ -299,13 +299,13 @@ def test_abi_header_table_and_library_agree():
         assert t is want, (a, t)
     assert [a.split()[-1].lstrip("*") for a in args] == ARGS
     version = int(re.search(r"#define DH_ABI_VERSION (\d+)", header).group(1))
-    assert version == _abi.ABI_VERSION == hip.ABI_VERSION == 34
+    assert version == _abi.ABI_VERSION == hip.ABI_VERSION == 35
     assert int(re.search(r"#define DH_BEAM_MAX_BAD_WORDS (\d+)", header).group(1)) == _abi.MAX_BAD_WORDS == hip.MAX_BAD_WORDS == 4096
     assert int(re.search(r"#define DH_BEAM_MAX_BAD_LEN (\d+)", header).group(1)) == _abi.MAX_BAD_LEN == hip.MAX_BAD_LEN == 32
     lib = ctypes.CDLL(_build.build())
     assert hasattr(lib, NAME)
     lib.dh_abi_version.restype = ctypes.c_int
-    assert lib.dh_abi_version() == 34
+    assert lib.dh_abi_version() == 35
     # one new symbol, no prototype moved
     assert len(_abi.SIGNATURES["dh_beam_history_logits"]) == 17 and len(_abi.SIGNATURES["dh_beam_row_sample_groups"]) == 22
     assert len(_abi.SIGNATURES["dh_beam_row_sample_nucleus"]) == 25 and len(_abi.SIGNATURES["dh_beam_select"]) == 26

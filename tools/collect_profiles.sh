@@ -47,12 +47,8 @@ python3 $R/bench.py --full --workload c3 --batch 32 --shard-of 8 --steps 5 --war
 ( cd "$TMPDIR" && rocprofv3 --kernel-trace --stats -d $TMPDIR/prof_c5s -o t -- python3 $R/bench.py --full --workload c5 --shard-of 8 --shard-only --steps 2 --warmup 1 > /dev/null 2>&1
   python3 $R/tools/rocpd_stats.py $TMPDIR/prof_c5s/t_results.db --by-grid --top 0 --sequence 60 --csv $OUT/c5_shard_kernel_stats.csv > $OUT/c5_shard_kernel_stats.txt 2>&1 )
 python3 $R/tools/gather_cost.py > $OUT/gather_cost.json 2>/dev/null
-# round 6: the split-operand decode layers per shape, the persistent decoder-layer kernel (opt-in: C3 step with it, per-phase stamps of
-# layer 0, rocprofv3 duration of the launch), the encoder as sub-batches on several streams
+# round 6: the split-operand decode layers per shape, the encoder as sub-batches on several streams (the persistent decoder-layer
+# kernel's records in profiles/r6/ were taken before its removal)
 python3 $R/tools/f32x_kbench.py > $OUT/f32x_kbench.txt 2>/dev/null
-DH_DECODE_LAYERS=1 python3 $R/bench.py --full --workload c3 --steps 5 --warmup 2 --quick --schedule sequential 2>/dev/null | tail -1 > $OUT/bench_c3_decode_layers.json
-DH_DECODE_LAYERS=1 DH_DL_DEBUG=2 python3 $R/tools/decode_layers_stamps.py > $OUT/decode_layers_phase_stamps.txt 2>/dev/null
-( cd "$TMPDIR" && DH_DECODE_LAYERS=1 rocprofv3 --kernel-trace --stats -d $TMPDIR/prof_c3dl -o t -- python3 $R/bench.py --full --workload c3 --steps 2 --warmup 1 --quick --schedule sequential > /dev/null 2>&1
-  python3 $R/tools/rocpd_stats.py $TMPDIR/prof_c3dl/t_results.db --by-grid --top 12 --csv $OUT/c3_decode_layers_kernel_stats.csv 2> $OUT/c3_decode_layers_kernel_stats.txt )
 python3 $R/tools/enc_streams_probe.py > $OUT/encoder_streams_probe.txt 2>/dev/null
 ls -la $OUT
