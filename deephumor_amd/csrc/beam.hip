@@ -605,7 +605,9 @@ struct SelLds {
 // count the instantiation takes (register arrays of the beams' flags / scores): 16 for the usual settings, 64 for beam_size > 16.
 // PR (dh_beam_select_prompted): the image's phase comes from p.first_pos[img] against p.step_index instead of the launch-wide p.first
 // (see prompt_row_idle); its first step reads the picks of its logical row img * beam, where the prompted samplers leave them.
-template <int MB, bool PR = false>
+// DT (dh_beam_select_best): no draw -- the `beam` candidates with the largest score stay, equal scores to the lower candidate index,
+// -inf last; hparent is the real parent row.  Neither noise nor temperature is read.
+template <int MB, bool PR = false, bool DT = false>
 __device__ __forceinline__ void beam_select_image(const SelectParams& p, const int img, const int lane, const SelLds& L) {
     int32_t* stage = L.stage;
     int* ctok = L.ctok; int* cpar = L.cpar; int* keep = L.keep; float* cval = L.cval; float* q = L.q; uint8_t* cend = L.cend;
@@ -689,7 +691,18 @@ __device__ __forceinline__ void beam_select_image(const SelectParams& p, const i
     }
     wave_lds_sync();
     const int n = s_n;
-    if (!first) {
+    if constexpr (DT) {
+        if (!first) {
+            for (int j = lane; j < B; j += 64) keep[j] = min(j, n - 1);
+            wave_lds_sync();
+            for (int c = lane; c < n; c += 64) {
+                const float me = cval[c];
+                int r = 0;
+                for (int j = 0; j < n; ++j) r += (cval[j] > me) || (cval[j] == me && j < c);
+                if (r < B) keep[r] = c;
+            }
+        }
+    } else if (!first) {
         // draw `beam` candidates without replacement from softmax(cand_val / T)
         float m = -INFINITY;
         for (int c = lane; c < n; c += 64) m = fmaxf(m, cval[c] / p.temperature);
@@ -736,7 +749,7 @@ __device__ __forceinline__ void beam_select_image(const SelectParams& p, const i
             p.vals[base + b] = cval[c];
             p.ended[base + b] = cend[c];
             p.parent[base + b] = base + par;
-            p.hparent[base + b] = base + c / B;        // rnn_models.py:135-137: dense B*B layout index
+            p.hparent[base + b] = DT ? base + par : base + c / B;        // rnn_models.py:135-137: dense B*B layout index
         }
         all_ended &= cend[c];
     }
@@ -1141,7 +1154,7 @@ extern "C" int dh_beam_constrain_logits(float* logits, int ldl, int V, float* gr
 
 // ------------------------------------------------------------------------------------------------
 
-template <int MB, bool PR>
+template <int MB, bool PR, bool DT = false>
 __global__ __launch_bounds__(64) void beam_select_kernel(SelectParams p) {
     extern __shared__ int32_t stage[];
     __shared__ int ctok[MB * MB], cpar[MB * MB], keep[MB];
@@ -1151,10 +1164,10 @@ __global__ __launch_bounds__(64) void beam_select_kernel(SelectParams p) {
     __shared__ int32_t pki[MB * MB];
     __shared__ float pkv[MB * MB];
     const SelLds L{stage, ctok, cpar, keep, cval, q, cend, &s_n, pki, pkv};
-    beam_select_image<MB, PR>(p, blockIdx.x, threadIdx.x, L);
+    beam_select_image<MB, PR, DT>(p, blockIdx.x, threadIdx.x, L);
 }
 
-template <bool PR>
+template <bool PR, bool DT = false>
 static int select_launch(const int32_t* pick_idx, const float* pick_val, int32_t* tokens, int tok_ld,
                          float* vals, uint8_t* ended, int32_t* src, int src_ld, int32_t* parent,
                          int32_t* hparent, uint8_t* done, int32_t* end_step, int n_img, int beam,
@@ -1165,13 +1178,13 @@ static int select_launch(const int32_t* pick_idx, const float* pick_val, int32_t
     DH_REQUIRE(n_img > 0 && beam >= 1 && beam <= DH_BEAM_MAX_BEAMS && tok_ld > 0 && t >= 0 && temperature > 0.f);
     DH_REQUIRE(!src || src_ld > t);
     DH_REQUIRE(!PR || first_pos);
-    DhProfScope prof("dh_beam_select", 0.0, 0.0, stream);
+    DhProfScope prof(DT ? "dh_beam_select_best" : "dh_beam_select", 0.0, 0.0, stream);
     SelectParams p{pick_idx, pick_val, tokens, tok_ld, vals, ended, src, src_ld, parent, hparent, done, end_step,
                    beam, first, first_sets_ended, write_pos, t, step_index, eos_index, img0, temperature, noise, seed, seed_ptr, first_pos};
     const size_t lds = (size_t)beam * (tok_ld + (src ? t : 0)) * sizeof(int32_t);
     DH_REQUIRE(lds <= 56 * 1024);                         // beam * (tok_ld + t) ints of staging next to the candidate arrays
-    if (beam <= 16) hipLaunchKernelGGL((beam_select_kernel<16, PR>), dim3(n_img), dim3(64), lds, (hipStream_t)stream, p);
-    else hipLaunchKernelGGL((beam_select_kernel<DH_BEAM_MAX_BEAMS, PR>), dim3(n_img), dim3(64), lds, (hipStream_t)stream, p);   // beam.py:7-9: any beam_size <= top_k
+    if (beam <= 16) hipLaunchKernelGGL((beam_select_kernel<16, PR, DT>), dim3(n_img), dim3(64), lds, (hipStream_t)stream, p);
+    else hipLaunchKernelGGL((beam_select_kernel<DH_BEAM_MAX_BEAMS, PR, DT>), dim3(n_img), dim3(64), lds, (hipStream_t)stream, p);   // beam.py:7-9: any beam_size <= top_k
     DH_LAUNCH_CHECK();
 }
 
@@ -1195,6 +1208,22 @@ extern "C" int dh_beam_select_prompted(const int32_t* pick_idx, const float* pic
     return select_launch<true>(pick_idx, pick_val, tokens, tok_ld, vals, ended, src, src_ld, parent, hparent, done, end_step, n_img, beam,
                                0, first_pos, first_sets_ended, write_pos, t, step_index, temperature, eos_index, noise, seed, seed_ptr, img0,
                                stream);
+}
+
+// The deterministic select of search="beam" (the DT instantiations): dense with first_pos == NULL and the launch-wide `first`, prompted
+// with first_pos (`first` is not read then).  No noise, no seed, no temperature: the rank is on the fp32 scores themselves.
+extern "C" int dh_beam_select_best(const int32_t* pick_idx, const float* pick_val, int32_t* tokens, int tok_ld,
+                                   float* vals, uint8_t* ended, int32_t* src, int src_ld, int32_t* parent,
+                                   int32_t* hparent, uint8_t* done, int32_t* end_step, int n_img, int beam,
+                                   int first, const int32_t* first_pos, int first_sets_ended, int write_pos, int t, int step_index,
+                                   int eos_index, void* stream) {
+    if (first_pos)
+        return select_launch<true, true>(pick_idx, pick_val, tokens, tok_ld, vals, ended, src, src_ld, parent, hparent, done, end_step, n_img,
+                                         beam, 0, first_pos, first_sets_ended, write_pos, t, step_index, 1.f, eos_index, nullptr, 0ull, nullptr,
+                                         0, stream);
+    return select_launch<false, true>(pick_idx, pick_val, tokens, tok_ld, vals, ended, src, src_ld, parent, hparent, done, end_step, n_img,
+                                      beam, first, nullptr, first_sets_ended, write_pos, t, step_index, 1.f, eos_index, nullptr, 0ull, nullptr,
+                                      0, stream);
 }
 
 // ---- the reference's METHOD surface (deephumor/models/beam.py:32-108), one kernel per method ------------------------------------

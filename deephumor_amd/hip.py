@@ -926,6 +926,36 @@ def beam_row_sample_nucleus(logits, v, rows, rows_per_img, beam, top_k, top_p, t
             _ptr(pick_idx), _ptr(pick_val), _ptr(err), _stream())
 
 
+def beam_row_best(logits, v, rows, rows_per_img, beam, temperature, unk_index, step, pick_idx, pick_val, err, group_max=None,
+                  first_pos=None):
+    """``dh_beam_row_best``, the row step of ``search="beam"``: per row of fp32 ``logits [rows, V]`` the ``beam`` columns with the largest
+    logit (never ``unk_index``; equal logits to the lower index) into ``pick_idx`` and their log-probabilities ``x / temperature -
+    logsumexp(x / temperature)`` into ``pick_val``, both ``[rows, beam]``.  No noise.  ``group_max``: the 64-column group maxima, which
+    spare the second look at the whole row; ``first_pos`` (int32 ``[rows // beam]``): the prompted phases at position ``step``."""
+    _dev(logits, pick_idx, pick_val, err, first_pos, group_max)
+    assert logits.dtype == torch.float32 and logits.stride(1) == 1 and pick_idx.dtype == torch.int32 and pick_val.dtype == torch.float32
+    assert pick_idx.is_contiguous() and pick_val.is_contiguous() and pick_idx.numel() >= rows * beam and pick_val.numel() >= rows * beam
+    assert logits.shape[0] >= rows and logits.shape[1] >= v
+    assert group_max is None or (group_max.dtype == torch.float32 and group_max.stride(1) == 1 and group_max.shape[0] >= rows
+                                 and group_max.shape[1] >= n_groups(v))
+    assert first_pos is None or (first_pos.dtype == torch.int32 and rows_per_img == beam and first_pos.numel() * beam == rows)
+    _launch("dh_beam_row_best", _ptr(logits), logits.stride(0), v, _ptr(group_max), group_max.stride(0) if group_max is not None else 0,
+            n_groups(v), GROUP_COLS, rows, rows_per_img, beam, float(temperature), unk_index, step, _ptr(first_pos), _ptr(pick_idx),
+            _ptr(pick_val), _ptr(err), _stream())
+
+
+def beam_select_best(pick_idx, pick_val, tokens, vals, ended, src, parent, hparent, done, end_step, n_img, beam, first, first_sets_ended,
+                     write_pos, t, step_index, eos_index, first_pos=None):
+    """``dh_beam_select_best``, the select step of ``search="beam"``: ``beam_select`` / ``beam_select_prompted`` (with ``first_pos``, int32
+    ``[n_img]``; ``first`` is then not read) keeping the ``beam`` candidates with the largest score instead of drawing among them; equal
+    scores to the lower candidate index.  ``hparent`` becomes the real parent row.  No noise, no seed, no temperature."""
+    _dev(pick_idx, pick_val, tokens, vals, ended, src, parent, hparent, done, end_step, first_pos)
+    assert first_pos is None or (first_pos.dtype == torch.int32 and first_pos.numel() == n_img)
+    _launch("dh_beam_select_best", _ptr(pick_idx), _ptr(pick_val), _ptr(tokens), tokens.stride(0), _ptr(vals), _ptr(ended), _ptr(src),
+            src.stride(0) if src is not None else 0, _ptr(parent), _ptr(hparent), _ptr(done), _ptr(end_step), n_img, beam, int(first),
+            _ptr(first_pos), int(first_sets_ended), write_pos, t, step_index, eos_index, _stream())
+
+
 def beam_history_logits(logits, v, tokens, tok_row_mult, pos, rows, rows_per_img, ngram, penalty, group_max=None, first_pos=None):
     """``dh_beam_history_logits``: the ``no_repeat_ngram_size`` / ``repetition_penalty`` edits of fp32 ``logits [rows, V]`` in place,
     from every row's own history ``tokens[r * tok_row_mult, :pos]`` (int32); with ``group_max`` the 64-column group maxima of every

@@ -38,7 +38,11 @@ class BeamCaptions(NamedTuple):
 
     ``scores`` are re-normalised over the drawn candidates at every step (``log_softmax`` over each row's ``B`` picks, reference
     beam.py:79): they order the beams the way the search does, but are NOT model log-probabilities --
-    ``experiments.rank_beams`` ranks by those."""
+    ``experiments.rank_beams`` ranks by those.
+
+    Under ``search="beam"`` nothing is drawn and nothing is re-normalised: ``scores`` ARE the beams' cumulative model log-probabilities
+    (the sum over the beam's generated tokens of ``log_softmax(logits / temperature)``, history edits and bans applied), slot 0 is the
+    caption the plain call returns and ``drawn`` is 0 for every image."""
     tokens: torch.Tensor
     lengths: torch.Tensor
     scores: torch.Tensor
@@ -97,6 +101,23 @@ def check_top_p(top_p):
     if math.isnan(top_p) or not 0.0 < top_p <= 1.0:
         raise ValueError(f"top_p must lie in (0, 1], got {top_p}")
     return top_p
+
+
+SEARCHES = ("sample", "beam")
+
+
+def check_search(search, top_p=1.0):
+    """``search`` is the ``str`` ``"sample"`` (the reference's sampled search, the default) or ``"beam"`` (the ``beam_size`` most likely
+    continuations, no noise): anything that is not a ``str`` is a ``TypeError``, another string a ``ValueError`` that names the two.
+    ``"beam"`` with ``top_p < 1`` is a ``ValueError``: a nucleus restricts a draw, and nothing is drawn there.  Returns it."""
+    if not isinstance(search, str):
+        raise TypeError(f'search must be "sample" or "beam", not {type(search).__name__}')
+    if search not in SEARCHES:
+        raise ValueError(f'search must be "sample" or "beam", got {search!r}')
+    if search == "beam" and top_p < 1.0:
+        raise ValueError(f'search="beam" keeps the most likely tokens and draws nothing: top_p={top_p} (a nucleus) has no meaning there -- '
+                         "use top_p=1.0")
+    return search
 
 
 def check_repeat(no_repeat_ngram_size=0, repetition_penalty=1.0, max_len=None):
@@ -256,7 +277,8 @@ def compile_bad_words(ids, num_tokens=None, device="cuda"):
 class DecodeSettings:
     """The validated decode settings of one call -- ``return_beams``, ``return_attention``, ``top_p``, ``no_repeat_ngram_size``,
     ``repetition_penalty``, ``min_len``, ``bad_words_ids`` -- as the ``check_*`` functions return them (``bad_words_ids``: ``None``, a
-    tuple of tuples, or a ``BadWords``), and ``num_tokens``, the vocabulary the list was checked against.  Built by ``from_kw``
+    tuple of tuples, or a ``BadWords``), ``num_tokens``, the vocabulary the list was checked against, and ``search`` (``check_search``;
+    behind ``num_tokens`` and with a default, so the positional order of the others is what it was).  Built by ``from_kw``
     only.  Immutable; equal and hashed by the settings, the list by its ids whether compiled or not."""
     return_beams: bool = False
     return_attention: bool = False
@@ -266,22 +288,24 @@ class DecodeSettings:
     min_len: int = 0
     bad_words_ids: object = None
     num_tokens: object = None
+    search: str = "sample"
 
     @classmethod
     def from_kw(cls, kw, max_len, num_tokens=None, model=None):
-        """Reads the seven settings out of the keyword dictionary ``kw`` (which keeps them) and checks them in this order, so a call
-        with two bad values raises for the earlier one; ``model``: see ``check_return_attention``."""
+        """Reads the settings out of the keyword dictionary ``kw`` (which keeps them) and checks them in this order -- ``search``
+        last --, so a call with two bad values raises for the earlier one; ``model``: see ``check_return_attention``."""
         return_beams = check_return_beams(kw.get("return_beams", False))
         return_attention = check_return_attention(kw.get("return_attention", False), model)
         top_p = check_top_p(kw.get("top_p", 1.0))
         ngram, penalty = check_repeat(kw.get("no_repeat_ngram_size", 0), kw.get("repetition_penalty", 1.0), max_len)
         min_len, bad_words = check_constraints(kw.get("min_len", 0), kw.get("bad_words_ids"), max_len, num_tokens)
-        return cls(return_beams, return_attention, top_p, ngram, penalty, min_len, bad_words, num_tokens)
+        search = check_search(kw.get("search", "sample"), top_p)
+        return cls(return_beams, return_attention, top_p, ngram, penalty, min_len, bad_words, num_tokens, search)
 
     def _key(self):
         bw = self.bad_words_ids
         return (self.return_beams, self.return_attention, self.top_p, self.no_repeat_ngram_size, self.repetition_penalty, self.min_len,
-                bw.ids if isinstance(bw, BadWords) else bw)
+                bw.ids if isinstance(bw, BadWords) else bw, self.search)
 
     def __eq__(self, other):
         return isinstance(other, DecodeSettings) and self._key() == other._key()
@@ -296,7 +320,7 @@ class DecodeSettings:
     def new_helper(self, **engine_args):
         """The ``BeamSearchHelper`` of one session with every setting applied; ``engine_args``: the constructor's other arguments."""
         return BeamSearchHelper(top_p=self.top_p, no_repeat_ngram_size=self.no_repeat_ngram_size, repetition_penalty=self.repetition_penalty,
-                                **engine_args).set_constraints(self.min_len, self.bad_words_ids)
+                                **engine_args).set_constraints(self.min_len, self.bad_words_ids).set_search(self.search)
 
 
 class BeamOverflow(RuntimeError):
@@ -464,6 +488,18 @@ class BeamSearchHelper:
     are repaired on the same condition as above.  A launch is made only when the list is not empty or ``write_pos < min_len``; the
     defaults ``0`` / ``None`` make none.  Both are set with ``helper.set_constraints(min_len=, bad_words_ids=)`` after construction
     (``bad_words_ids``: the raw nesting, compiled there by ``compile_bad_words``, or a ``BadWords``).
+
+    ``search="beam"`` (not in the reference either; ``helper.set_search("beam")`` after construction): nothing is drawn.  Behind the
+    history edits and the bans every live row keeps the ``beam_size`` columns with the largest logit (never ``unk_index``; equal
+    logits to the lower index), each with its log-probability ``x / temperature - logsumexp(x / temperature)`` over the whole row
+    (``dh_beam_row_best``); per image the ``beam_size`` candidates with the largest cumulative score stay, equal scores to the lower
+    candidate index (``dh_beam_select_best``: ``hparent`` is the real parent row there, and the first step sets ``ended`` from
+    ``<eos>`` for every decoder kind); ``finalize`` returns the beam with the largest score.  ``top_k`` keeps its assertion and has no
+    other effect; ``seed``, ``noise_source`` and ``exact`` have none: no noise is generated or consumed, two calls return the same
+    bits, and there is no overflow case.  ``vals`` -- ``BeamCaptions.scores`` -- are cumulative model log-probabilities of the tokens
+    the rows hold: a step that writes no token column (``write_pos`` past the table: the Transformer decoders' last) is skipped.  Length
+    normalisation is out of scope: ``return_beams=True`` plus ``experiments.rank_beams`` re-ranks.  All launch constants, so it
+    captures into a hipGraph like the rest.
     """
 
     def __init__(self, temperature=1.0, beam_size=10, top_k=50, unk_index=1, eos_index=3, device='cuda',
@@ -474,6 +510,7 @@ class BeamSearchHelper:
         self.no_repeat_ngram_size, self.repetition_penalty = check_repeat(no_repeat_ngram_size, repetition_penalty, max_len)
         self._history_edits = self.no_repeat_ngram_size > 0 or self.repetition_penalty != 1.0
         self.min_len, self.bad_words, self._constraints = 0, None, False      # min_len / bad_words_ids: set_constraints
+        self.search = "sample"            # "beam": set_search
         self.exact = bool(exact)          # row draws through the general sampler only (see BeamOverflow)
         if beam_size > hip.MAX_BEAMS:     # one wave draws among an image's beams (dh_beam_finalize); the reference has no limit
             raise ValueError(f"beam_size <= {hip.MAX_BEAMS} supported")
@@ -524,6 +561,12 @@ class BeamSearchHelper:
         self._constraints = self.min_len > 0 or self.bad_words is not None
         return self
 
+    def set_search(self, search):
+        """``search`` of this session (see the class docstring), validated by ``check_search`` against the helper's ``top_p``.  A method
+        like ``set_constraints``: the constructor's parameter list stays as it is.  Returns the helper."""
+        self.search = check_search(search, self.top_p)
+        return self
+
     def set_prefix(self, caption):
         """caption int64 [n_img, p]: teacher-forced beginning, copied to every beam row."""
         p = caption.shape[1]
@@ -550,7 +593,7 @@ class BeamSearchHelper:
         """One beam step of a prompted batch from ``logits [n_img*beam, V]`` at absolute position ``step_index``: per image forced
         (``step_index < first_pos``: nothing happens), first (``==``: ``step(first=True)`` from the image's base row) or normal
         (``>``: ``step(first=False)``) -- ``dh_beam_row_sample*_prompted`` + ``dh_beam_select_prompted``.  Philox noise only."""
-        assert self.noise_source is None
+        assert self.noise_source is None or self.search == "beam"
         self._draw_and_select(logits, False, write_pos, t, step_index, first_sets_ended, group_max, prompted=True)
 
     def _noise(self, kind, step, shape, ld=None):
@@ -577,11 +620,16 @@ class BeamSearchHelper:
         b = self.beam_size
         rpi = 1 if first else b
         assert rows == self.n_img * rpi
+        best = self.search == "beam"      # (its row step takes the maxima whenever they are there: it filters nothing by top_k)
+        if best and write_pos >= self.tokens.shape[1]:
+            # the Transformer decoders' last step writes no token (transformers.py:557) and only re-draws the beams: here it would add
+            # the log-probability of a token no caption holds to every live score, so it makes no launch
+            return
         mult = b if first else 1          # the token table's row of logits row r: a first step's compact rows sit at img * beam
         first_pos = self.first_pos if prompted else None
         # the general sampler reads the whole row; otherwise k group maxima bound the k-th logit.  Decided ONCE: the history pass and
         # the bans repair the maxima exactly when the sampler below reads them
-        gm = group_max if (group_max is not None and not self.exact and self.top_k <= hip.n_groups(v)) else None
+        gm = group_max if (group_max is not None and (best or (not self.exact and self.top_k <= hip.n_groups(v)))) else None
         if self._history_edits:           # no_repeat_ngram_size / repetition_penalty: the row's own history edits its logits first
             hip.beam_history_logits(logits, v, self.tokens, mult, write_pos, rows, rpi, self.no_repeat_ngram_size,
                                     self.repetition_penalty, group_max=gm, first_pos=first_pos)
@@ -592,6 +640,13 @@ class BeamSearchHelper:
             hip.beam_constrain_logits(logits, v, self.tokens, mult, write_pos, rows, rpi, self.eos_index, self.min_len,
                                       None if bw is None else bw.words, None if bw is None else bw.offsets, 0 if bw is None else len(bw),
                                       group_max=gm, first_pos=first_pos)
+        if best:                          # search="beam": the most likely tokens and candidates, no noise anywhere
+            hip.beam_row_best(logits, v, rows, rpi, b, self.temperature, self.unk_index, step_index, self.pick_idx, self.pick_val, self.err,
+                              group_max=gm, first_pos=first_pos)
+            hip.beam_select_best(self.pick_idx, self.pick_val, self.tokens, self.vals, self._ended, self.src, self.parent, self.hparent,
+                                 self.done, self.end_step, self.n_img, b, first, True, write_pos, t, step_index, self.eos_index,
+                                 first_pos=first_pos)
+            return
         noise = self._noise("row", step_index, (rows, v), logits.stride(0))       # (None in a prompted session: Philox only)
         draw = (self.seed, self.img0, step_index, self.pick_idx, self.pick_val, self.err)
         if self.top_p < 1.0:              # the nucleus of the survivors: one entry point for the three routes below
@@ -630,13 +685,18 @@ class BeamSearchHelper:
         ``attn_w`` (``return_attention``; fp32 ``[n_pos, rows, S]``, slab ``c`` = the maps position ``c`` wrote at its logical rows):
         always the ``beams`` launch, and one launch of ``dh_beam_gather_attention`` behind it leaves every kept beam's maps -- read
         through ``self.src``, for the columns below the beam's own length, zero elsewhere -- in the result's ``attention``, fp32
-        ``[n_img, beam, max_len, S]``; its ``captions`` are those of ``beams=True``."""
-        if first_beam:                 # the kernel's race p / noise with an infinite handicap on every beam but the first
+        ``[n_img, beam, max_len, S]``; its ``captions`` are those of ``beams=True``.
+        ``search="beam"``: no draw and no noise -- always the ``beams`` launch, whose slot 0 is the beam with the largest score (equal
+        scores: the lower engine index); ``drawn`` is 0 for every image and the plain pair is slot 0's row and ``row_lengths``."""
+        best = self.search == "beam"
+        if best:
+            noise = None
+        elif first_beam:                 # the kernel's race p / noise with an infinite handicap on every beam but the first
             noise = torch.full((self.n_img, self.beam_size), float("inf"), dtype=torch.float32, device=self.device)
             noise[:, 0] = 1.0
         else:
             noise = self._noise("final", 0, (self.n_img, self.beam_size))
-        if beams or attn_w is not None:
+        if beams or attn_w is not None or best:
             n, b, dev = self.n_img, self.beam_size, self.device
             out = torch.empty((n, b, self.max_len), dtype=torch.int32, device=dev)
             ints = torch.empty((2 * n * b + 2 * n,), dtype=torch.int32, device=dev)
@@ -649,7 +709,11 @@ class BeamSearchHelper:
             if attn_w is not None:
                 attention = torch.empty((n, b, self.max_len, attn_w.shape[2]), dtype=torch.float32, device=dev)
                 hip.beam_gather_attention(attn_w, self.src, o_idx, o_len, attention)
+            if best:
+                o_drawn.zero_()           # (the kernel's draw among the beams is not this search's: slot 0, the best score, is returned)
             captions = BeamCaptions(out.long(), o_len.long(), o_score, o_idx.long(), o_drawn.long(), o_row.long())
+            if best and not beams and attn_w is None:
+                captions = (captions.tokens[:, 0], captions.row_lengths)
         else:
             attention = None
             out = torch.empty((self.n_img, self.max_len), dtype=torch.int32, device=self.device)
@@ -715,6 +779,9 @@ class BeamSearchHelper:
         if self._constraints:
             raise NotImplementedError(f"{what} with min_len / bad_words_ids: the bans live in the batched engine's row draw (step / "
                                       "step_prompted); the reference-style method surface has none")
+        if self.search == "beam":
+            raise NotImplementedError(f'{what} with search="beam": the deterministic search lives in the batched engine\'s steps (step / '
+                                      "step_prompted); the reference-style method surface draws")
         if self.top_p < 1.0:
             raise NotImplementedError(f"{what} with top_p < 1: the nucleus lives in the batched engine's row draw (step / step_prompted); "
                                       "the reference-style method surface has none")

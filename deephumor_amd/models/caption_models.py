@@ -54,6 +54,8 @@ class _CaptioningBase(nn.Module):
         """Batched beam-search decoding of ``encode``'s output -> ``(tokens [N, max_len], lengths [N])``, or with
         ``return_beams=True`` every beam of every image as a ``beam.BeamCaptions`` (``LSTMDecoder.generate_batch``).
         ``top_p``, ``no_repeat_ngram_size`` / ``repetition_penalty``, ``min_len`` / ``bad_words_ids`` (in ``kw``): see there.
+        ``search="beam"`` (in ``kw``; default ``"sample"``, the call without it): the deterministic search -- the ``beam_size`` most
+        likely continuations, the same caption on every call, ``BeamCaptions.scores`` that are model log-probabilities (see there).
         ``caption_lengths`` (keyword only, int64 / int32 ``[N]``): a prompt of its own length per image -- row ``i`` is
         teacher-forced with ``caption[i, :caption_lengths[i]]`` (0: none; the rest of the row is ignored) and equals the dense
         single-image call with that prompt and ``img0 + i`` (``LSTMDecoder.generate_batch``).
@@ -84,7 +86,8 @@ class _CaptioningBase(nn.Module):
         if getattr(self.decoder, "pad_index", 0) == 1:
             raise NotImplementedError("caption_lengths with pad_index == 1: that decoder re-runs the whole sequence per token on the "
                                       "module path, which has no per-image prompt phase")
-        prompts_need_philox(kw.get("rng"), kw.get("noise_source"))
+        if settings.search != "beam":     # (search="beam" draws nothing: rng / noise_source are accepted and unused)
+            prompts_need_philox(kw.get("rng"), kw.get("noise_source"))
         lens = torch.as_tensor(caption_lengths)
         if not (lens.is_cuda and (kw.get("defer_check") or torch.cuda.is_current_stream_capturing())):
             return check_prompts(caption, lens, max_len, self._hp["num_tokens"])      # on the host from here on: the decoder's own
@@ -121,7 +124,8 @@ class _CaptioningBase(nn.Module):
         step), so one graph serves every set of lengths of that shape and returns what eager returns for them."""
         # every decode setting rides in ``kw`` and so is part of the cache key below: the graph of ``return_beams=True`` (it ends in
         # dh_beam_finalize_beams), of ``return_attention=True`` (one dh_attn_cross_weights node per position and the gather behind the
-        # final draw), of ``top_p < 1`` (nucleus row draws), of the repeat controls and of ``min_len`` / ``bad_words_ids`` (one
+        # final draw), of ``top_p < 1`` (nucleus row draws), of ``search="beam"`` (dh_beam_row_best / dh_beam_select_best nodes), of the
+        # repeat controls and of ``min_len`` / ``bad_words_ids`` (one
         # dh_beam_history_logits / dh_beam_constrain_logits node per position that edits something; the position is a launch constant)
         # each lives beside the plain one of the same shapes, and a replay returns clones of every field
         settings = DecodeSettings.from_kw(kw, kw.get("max_len", 25), self._hp["num_tokens"], self)
@@ -132,13 +136,15 @@ class _CaptioningBase(nn.Module):
         # tensors alive
         if "bad_words_ids" in kw:
             kw["bad_words_ids"] = settings.compiled(inputs[0].device).bad_words_ids
-        if kw.get("rng") == "torch":      # host-generated noise (parity mode): nothing to replay
+        if settings.search == "sample":
+            kw.pop("search", None)                    # (the default is the call without the keyword: the plain graph, not a second one)
+        if kw.get("rng") == "torch" and settings.search != "beam":      # host-generated noise (parity mode): nothing to replay
             return self.generate_batch(*inputs, caption=caption, seed=seed, caption_lengths=caption_lengths, **kw)
         if caption_lengths is not None:
             caption_lengths = self._check_prompts(caption, torch.as_tensor(caption_lengths).cpu(), kw.get("max_len", 25), kw)
             caption_lengths = caption_lengths.to(device=inputs[0].device, dtype=torch.int32)
             caption = caption.to(inputs[0].device)
-        seed = resolve_seed(seed)
+        seed = 0 if settings.search == "beam" else resolve_seed(seed)     # (nothing is drawn there: the default generator is not read)
         # ids are looked up without bounds tests and nothing can be read back inside a capture: the caption prefix and integer inputs
         # (labels) are range-checked here, in front of the capture / replay (beam.check_ids: nn.Embedding's IndexError)
         dec = getattr(self, "decoder", None)

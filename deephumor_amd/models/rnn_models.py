@@ -22,7 +22,7 @@ from .encoders import _Planned
 def _later_keywords(*names):
     """Decorator of ``LSTMDecoder.generate_batch``: the method keeps the parameter list it had (positional order, keyword-only tail
     ending at ``repetition_penalty``), and the keyword-only controls added since -- ``names`` -- are accepted by name here and go to
-    ``self._generate_batch`` together with everything else.  A call without them is the method's own body."""
+    ``self._decode_batch``, the implementation, together with everything else.  A call without them is the method's own body."""
     import functools
 
     def deco(fn):
@@ -31,7 +31,7 @@ def _later_keywords(*names):
             later = {k: kw.pop(k) for k in names if k in kw}
             if not later:
                 return fn(self, *args, **kw)
-            return self._generate_batch(*args, **kw, **later)
+            return self._decode_batch(*args, **kw, **later)
         return generate_batch
     return deco
 
@@ -190,7 +190,7 @@ class LSTMDecoder(_Planned, nn.Module):
         hs.mul_(valid[..., None])          # pad_packed_sequence zero rows (mask, not arithmetic on valid rows)
         return hs, bs, steps_out
 
-    @_later_keywords("min_len", "bad_words_ids")
+    @_later_keywords("min_len", "bad_words_ids", "search")
     def generate_batch(self, image_emb, caption=None, max_len=25, temperature=1.0, beam_size=10, top_k=50,
                        eos_index=3, seed=None, img0=0, noise_source=None, logits_hook=None, streams=1, seed_tensor=None,
                        defer_check=False, early_stop_every=0, exact=False, rng=None, *, caption_lengths=None, return_beams=False, top_p=1.0,
@@ -234,9 +234,18 @@ class LSTMDecoder(_Planned, nn.Module):
         edits and in front of the row draw, only at positions where there is something to ban; ``logits_hook`` still sees the raw
         logits.  ``0`` / ``None``, the defaults, are the call without the keywords: same launches, same bits.  All validation:
         ``beam.check_constraints``.
-        ``min_len`` and ``bad_words_ids`` are not in the parameter list above, which ends at ``repetition_penalty`` as it did: they
-        are taken by name (``_later_keywords``) and handed to ``_generate_batch``, the implementation, which spells every keyword
-        out."""
+        ``search`` (keyword only, ``"sample"`` or ``"beam"``; ``beam.check_search``): ``"sample"``, the default, is the call without
+        the keyword -- same launches, same bits.  ``"beam"`` is the deterministic search: every row keeps its ``beam_size`` most
+        likely tokens (after the history edits and the bans; never ``<unk>``), every image the ``beam_size`` candidates with the
+        largest cumulative log-probability, and the caption returned is the beam with the largest one -- the same on every call,
+        whatever ``seed``, ``rng`` and ``noise_source`` are (accepted, unused: no noise is generated or consumed).  ``top_k`` keeps
+        its assertion ``beam_size <= top_k`` and filters nothing; ``top_p < 1`` is a ``ValueError``.  With ``return_beams=True`` the
+        ``scores`` are cumulative model log-probabilities and ``drawn`` is 0.  Two launches per position (``dh_beam_row_best``,
+        ``dh_beam_select_best``) in place of the sampled pair (``BeamSearchHelper``).  No length normalisation: ``return_beams=True``
+        plus ``experiments.rank_beams`` re-ranks.
+        ``min_len``, ``bad_words_ids`` and ``search`` are not in the parameter list above, which ends at ``repetition_penalty`` as it
+        did: they are taken by name (``_later_keywords``) and handed to ``_decode_batch``, the implementation, which spells every
+        keyword out."""
         return self._generate_batch(image_emb, caption, max_len, temperature, beam_size, top_k, eos_index, seed, img0, noise_source,
                                     logits_hook, streams, seed_tensor, defer_check, early_stop_every, exact, rng,
                                     caption_lengths=caption_lengths, return_beams=return_beams, top_p=top_p,
@@ -247,10 +256,25 @@ class LSTMDecoder(_Planned, nn.Module):
                         eos_index=3, seed=None, img0=0, noise_source=None, logits_hook=None, streams=1, seed_tensor=None,
                         defer_check=False, early_stop_every=0, exact=False, rng=None, *, caption_lengths=None, return_beams=False, top_p=1.0,
                         no_repeat_ngram_size=0, repetition_penalty=1.0, min_len=0, bad_words_ids=None):
-        """``generate_batch`` with its keyword-only tail written out."""
+        """``generate_batch`` with its keyword-only tail up to ``bad_words_ids`` written out: this parameter list is what it was, and
+        ``_decode_batch`` behind it takes the keywords added since."""
+        return self._decode_batch(image_emb, caption, max_len, temperature, beam_size, top_k, eos_index, seed, img0, noise_source,
+                                  logits_hook, streams, seed_tensor, defer_check, early_stop_every, exact, rng,
+                                  caption_lengths=caption_lengths, return_beams=return_beams, top_p=top_p,
+                                  no_repeat_ngram_size=no_repeat_ngram_size, repetition_penalty=repetition_penalty, min_len=min_len,
+                                  bad_words_ids=bad_words_ids)
+
+    @f32x_guarded
+    def _decode_batch(self, image_emb, caption=None, max_len=25, temperature=1.0, beam_size=10, top_k=50,
+                      eos_index=3, seed=None, img0=0, noise_source=None, logits_hook=None, streams=1, seed_tensor=None,
+                      defer_check=False, early_stop_every=0, exact=False, rng=None, *, caption_lengths=None, return_beams=False, top_p=1.0,
+                      no_repeat_ngram_size=0, repetition_penalty=1.0, min_len=0, bad_words_ids=None, search="sample"):
+        """The implementation of ``generate_batch``, every keyword spelled out."""
         settings = DecodeSettings.from_kw(dict(return_beams=return_beams, top_p=top_p, no_repeat_ngram_size=no_repeat_ngram_size,
-                                               repetition_penalty=repetition_penalty, min_len=min_len, bad_words_ids=bad_words_ids),
-                                          max_len, self.num_tokens)
+                                               repetition_penalty=repetition_penalty, min_len=min_len, bad_words_ids=bad_words_ids,
+                                               search=search), max_len, self.num_tokens)
+        if settings.search == "beam":     # nothing is drawn: no generator is read, no noise source is asked
+            rng, noise_source, seed = None, None, 0
         self._check_mode()
         plan = self._get_plan()
         classifier_must_be_finite(plan)
@@ -347,7 +371,7 @@ class LSTMDecoder(_Planned, nn.Module):
                  temperature=1.0, beam_size=10, top_k=50, eos_index=3, **kw):
         """Single-image API of the reference (rnn_models.py:48-49): ``image_emb [1, 1, E]`` ->
         1-D int64 token tensor; with ``return_beams=True`` the image's ``BeamCaptions`` (``N = 1``, nothing squeezed).  ``top_p``,
-        ``no_repeat_ngram_size``, ``repetition_penalty``, ``min_len``, ``bad_words_ids`` (in ``kw``): see ``generate_batch``."""
+        ``no_repeat_ngram_size``, ``repetition_penalty``, ``min_len``, ``bad_words_ids``, ``search`` (in ``kw``): see ``generate_batch``."""
         res = self.generate_batch(image_emb, caption=caption, max_len=max_len, temperature=temperature,
                                   beam_size=beam_size, top_k=top_k, eos_index=eos_index, **kw)
         return self.single_output(res, caption, max_len, beam_size)

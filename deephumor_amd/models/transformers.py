@@ -541,10 +541,13 @@ class _IncrementalDecoder(_Planned, nn.Module):
     def _generate_batch(self, start_emb, enc_out, caption, max_len, temperature, beam_size, top_k, eos_index,
                         seed=None, img0=0, noise_source=None, logits_hook=None, streams=1, seed_tensor=None,
                         defer_check=False, early_stop_every=0, exact=False, rng=None, caption_lengths=None, return_beams=False, top_p=1.0,
-                        no_repeat_ngram_size=0, repetition_penalty=1.0, min_len=0, bad_words_ids=None, return_attention=False):
+                        no_repeat_ngram_size=0, repetition_penalty=1.0, min_len=0, bad_words_ids=None, return_attention=False,
+                        search="sample"):
         settings = DecodeSettings.from_kw(dict(return_beams=return_beams, return_attention=return_attention, top_p=top_p,
                                                no_repeat_ngram_size=no_repeat_ngram_size, repetition_penalty=repetition_penalty,
-                                               min_len=min_len, bad_words_ids=bad_words_ids), max_len, self.num_tokens, self)
+                                               min_len=min_len, bad_words_ids=bad_words_ids, search=search), max_len, self.num_tokens, self)
+        if settings.search == "beam":     # nothing is drawn: no generator is read, no noise source is asked
+            rng, noise_source, seed = None, None, 0
         self._check_mode()
         plan = self._get_plan()
         classifier_must_be_finite(plan)
@@ -672,7 +675,7 @@ class TransformerDecoder(_IncrementalDecoder):
                        top_k=50, eos_index=3, *, caption_lengths=None, **kw):
         """``start_emb [N, D]``, ``enc_out [N, S, D]`` -> ``(tokens [N, max_len], lengths [N])``.  ``caption_lengths`` (keyword only):
         a prompt of its own length per image; ``return_beams``, ``top_p``, ``no_repeat_ngram_size`` / ``repetition_penalty``, ``min_len`` /
-        ``bad_words_ids`` (in ``kw``): see ``LSTMDecoder.generate_batch`` for all;
+        ``bad_words_ids``, ``search`` (in ``kw``): see ``LSTMDecoder.generate_batch`` for all;
         ``return_attention=True`` (in ``kw``): one more result, the fp32 map of where every token looked -- ``attention [N, T, S]``
         behind the pair, or ``[N, B, T, S]`` behind the ``BeamCaptions`` -- see ``caption_models._CaptioningBase.decode``."""
         return self._generate_batch(start_emb, enc_out, caption, max_len, temperature, beam_size, top_k,

@@ -39,6 +39,7 @@ def u8_preprocess(model, size=(224, 224)):
 class CaptionPipeline:
     def __init__(self, model, overlap=True, preprocess=None, **gen_kw):
         """``return_beams=True`` (one of ``gen_kw``): every batch comes out as a ``beam.BeamCaptions`` instead of the pair.
+        ``search="beam"`` (one of ``gen_kw``): every batch is decoded by the deterministic search (``LSTMDecoder.generate_batch``).
         ``preprocess``: optional callable mapping the staged device tensors of a batch to ``model.encode``'s inputs
         (e.g. ``u8_preprocess(model)``); it runs on the encode stream in front of the encoder.  ``gen_kw`` goes to every batch's
         ``model.decode`` unchanged: ``caption`` -- and with it ``caption_lengths``, one prompt length per image -- is per pipeline,
@@ -72,6 +73,8 @@ class CaptionPipeline:
         self._async = getattr(getattr(model, "decoder", None), "pad_index", 0) != 1
         # return_beams=True (in gen_kw): every batch is yielded as a beam.BeamCaptions (to_host: its fields in pinned memory)
         self._beams = settings.return_beams
+        # search="beam" (in gen_kw) draws nothing: no seed is resolved for it, so torch's default generator is left alone
+        self._search = settings.search
 
     # -- stages ------------------------------------------------------------------------------------------------------
     def _stage(self, host_inputs):
@@ -124,7 +127,9 @@ class CaptionPipeline:
         """Queues the decode of one batch on the decode stream and returns WITHOUT waiting for it: the beam engine's error word is
         not read here (``defer_check``) but copied to pinned memory behind the token ids and examined by ``_finish`` once the
         batch's event has fired."""
-        if self.gen_kw.get("rng") != "torch":
+        if self._search == "beam":
+            seed = 0
+        elif self.gen_kw.get("rng") != "torch":
             seed = resolve_seed(seed)                 # fixed now: a repeated decode (BeamOverflow) must draw the same noise
         with torch.cuda.stream(self.dec_s), torch.no_grad():
             self.dec_s.wait_event(ev)

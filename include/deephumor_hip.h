@@ -546,6 +546,43 @@ int dh_beam_row_sample_nucleus(const float* logits, int ldl, int V, const float*
                                int img0, int step, const int32_t* first_pos, int exact, int32_t* pick_idx, float* pick_val,
                                int32_t* err, void* stream);
 
+/* ---- Deterministic search (search="beam", not in the reference): the row step and the select step that keep the most likely
+ * continuations instead of drawing.  No noise is generated or read, nothing is filtered by top_k, and two runs are bit-identical (no
+ * float atomics; every reduction in a fixed order).
+ * dh_beam_row_best, per row of fp32 logits [rows, ldl] as the samplers would see it (behind dh_beam_history_logits /
+ * dh_beam_constrain_logits):
+ *   lse      = logsumexp(x[0 .. V) / temperature) over every real column, unk_index included (mass the model assigns);
+ *   pick_idx = the `beam` columns with the largest stored logit x, largest first; equal logits (-0.0 == +0.0) go to the lower column
+ *              index; unk_index, -inf and columns >= V are never picked.  The order is on x itself: exact;
+ *   pick_val = x[pick] / temperature - lse: the model's log-probability of the pick.
+ * Picks go to pick_idx / pick_val [rows, beam] at row r, as dh_beam_row_sample leaves them.  err:
+ *   DH_BEAM_ERR_NONFINITE     a NaN or +inf anywhere in the row's real columns (picks: token 0, value 0);
+ *   DH_BEAM_ERR_ALL_FILTERED  no column but unk_index is > -inf (picks: token 0, value 0);
+ *   DH_BEAM_ERR_TOO_FEW       fewer than `beam` such columns: the slots behind them hold token 0 at -inf (dead beams, informational);
+ *   never DH_BEAM_ERR_OVERFLOW: a constant row has a defined answer, its `beam` lowest eligible columns.
+ * group_max != NULL ([rows, gm_ld] maxima of n_groups <= 1024 groups of group_cols <= 64 columns, dh_beam_row_sample_groups' contract):
+ * the second look at the row reads only the groups whose maximum reaches the bound the first sweep found; NULL: it reads the row again
+ * (gm_ld, n_groups, group_cols are then not looked at).  Same picks either way.
+ * rows_per_img = 1 for the dense first step (logits [n_img, V]), beam otherwise.  first_pos != NULL ([rows / beam] int32,
+ * rows_per_img == beam): the prompted phases with `step` the absolute position -- a forced image's rows are neither read nor written,
+ * an image at its first step uses its base row img * beam only.  beam <= DH_BEAM_MAX_BEAMS, 0 < temperature < inf, ldl >= V. */
+int dh_beam_row_best(const float* logits, int ldl, int V, const float* group_max, int gm_ld, int n_groups, int group_cols,
+                     int rows, int rows_per_img, int beam, float temperature, int unk_index, int step,
+                     const int32_t* first_pos, int32_t* pick_idx, float* pick_val, int32_t* err, void* stream);
+
+/* dh_beam_select / dh_beam_select_prompted without the draw: the candidate list is built exactly as there (a live beam: `beam`
+ * candidates vals[b] + pick_val, one fp32 add; an ended beam: one candidate, token 0, its score unchanged) and the `beam` candidates
+ * with the largest score stay, largest first; equal scores go to the lower candidate index, -inf ranks last.  Token rows, src, parent,
+ * ended, done, end_step, write_pos and t are dh_beam_select's.  Two differences: hparent is the real parent row (base + parent beam),
+ * not the dense-layout index; and the caller passes first_sets_ended = 1 for every decoder kind.
+ * first_pos == NULL: a dense batch, `first` is the launch-wide flag; first_pos != NULL ([n_img] int32): the prompted phases of
+ * dh_beam_select_prompted against step_index (`first` is not read). */
+int dh_beam_select_best(const int32_t* pick_idx, const float* pick_val, int32_t* tokens, int tok_ld,
+                        float* vals, uint8_t* ended, int32_t* src, int src_ld, int32_t* parent,
+                        int32_t* hparent, uint8_t* done, int32_t* end_step, int n_img, int beam,
+                        int first, const int32_t* first_pos, int first_sets_ended, int write_pos, int t, int step_index,
+                        int eos_index, void* stream);
+
 /* ---- History-dependent logit edits in front of a row draw: no_repeat_ngram_size and repetition_penalty, IN PLACE on fp32 logits
  * [rows, ldl], one launch.  Logits row r reads its history h[0 .. pos) from tokens[r * tok_row_mult, 0 .. pos) (int32, row stride tok_ld):
  * tok_row_mult = beam for the dense first step (logits [n_img, V], image i's tokens at row i * beam), 1 otherwise.  Ids outside [0, V)
