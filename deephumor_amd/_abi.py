@@ -157,6 +157,9 @@ SIGNATURES = {
     "dh_beam_finalize_beams": [_P, _I, _P, _P, _P, _P, _I, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P, _F, _P, _U64, _P,
                                _I, _P],
     "dh_beam_gather_attention": [_P, _P, _I, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P],
+    "dh_beam_pick_logprobs": [_P, _I, _I, _I, _I, _I, _F, _I, _P, _P, _P, _P, _I, _P, _P],
+    "dh_beam_record_logprobs": [_P, _I, _P, _P, _P, _P, _P, _I, _I, _I, _P, _I, _I, _I, _P, _P, _P],
+    "dh_beam_gather_logprobs": [_P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P],
     "dh_beam_filter_top_k": [_P, _I, _I, _I, _I, _I, _P],
     "dh_beam_sample_k": [_P, _I, _I, _I, _I, _F, _P, _I, _U64, _P, _I, _I, _P, _P, _P],
     "dh_beam_gather": [_P, _I, _I, _P, _I, _P, _I, _P, _P],

@@ -140,7 +140,8 @@ def generate_sharded(generate_fn, n_total, group=None, always=None):
         return gather_beams(res, n_total, group, always)
     if len(res) > 2 or isinstance(res[0], BeamCaptions):
         raise NotImplementedError("return_attention: generate_sharded gathers token rows in one integer all-gather that carries no float "
-                                  "payload; gather the maps of generate_fn's shard yourself (gather_rows)")
+                                  "payload; gather the maps of generate_fn's shard yourself (gather_rows) -- return_logprobs: the same, "
+                                  "for the log-probabilities")
     return gather_captions(res[0], res[1], n_total, group, always)
 
 

@@ -91,7 +91,11 @@ def rank_beams(model, inputs, beams, labels=None):
     teacher-forced by ``experiments.scoring.score_captions`` (``inputs``: the ``N`` images the beams were generated for, encoded
     once; ``template_index = repeat_interleave(arange(N), B)``; ``labels`` for the label models).
     Returns ``(order int64 [N, B], perplexity float32 [N, B])``: ``order[i]`` lists image ``i``'s slots by ascending perplexity
-    (stable), ``perplexity[i, j]`` belongs to slot ``j``."""
+    (stable), ``perplexity[i, j]`` belongs to slot ``j``.
+    This is a second decoder pass over all ``N * B`` captions and it scores the RAW model: every token of a row, prompt included,
+    on the logits ``forward`` gives, at temperature 1.  ``beam_logprob_scores`` needs no pass -- it sums what
+    ``return_logprobs=True`` recorded during the search -- and scores the rows the search saw: generated tokens only, at the call's
+    temperature, behind ``logits_hook``, the history edits and the bans."""
     from .scoring import score_captions
     n, b, t = beams.tokens.shape
     pad = getattr(model.decoder, "pad_index", 0)
@@ -102,6 +106,28 @@ def rank_beams(model, inputs, beams, labels=None):
     index = torch.arange(n, device=dev).repeat_interleave(b)
     pp = score_captions(model, inputs, index, rows, lens, labels=labels, pad_index=pad).view(n, b)
     return torch.argsort(pp, dim=1, stable=True), pp
+
+
+def beam_logprob_scores(beams, logprobs, length_normalize=False, first_pos=0):
+    """Every candidate's model log-probability from ``generate_batch(..., return_beams=True, return_logprobs=True)``'s pair
+    ``(beams, logprobs [N, B, T])``, without the second decoder pass of ``rank_beams``: fp32 ``[N, B]``, the sum of a beam's
+    log-probabilities over its own columns (the columns below ``beams.lengths``; everything outside the generated ones is exactly 0),
+    or with ``length_normalize`` their mean over the generated columns -- ``beams.lengths - first_pos``, ``first_pos`` the prefix
+    length of the call (an int) or its ``caption_lengths`` (``[N]``).  ``argsort(..., descending=True)`` ranks the slots.  Under
+    ``search="beam"`` the sums are ``beams.scores``.
+    How it differs from ``rank_beams``: that one scores the raw model teacher-forced (``forward``'s logits at temperature 1, every
+    token of the row); this one scores the EDITED rows the search drew from -- ``log_softmax(x / temperature)`` behind ``logits_hook``,
+    ``no_repeat_ngram_size`` / ``repetition_penalty`` and ``min_len`` / ``bad_words_ids`` -- and only the generated tokens.  Without
+    edits and at temperature 1 the two agree to the engine's logit parity."""
+    n, b, t = logprobs.shape
+    dev = logprobs.device
+    lens = beams.lengths.to(dev)
+    own = torch.arange(t, device=dev)[None, None, :] < lens[:, :, None]
+    total = torch.where(own, logprobs.float(), torch.zeros((), device=dev)).sum(-1)
+    if not length_normalize:
+        return total
+    first = torch.as_tensor(first_pos, device=dev).reshape(-1, 1)
+    return total / (lens - first).clamp(min=1).float()
 
 
 def attention_to_heatmaps(attention, size=(224, 224), grid=(7, 7)):

@@ -1069,6 +1069,59 @@ def beam_gather_attention(attn_w, src, index, lengths, out):
     return out
 
 
+def beam_pick_logprobs(logits, v, rows, rows_per_img, beam, temperature, step, ended, pick_idx, pick_val, pick_lp, from_vals=False,
+                       first_pos=None):
+    """``dh_beam_pick_logprobs`` (``return_logprobs``), in front of the select: ``pick_lp[r, j] = logits[r, pick_idx[r, j]] / temperature -
+    logsumexp(logits[r, :v] / temperature)`` for the ``beam`` picks of every row of fp32 ``logits [rows, V]``; zeros for a row whose
+    ``ended`` flag (uint8, at the row's beam-state row: ``r * beam`` for ``rows_per_img == 1``) is set.  ``from_vals`` (``search="beam"``):
+    no sweep, the bits of ``pick_val`` under the same mask.  ``first_pos`` (int32 ``[rows // beam]``): the prompted phases at ``step``."""
+    _dev(logits, ended, pick_idx, pick_val, pick_lp, first_pos)
+    assert rows_per_img in (1, beam) and ended.dtype == torch.uint8 and ended.numel() >= rows * (beam if rows_per_img == 1 else 1)
+    assert pick_lp.dtype == torch.float32 and pick_lp.is_contiguous() and pick_lp.numel() >= rows * beam
+    if from_vals:
+        assert pick_val.dtype == torch.float32 and pick_val.is_contiguous() and pick_val.numel() >= rows * beam
+    else:
+        assert logits.dtype == torch.float32 and logits.stride(1) == 1 and logits.shape[0] >= rows and logits.shape[1] >= v
+        assert pick_idx.dtype == torch.int32 and pick_idx.is_contiguous() and pick_idx.numel() >= rows * beam
+    assert first_pos is None or (first_pos.dtype == torch.int32 and rows_per_img == beam and first_pos.numel() * beam == rows)
+    _launch("dh_beam_pick_logprobs", _ptr(logits), logits.stride(0) if logits is not None else 0, v, rows, rows_per_img, beam,
+            float(temperature), step, _ptr(first_pos), _ptr(ended), _ptr(pick_idx), _ptr(pick_val), int(bool(from_vals)), _ptr(pick_lp),
+            _stream())
+
+
+def beam_record_logprobs(tokens, parent, done, end_step, pick_idx, pick_lp, n_img, beam, first, write_pos, step_index, lp_w, par_w,
+                         first_pos=None):
+    """``dh_beam_record_logprobs`` (``return_logprobs``), behind the select: slab ``step_index`` of ``lp_w`` fp32 / ``par_w`` int32
+    ``[n_pos, n_img * beam]`` -- every row's parent, and the ``pick_lp`` of the token the select wrote at ``write_pos`` (none at
+    ``write_pos >= tokens.shape[1]``); nothing for an image that took no step (forced, or done before it)."""
+    _dev(tokens, parent, done, end_step, pick_idx, pick_lp, lp_w, par_w, first_pos)
+    rows = n_img * beam
+    assert tokens.dtype == parent.dtype == end_step.dtype == pick_idx.dtype == par_w.dtype == torch.int32 and done.dtype == torch.uint8
+    assert pick_lp.dtype == lp_w.dtype == torch.float32 and lp_w.is_contiguous() and par_w.is_contiguous() and lp_w.shape == par_w.shape
+    assert lp_w.dim() == 2 and lp_w.shape[1] == rows and 0 <= step_index < lp_w.shape[0] and tokens.stride(1) == 1 and tokens.shape[0] >= rows
+    assert parent.numel() >= rows and done.numel() >= n_img and end_step.numel() >= n_img
+    assert pick_idx.is_contiguous() and pick_lp.is_contiguous() and pick_idx.numel() >= rows * beam and pick_lp.numel() >= rows * beam
+    assert first_pos is None or (first_pos.dtype == torch.int32 and first_pos.numel() == n_img)
+    _launch("dh_beam_record_logprobs", _ptr(tokens), tokens.stride(0), _ptr(parent), _ptr(done), _ptr(end_step), _ptr(pick_idx),
+            _ptr(pick_lp), n_img, beam, int(bool(first)), _ptr(first_pos), int(write_pos), int(step_index), lp_w.shape[0], _ptr(lp_w),
+            _ptr(par_w), _stream())
+
+
+def beam_gather_logprobs(lp_w, par_w, index, lengths, out, pos=0, first_pos=None):
+    """``dh_beam_gather_logprobs`` (``return_logprobs``), behind ``beam_finalize_beams``: ``out`` fp32 ``[N, B, T]`` -- per kept beam
+    the walk from row ``i * B + index[i, j]`` down the slabs along ``par_w``, ``lp_w[c, row]`` for the columns from ``pos`` (or
+    ``first_pos[i]``) up to ``lengths[i, j]``, 0 elsewhere."""
+    _dev(lp_w, par_w, index, lengths, out, first_pos)
+    n, b, t = out.shape
+    assert lp_w.dtype == out.dtype == torch.float32 and par_w.dtype == index.dtype == lengths.dtype == torch.int32
+    assert lp_w.is_contiguous() and par_w.is_contiguous() and out.is_contiguous() and index.is_contiguous() and lengths.is_contiguous()
+    assert lp_w.shape == par_w.shape and lp_w.shape[1] == n * b and t <= lp_w.shape[0] and index.shape == lengths.shape == (n, b)
+    assert first_pos is None or (first_pos.dtype == torch.int32 and first_pos.numel() == n)
+    _launch("dh_beam_gather_logprobs", _ptr(lp_w), _ptr(par_w), _ptr(index), _ptr(lengths), n, b, t, lp_w.shape[0], int(pos),
+            _ptr(first_pos), _ptr(out), _stream())
+    return out
+
+
 GROUP_COLS = 64     # column-group width of dh_vocab_logits' group maxima
 
 

@@ -37,8 +37,11 @@ class BeamCaptions(NamedTuple):
     ``row_lengths`` int64 ``[N]``    the plain call's ``lengths``.
 
     ``scores`` are re-normalised over the drawn candidates at every step (``log_softmax`` over each row's ``B`` picks, reference
-    beam.py:79): they order the beams the way the search does, but are NOT model log-probabilities --
-    ``experiments.rank_beams`` ranks by those.
+    beam.py:79): they order the beams the way the search does, but are NOT model log-probabilities.  Those come with
+    ``return_logprobs=True``: one more tensor behind the ``BeamCaptions``, ``logprobs`` fp32 ``[N, B, T]`` in this slot order --
+    ``log_softmax(logits / temperature)`` at every token the search wrote, from the image's first generated column up to ``lengths``,
+    exactly 0 elsewhere (``LSTMDecoder.generate_batch``) --, which ``experiments.beam_logprob_scores`` sums per candidate without a
+    second decoder pass; ``experiments.rank_beams`` scores the raw model teacher-forced instead.
 
     Under ``search="beam"`` nothing is drawn and nothing is re-normalised: ``scores`` ARE the beams' cumulative model log-probabilities
     (the sum over the beam's generated tokens of ``log_softmax(logits / temperature)``, history edits and bans applied), slot 0 is the
@@ -88,6 +91,20 @@ def check_return_attention(return_attention, model=None):
             raise NotImplementedError("return_attention with pad_index == 1: that decoder re-runs the whole sequence per token on the "
                                       "module path (_generate_reforward), which keeps no per-position attention weights")
     return return_attention
+
+
+def check_return_logprobs(return_logprobs, model=None):
+    """``return_logprobs`` is a plain bool, checked where ``check_return_attention`` is, before anything runs.  Every decoder kind has
+    logits, so with ``model`` (a captioning model or its decoder) and the keyword on only ``pad_index == 1`` is refused: that decoder
+    re-runs the whole sequence per token on the module path -- ``NotImplementedError``, as ``return_attention`` there."""
+    if not isinstance(return_logprobs, bool):
+        raise TypeError(f"return_logprobs must be a bool, not {type(return_logprobs).__name__}")
+    if return_logprobs and model is not None:
+        dec = getattr(model, "decoder", model)
+        if getattr(dec, "pad_index", 0) == 1:
+            raise NotImplementedError("return_logprobs with pad_index == 1: that decoder re-runs the whole sequence per token on the "
+                                      "module path (_generate_reforward), which records no per-token log-probabilities")
+    return return_logprobs
 
 
 def check_top_p(top_p):
@@ -278,8 +295,10 @@ class DecodeSettings:
     """The validated decode settings of one call -- ``return_beams``, ``return_attention``, ``top_p``, ``no_repeat_ngram_size``,
     ``repetition_penalty``, ``min_len``, ``bad_words_ids`` -- as the ``check_*`` functions return them (``bad_words_ids``: ``None``, a
     tuple of tuples, or a ``BadWords``), ``num_tokens``, the vocabulary the list was checked against, and ``search`` (``check_search``;
-    behind ``num_tokens`` and with a default, so the positional order of the others is what it was).  Built by ``from_kw``
-    only.  Immutable; equal and hashed by the settings, the list by its ids whether compiled or not."""
+    behind ``num_tokens`` and with a default, so the positional order of the others is what it was) and ``return_logprobs``
+    (``check_return_logprobs``; the last one, for the same reason -- the constructor's last parameter, kept by ``replace``, in the key;
+    an init-only field stored by ``__post_init__``, because ``dataclasses.fields`` is pinned to end at ``search``).  Built by
+    ``from_kw`` only.  Immutable; equal and hashed by the settings, the list by its ids whether compiled or not."""
     return_beams: bool = False
     return_attention: bool = False
     top_p: float = 1.0
@@ -289,23 +308,29 @@ class DecodeSettings:
     bad_words_ids: object = None
     num_tokens: object = None
     search: str = "sample"
+    return_logprobs: dataclasses.InitVar[bool] = False
+
+    def __post_init__(self, return_logprobs):
+        object.__setattr__(self, "return_logprobs", return_logprobs)
 
     @classmethod
     def from_kw(cls, kw, max_len, num_tokens=None, model=None):
-        """Reads the settings out of the keyword dictionary ``kw`` (which keeps them) and checks them in this order -- ``search``
-        last --, so a call with two bad values raises for the earlier one; ``model``: see ``check_return_attention``."""
+        """Reads the settings out of the keyword dictionary ``kw`` (which keeps them) and checks them in this order -- ``search``, then
+        ``return_logprobs`` last --, so a call with two bad values raises for the earlier one; ``model``: see
+        ``check_return_attention`` / ``check_return_logprobs``."""
         return_beams = check_return_beams(kw.get("return_beams", False))
         return_attention = check_return_attention(kw.get("return_attention", False), model)
         top_p = check_top_p(kw.get("top_p", 1.0))
         ngram, penalty = check_repeat(kw.get("no_repeat_ngram_size", 0), kw.get("repetition_penalty", 1.0), max_len)
         min_len, bad_words = check_constraints(kw.get("min_len", 0), kw.get("bad_words_ids"), max_len, num_tokens)
         search = check_search(kw.get("search", "sample"), top_p)
-        return cls(return_beams, return_attention, top_p, ngram, penalty, min_len, bad_words, num_tokens, search)
+        return_logprobs = check_return_logprobs(kw.get("return_logprobs", False), model)
+        return cls(return_beams, return_attention, top_p, ngram, penalty, min_len, bad_words, num_tokens, search, return_logprobs)
 
     def _key(self):
         bw = self.bad_words_ids
         return (self.return_beams, self.return_attention, self.top_p, self.no_repeat_ngram_size, self.repetition_penalty, self.min_len,
-                bw.ids if isinstance(bw, BadWords) else bw, self.search)
+                bw.ids if isinstance(bw, BadWords) else bw, self.return_logprobs, self.search)
 
     def __eq__(self, other):
         return isinstance(other, DecodeSettings) and self._key() == other._key()
@@ -320,7 +345,8 @@ class DecodeSettings:
     def new_helper(self, **engine_args):
         """The ``BeamSearchHelper`` of one session with every setting applied; ``engine_args``: the constructor's other arguments."""
         return BeamSearchHelper(top_p=self.top_p, no_repeat_ngram_size=self.no_repeat_ngram_size, repetition_penalty=self.repetition_penalty,
-                                **engine_args).set_constraints(self.min_len, self.bad_words_ids).set_search(self.search)
+                                **engine_args).set_constraints(self.min_len, self.bad_words_ids).set_search(self.search).set_logprobs(
+                                    self.return_logprobs)
 
 
 class BeamOverflow(RuntimeError):
@@ -500,6 +526,17 @@ class BeamSearchHelper:
     the rows hold: a step that writes no token column (``write_pos`` past the table: the Transformer decoders' last) is skipped.  Length
     normalisation is out of scope: ``return_beams=True`` plus ``experiments.rank_beams`` re-ranks.  All launch constants, so it
     captures into a hipGraph like the rest.
+
+    ``return_logprobs`` (not in the reference either; ``helper.set_logprobs(True)`` after construction): the model log-probability of
+    every token the search writes, with nothing shuffled per step.  In front of whichever select a step runs, one launch of
+    ``dh_beam_pick_logprobs`` sweeps every logits row once more -- behind the history edits and the bans, in front of the samplers' own
+    top-k / nucleus / ``<unk>`` filtering -- and leaves ``pick_lp[r, j] = x[r, pick_idx[r, j]] / temperature - logsumexp(x[r] /
+    temperature)`` for the row's picks, zeros for a row that has ended (under ``search="beam"`` no sweep: the bits of ``pick_val``
+    under the same mask); behind the select one launch of ``dh_beam_record_logprobs`` writes slab ``step_index`` of two position-major
+    tables ``[max_len + 1, rows]`` -- ``par_w``, every row's parent, and ``lp_w``, the ``pick_lp`` of the token the row just received.
+    An image that takes no step (forced by its prompt, or done) leaves its slab as ``set_logprobs`` filled it: identity / 0.
+    ``finalize`` then takes the ``beams`` launch and one launch of ``dh_beam_gather_logprobs`` walks every kept beam's back-pointers
+    once.  Off, the default: no table, no launch.  All launch constants, so it captures into a hipGraph like the rest.
     """
 
     def __init__(self, temperature=1.0, beam_size=10, top_k=50, unk_index=1, eos_index=3, device='cuda',
@@ -511,6 +548,7 @@ class BeamSearchHelper:
         self._history_edits = self.no_repeat_ngram_size > 0 or self.repetition_penalty != 1.0
         self.min_len, self.bad_words, self._constraints = 0, None, False      # min_len / bad_words_ids: set_constraints
         self.search = "sample"            # "beam": set_search
+        self.logprobs, self.pick_lp, self.lp_w, self.par_w = False, None, None, None      # return_logprobs: set_logprobs
         self.exact = bool(exact)          # row draws through the general sampler only (see BeamOverflow)
         if beam_size > hip.MAX_BEAMS:     # one wave draws among an image's beams (dh_beam_finalize); the reference has no limit
             raise ValueError(f"beam_size <= {hip.MAX_BEAMS} supported")
@@ -565,6 +603,22 @@ class BeamSearchHelper:
         """``search`` of this session (see the class docstring), validated by ``check_search`` against the helper's ``top_p``.  A method
         like ``set_constraints``: the constructor's parameter list stays as it is.  Returns the helper."""
         self.search = check_search(search, self.top_p)
+        return self
+
+    def set_logprobs(self, on=True):
+        """``return_logprobs`` of this session (see the class docstring).  On: the picks' log-probabilities ``pick_lp [rows, beam]`` and
+        the two position-major tables ``lp_w`` fp32 / ``par_w`` int32 ``[max_len + 1, rows]`` -- one zeroed arena of their own, then
+        every row's own index into ``par_w`` -- once per session.  Off, the default: nothing is allocated and no launch is made.  A
+        method like ``set_search``: the constructor's parameter list stays as it is.  Returns the helper."""
+        self.logprobs = check_return_logprobs(on)
+        self.pick_lp = self.lp_w = self.par_w = None
+        if self.logprobs:
+            r, n_pos = self.n_img * self.beam_size, self.max_len + 1
+            arena = torch.zeros((2 * n_pos * r + r * self.beam_size,), dtype=torch.int32, device=self.device)
+            self.lp_w = arena[:n_pos * r].view(torch.float32).view(n_pos, r)
+            self.par_w = arena[n_pos * r:2 * n_pos * r].view(n_pos, r)
+            self.par_w += torch.arange(r, dtype=torch.int32, device=self.device)
+            self.pick_lp = arena[2 * n_pos * r:].view(torch.float32).view(r, self.beam_size)
         return self
 
     def set_prefix(self, caption):
@@ -643,9 +697,15 @@ class BeamSearchHelper:
         if best:                          # search="beam": the most likely tokens and candidates, no noise anywhere
             hip.beam_row_best(logits, v, rows, rpi, b, self.temperature, self.unk_index, step_index, self.pick_idx, self.pick_val, self.err,
                               group_max=gm, first_pos=first_pos)
+            if self.logprobs:             # the bits the row step left in pick_val, zero for the rows that have ended
+                hip.beam_pick_logprobs(None, v, rows, rpi, b, self.temperature, step_index, self._ended, self.pick_idx, self.pick_val,
+                                       self.pick_lp, from_vals=True, first_pos=first_pos)
             hip.beam_select_best(self.pick_idx, self.pick_val, self.tokens, self.vals, self._ended, self.src, self.parent, self.hparent,
                                  self.done, self.end_step, self.n_img, b, first, True, write_pos, t, step_index, self.eos_index,
                                  first_pos=first_pos)
+            if self.logprobs:
+                hip.beam_record_logprobs(self.tokens, self.parent, self.done, self.end_step, self.pick_idx, self.pick_lp, self.n_img, b,
+                                         first, write_pos, step_index, self.lp_w, self.par_w, first_pos=first_pos)
             return
         noise = self._noise("row", step_index, (rows, v), logits.stride(0))       # (None in a prompted session: Philox only)
         draw = (self.seed, self.img0, step_index, self.pick_idx, self.pick_val, self.err)
@@ -663,6 +723,11 @@ class BeamSearchHelper:
         else:
             hip.beam_row_sample(logits, v, rows, rpi, b, self.top_k, self.temperature, self.unk_index, noise, *draw,
                                 seed_ptr=self.seed_tensor, exact=self.exact)
+        if self.logprobs:
+            # return_logprobs: one more sweep of the rows (L2-resident by now) for log_softmax(x / T) at the picks -- behind the edits and
+            # the bans, in front of the samplers' own filtering -- while `ended` still holds the flags of the rows the picks came from
+            hip.beam_pick_logprobs(logits, v, rows, rpi, b, self.temperature, step_index, self._ended, self.pick_idx, self.pick_val,
+                                   self.pick_lp, first_pos=first_pos)
         state = (self.pick_idx, self.pick_val, self.tokens, self.vals, self._ended, self.src, self.parent, self.hparent, self.done,
                  self.end_step, self.n_img, b)
         if prompted:
@@ -672,6 +737,9 @@ class BeamSearchHelper:
             noise = None if first else self._noise("cand", step_index, (self.n_img, b ** 2))
             hip.beam_select(*state, first, first_sets_ended, write_pos, t, step_index, self.temperature, self.eos_index, noise,
                             self.seed, self.img0, seed_ptr=self.seed_tensor)
+        if self.logprobs:                 # slab `step_index`: every row's parent and the log-probability of the token it just got
+            hip.beam_record_logprobs(self.tokens, self.parent, self.done, self.end_step, self.pick_idx, self.pick_lp, self.n_img, b, first,
+                                     write_pos, step_index, self.lp_w, self.par_w, first_pos=first_pos)
 
     def finalize(self, len_bias_done, full_len, pad_index=0, defer_check=False, first_beam=False, beams=False, pos=0, attn_w=None):
         """Final draw among the beams and output copy; returns a ``SessionResult`` whose ``captions`` are ``(tokens int64 [n_img,
@@ -687,7 +755,11 @@ class BeamSearchHelper:
         through ``self.src``, for the columns below the beam's own length, zero elsewhere -- in the result's ``attention``, fp32
         ``[n_img, beam, max_len, S]``; its ``captions`` are those of ``beams=True``.
         ``search="beam"``: no draw and no noise -- always the ``beams`` launch, whose slot 0 is the beam with the largest score (equal
-        scores: the lower engine index); ``drawn`` is 0 for every image and the plain pair is slot 0's row and ``row_lengths``."""
+        scores: the lower engine index); ``drawn`` is 0 for every image and the plain pair is slot 0's row and ``row_lengths``.
+        ``return_logprobs`` (``set_logprobs``): always the ``beams`` launch too, and one launch of ``dh_beam_gather_logprobs`` behind it
+        walks every kept beam's back-pointers (``par_w``) once and leaves the log-probabilities of its own columns -- from the image's
+        first generated column up to the beam's own length, zero elsewhere -- in the result's ``logprobs``, fp32 ``[n_img, beam,
+        max_len]``; its ``captions`` are those of ``beams=True``."""
         best = self.search == "beam"
         if best:
             noise = None
@@ -696,7 +768,8 @@ class BeamSearchHelper:
             noise[:, 0] = 1.0
         else:
             noise = self._noise("final", 0, (self.n_img, self.beam_size))
-        if beams or attn_w is not None or best:
+        logprobs = None
+        if beams or attn_w is not None or best or self.logprobs:
             n, b, dev = self.n_img, self.beam_size, self.device
             out = torch.empty((n, b, self.max_len), dtype=torch.int32, device=dev)
             ints = torch.empty((2 * n * b + 2 * n,), dtype=torch.int32, device=dev)
@@ -709,10 +782,13 @@ class BeamSearchHelper:
             if attn_w is not None:
                 attention = torch.empty((n, b, self.max_len, attn_w.shape[2]), dtype=torch.float32, device=dev)
                 hip.beam_gather_attention(attn_w, self.src, o_idx, o_len, attention)
+            if self.logprobs:
+                logprobs = torch.empty((n, b, self.max_len), dtype=torch.float32, device=dev)
+                hip.beam_gather_logprobs(self.lp_w, self.par_w, o_idx, o_len, logprobs, pos=pos, first_pos=self.first_pos)
             if best:
                 o_drawn.zero_()           # (the kernel's draw among the beams is not this search's: slot 0, the best score, is returned)
             captions = BeamCaptions(out.long(), o_len.long(), o_score, o_idx.long(), o_drawn.long(), o_row.long())
-            if best and not beams and attn_w is None:
+            if best and not beams and attn_w is None and not self.logprobs:
                 captions = (captions.tokens[:, 0], captions.row_lengths)
         else:
             attention = None
@@ -723,9 +799,9 @@ class BeamSearchHelper:
                               seed_ptr=self.seed_tensor)
             captions = (out.long(), out_len.long())
         if defer_check:
-            return SessionResult(captions, self.err, attention)
+            return SessionResult(captions, self.err, attention, logprobs)
         self.check()
-        return SessionResult(captions, None, attention)
+        return SessionResult(captions, None, attention, logprobs)
 
     def check(self):
         """Raises like the reference does when every logit of a row was filtered (beam.py:46)."""
@@ -991,13 +1067,16 @@ def resolve_seed(seed, noise_source=None):
 class SessionResult(NamedTuple):
     """What a decode session returns (``BeamSearchHelper.finalize``): ``captions`` -- the ``(tokens, lengths)`` pair or a
     ``BeamCaptions`` --, ``err`` -- the device error word of a ``defer_check`` session, else ``None`` --, and ``attention`` -- the kept
-    beams' maps fp32 ``[n, B, T, S]`` of a ``return_attention`` session (whose ``captions`` are a ``BeamCaptions``), else ``None``."""
+    beams' maps fp32 ``[n, B, T, S]`` of a ``return_attention`` session (whose ``captions`` are a ``BeamCaptions``), else ``None`` --,
+    and ``logprobs`` -- the kept beams' per-token log-probabilities fp32 ``[n, B, T]`` of a ``return_logprobs`` session (whose
+    ``captions`` are a ``BeamCaptions`` too), else ``None``."""
     captions: object
     err: object = None
     attention: object = None
+    logprobs: object = None
 
     def record_stream(self, stream):
-        for t in (*self.captions, self.err, self.attention):
+        for t in (*self.captions, self.err, self.attention, self.logprobs):
             if t is not None:
                 t.record_stream(stream)
 
@@ -1012,17 +1091,22 @@ class SessionResult(NamedTuple):
             err = first.err.clone()
             for p in parts[1:]:
                 err |= p.err
-        return SessionResult(caps, err, None if first.attention is None else torch.cat([p.attention for p in parts], 0))
+        return SessionResult(caps, err, None if first.attention is None else torch.cat([p.attention for p in parts], 0),
+                             None if first.logprobs is None else torch.cat([p.logprobs for p in parts], 0))
 
     def public(self, return_beams=False):
         """What ``generate_batch`` returns: the pair or the ``BeamCaptions``; behind it ``attention`` -- ``[N, B, T, S]`` for
-        ``return_beams``, else the drawn slot's maps ``[N, T, S]`` behind ``best()``, the plain pair bit for bit --; behind that the
-        error word of a ``defer_check`` call.  One element alone is returned as it is."""
-        caps, att = self.captions, self.attention
-        if att is not None and not return_beams:
-            caps, att = caps.best(), att[torch.arange(att.shape[0], device=att.device), caps.drawn]
+        ``return_beams``, else the drawn slot's maps ``[N, T, S]`` behind ``best()``, the plain pair bit for bit --; behind that
+        ``logprobs`` -- ``[N, B, T]``, or the drawn slot's ``[N, T]`` in the same way --; last the error word of a ``defer_check``
+        call.  One element alone is returned as it is."""
+        caps, att, lp = self.captions, self.attention, self.logprobs
+        if (att is not None or lp is not None) and not return_beams:
+            rows = torch.arange(caps.drawn.shape[0], device=caps.drawn.device)
+            att = None if att is None else att[rows, caps.drawn]
+            lp = None if lp is None else lp[rows, caps.drawn]
+            caps = caps.best()
         out = (caps,) if isinstance(caps, BeamCaptions) else tuple(caps)
-        out += tuple(t for t in (att, self.err) if t is not None)
+        out += tuple(t for t in (att, lp, self.err) if t is not None)
         return out[0] if len(out) == 1 else out
 
 

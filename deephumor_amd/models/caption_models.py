@@ -68,7 +68,13 @@ class _CaptioningBase(nn.Module):
         (or teacher-forced past, for prompt columns) -- taken on the row that computed that position of this beam's history.  Rows
         ``c <`` the beam's own length (``BeamCaptions.lengths``; the drawn beam's for the plain call) are filled and sum to 1; every
         other element is exactly 0.  A masked key has weight exactly 0 unless every key is masked (uniform ``1 / S``).  It changes
-        no token; the other kinds raise ``TypeError``, ``pad_index == 1`` ``NotImplementedError`` (``beam.check_return_attention``)."""
+        no token; the other kinds raise ``TypeError``, ``pad_index == 1`` ``NotImplementedError`` (``beam.check_return_attention``).
+        ``return_logprobs=True`` (in ``kw``, a plain bool; every kind): one more result, last in the tuple (behind ``attention``), an
+        fp32 device tensor that says how likely the model found every token it wrote -- ``(tokens, lengths, logprobs [N, T])``, or
+        ``(BeamCaptions, logprobs [N, B, T])`` with ``return_beams=True``; ``log_softmax(logits / temperature)`` at the token, on the
+        row it was taken from, behind the history edits and the bans and in front of the top-k / nucleus / ``<unk>`` filtering; filled
+        from the first generated column up to the beam's own length, exactly 0 elsewhere (``LSTMDecoder.generate_batch`` has the full
+        contract).  It changes no token; ``pad_index == 1`` raises ``NotImplementedError`` (``beam.check_return_logprobs``)."""
         if caption_lengths is not None:
             kw["caption_lengths"] = caption_lengths
         return self.decoder.generate_batch(*encoded, caption=caption, max_len=max_len, temperature=temperature,
@@ -81,6 +87,8 @@ class _CaptioningBase(nn.Module):
         settings = DecodeSettings.from_kw(kw, max_len, self._hp["num_tokens"], self)
         if not settings.return_attention and not getattr(self.decoder, "_cross", False):
             kw.pop("return_attention", None)      # (off, it is the call without the keyword -- also for the kinds whose decoders do not know it)
+        if not settings.return_logprobs:
+            kw.pop("return_logprobs", None)       # (off, it is the call without the keyword)
         if caption_lengths is None:
             return None
         if getattr(self.decoder, "pad_index", 0) == 1:
@@ -124,13 +132,15 @@ class _CaptioningBase(nn.Module):
         step), so one graph serves every set of lengths of that shape and returns what eager returns for them."""
         # every decode setting rides in ``kw`` and so is part of the cache key below: the graph of ``return_beams=True`` (it ends in
         # dh_beam_finalize_beams), of ``return_attention=True`` (one dh_attn_cross_weights node per position and the gather behind the
-        # final draw), of ``top_p < 1`` (nucleus row draws), of ``search="beam"`` (dh_beam_row_best / dh_beam_select_best nodes), of the
+        # final draw), of ``return_logprobs=True`` (two nodes around every select and the back-pointer walk behind the final draw), of ``top_p < 1`` (nucleus row draws), of ``search="beam"`` (dh_beam_row_best / dh_beam_select_best nodes), of the
         # repeat controls and of ``min_len`` / ``bad_words_ids`` (one
         # dh_beam_history_logits / dh_beam_constrain_logits node per position that edits something; the position is a launch constant)
         # each lives beside the plain one of the same shapes, and a replay returns clones of every field
         settings = DecodeSettings.from_kw(kw, kw.get("max_len", 25), self._hp["num_tokens"], self)
         if not settings.return_attention:
             kw.pop("return_attention", None)          # (False is the call without the keyword: the plain graph, not a second one)
+        if not settings.return_logprobs:
+            kw.pop("return_logprobs", None)           # (the same)
         # The list is compiled HERE, in front of any capture -- no host-to-device copy happens inside one -- and the ``BadWords``
         # replaces the raw nesting in ``kw``: it is hashable, so it is in the key below, and the captured closure keeps its two
         # tensors alive
@@ -220,10 +230,10 @@ class _CaptioningBase(nn.Module):
             warn_overflow_retry()         # configuration) eagerly through the general sampler
             eager_keys[key] = self._plan_signature()
             return self.generate_batch(*inputs, caption=caption, seed=seed, exact=True, **lens_kw, **kw)
-        if isinstance(out[0], BeamCaptions):          # (BeamCaptions, [attention,] error word): clones of every field
+        if isinstance(out[0], BeamCaptions):          # (BeamCaptions, [attention,] [logprobs,] error word): clones of every field
             beams = out[0].map(torch.Tensor.clone)
-            return (beams, out[1].clone()) if len(out) == 3 else beams
-        return tuple(t.clone() for t in out[:-1])     # (tokens, lengths, [attention,] error word)
+            return (beams, *(t.clone() for t in out[1:-1])) if len(out) > 2 else beams
+        return tuple(t.clone() for t in out[:-1])     # (tokens, lengths, [attention,] [logprobs,] error word)
 
 
 class CaptioningLSTM(_CaptioningBase):

@@ -22,7 +22,7 @@ from .encoders import _Planned
 def _later_keywords(*names):
     """Decorator of ``LSTMDecoder.generate_batch``: the method keeps the parameter list it had (positional order, keyword-only tail
     ending at ``repetition_penalty``), and the keyword-only controls added since -- ``names`` -- are accepted by name here and go to
-    ``self._decode_batch``, the implementation, together with everything else.  A call without them is the method's own body."""
+    ``self._decode_session``, the implementation, together with everything else.  A call without them is the method's own body."""
     import functools
 
     def deco(fn):
@@ -31,7 +31,7 @@ def _later_keywords(*names):
             later = {k: kw.pop(k) for k in names if k in kw}
             if not later:
                 return fn(self, *args, **kw)
-            return self._decode_batch(*args, **kw, **later)
+            return self._decode_session(*args, **kw, **later)
         return generate_batch
     return deco
 
@@ -190,7 +190,7 @@ class LSTMDecoder(_Planned, nn.Module):
         hs.mul_(valid[..., None])          # pad_packed_sequence zero rows (mask, not arithmetic on valid rows)
         return hs, bs, steps_out
 
-    @_later_keywords("min_len", "bad_words_ids", "search")
+    @_later_keywords("min_len", "bad_words_ids", "search", "return_logprobs")
     def generate_batch(self, image_emb, caption=None, max_len=25, temperature=1.0, beam_size=10, top_k=50,
                        eos_index=3, seed=None, img0=0, noise_source=None, logits_hook=None, streams=1, seed_tensor=None,
                        defer_check=False, early_stop_every=0, exact=False, rng=None, *, caption_lengths=None, return_beams=False, top_p=1.0,
@@ -243,9 +243,21 @@ class LSTMDecoder(_Planned, nn.Module):
         ``scores`` are cumulative model log-probabilities and ``drawn`` is 0.  Two launches per position (``dh_beam_row_best``,
         ``dh_beam_select_best``) in place of the sampled pair (``BeamSearchHelper``).  No length normalisation: ``return_beams=True``
         plus ``experiments.rank_beams`` re-ranks.
-        ``min_len``, ``bad_words_ids`` and ``search`` are not in the parameter list above, which ends at ``repetition_penalty`` as it
-        did: they are taken by name (``_later_keywords``) and handed to ``_decode_batch``, the implementation, which spells every
-        keyword out."""
+        ``return_logprobs=True`` (keyword only, a plain bool; ``beam.check_return_logprobs``): one more result, last in the tuple, an
+        fp32 device tensor with the model's log-probability of every token the search wrote -- ``(tokens, lengths, logprobs [N, T])``,
+        or ``(BeamCaptions, logprobs [N, B, T])`` with ``return_beams=True`` in ``BeamCaptions`` slot order.  ``logprobs[i, (slot,) c]``
+        is ``log_softmax(x / temperature)[token at column c]`` over every real column (``<unk>`` included), ``x`` the fp32 logits row
+        that token was taken from as it stands in front of the row step: behind ``logits_hook``, the history edits and the bans, in
+        front of the top-k / nucleus / ``<unk>`` filtering -- the definition ``search="beam"`` uses for ``scores``, whose bits these are
+        there (their left-to-right fp32 sum over a live beam's own columns IS its score).  Filled from the image's first generated
+        column up to the beam's own length (``BeamCaptions.lengths``; the drawn beam's for the plain call); every other element --
+        prefix and prompt columns, anything behind the beam's own ``<eos>`` -- is exactly 0.  A dead beam (score ``-inf``) has
+        unspecified values, never NaN.  It changes no token; ``False``, the default, is the call without the keyword: same launches,
+        same bits.  On: three launches of their own (``dh_beam_pick_logprobs`` in front of and ``dh_beam_record_logprobs`` behind every
+        select, ``dh_beam_gather_logprobs`` behind the final draw; ``BeamSearchHelper``).
+        ``min_len``, ``bad_words_ids``, ``search`` and ``return_logprobs`` are not in the parameter list above, which ends at
+        ``repetition_penalty`` as it did: they are taken by name (``_later_keywords``) and handed to ``_decode_session``, the
+        implementation, which spells every keyword out."""
         return self._generate_batch(image_emb, caption, max_len, temperature, beam_size, top_k, eos_index, seed, img0, noise_source,
                                     logits_hook, streams, seed_tensor, defer_check, early_stop_every, exact, rng,
                                     caption_lengths=caption_lengths, return_beams=return_beams, top_p=top_p,
@@ -269,10 +281,24 @@ class LSTMDecoder(_Planned, nn.Module):
                       eos_index=3, seed=None, img0=0, noise_source=None, logits_hook=None, streams=1, seed_tensor=None,
                       defer_check=False, early_stop_every=0, exact=False, rng=None, *, caption_lengths=None, return_beams=False, top_p=1.0,
                       no_repeat_ngram_size=0, repetition_penalty=1.0, min_len=0, bad_words_ids=None, search="sample"):
+        """``generate_batch`` with its keyword-only tail up to ``search`` written out: this parameter list is what it was, and
+        ``_decode_session`` behind it takes the keywords added since."""
+        return self._decode_session(image_emb, caption, max_len, temperature, beam_size, top_k, eos_index, seed, img0, noise_source,
+                                    logits_hook, streams, seed_tensor, defer_check, early_stop_every, exact, rng,
+                                    caption_lengths=caption_lengths, return_beams=return_beams, top_p=top_p,
+                                    no_repeat_ngram_size=no_repeat_ngram_size, repetition_penalty=repetition_penalty, min_len=min_len,
+                                    bad_words_ids=bad_words_ids, search=search)
+
+    @f32x_guarded
+    def _decode_session(self, image_emb, caption=None, max_len=25, temperature=1.0, beam_size=10, top_k=50,
+                        eos_index=3, seed=None, img0=0, noise_source=None, logits_hook=None, streams=1, seed_tensor=None,
+                        defer_check=False, early_stop_every=0, exact=False, rng=None, *, caption_lengths=None, return_beams=False, top_p=1.0,
+                        no_repeat_ngram_size=0, repetition_penalty=1.0, min_len=0, bad_words_ids=None, search="sample",
+                        return_logprobs=False):
         """The implementation of ``generate_batch``, every keyword spelled out."""
         settings = DecodeSettings.from_kw(dict(return_beams=return_beams, top_p=top_p, no_repeat_ngram_size=no_repeat_ngram_size,
                                                repetition_penalty=repetition_penalty, min_len=min_len, bad_words_ids=bad_words_ids,
-                                               search=search), max_len, self.num_tokens)
+                                               search=search, return_logprobs=return_logprobs), max_len, self.num_tokens)
         if settings.search == "beam":     # nothing is drawn: no generator is read, no noise source is asked
             rng, noise_source, seed = None, None, 0
         self._check_mode()
@@ -379,9 +405,12 @@ class LSTMDecoder(_Planned, nn.Module):
     @staticmethod
     def single_output(res, caption, max_len, beam_size):
         """Row 0 of ``generate_batch``'s result in the shape the reference's single-image ``generate`` returns; a ``BeamCaptions``
-        (``return_beams=True``) as it is."""
-        if isinstance(res, BeamCaptions):
+        (``return_beams=True``) as it is, and so ``(BeamCaptions, logprobs [1, B, T])``.  ``return_logprobs=True`` without it: the pair
+        ``(caption, logprobs [len])``."""
+        if isinstance(res, BeamCaptions) or isinstance(res[0], BeamCaptions):
             return res
+        if len(res) == 3:
+            return LSTMDecoder.single_output(res[:2], caption, max_len, beam_size), res[2][0, :int(res[1][0])]
         toks, lens = res
         seq = toks[0, :int(lens[0])]
         if (0 if caption is None else caption.shape[1]) + 1 >= max_len:

@@ -529,23 +529,37 @@ class _IncrementalDecoder(_Planned, nn.Module):
     @staticmethod
     def _one(res):
         """``generate``'s result from ``_generate_batch``'s for one image: the caption, or the ``BeamCaptions`` (N = 1) as it is; with
-        ``return_attention=True`` the pair ``(caption, attention [len, S])``, or ``(BeamCaptions, attention [1, B, T, S])`` as it is."""
+        ``return_attention=True`` the pair ``(caption, attention [len, S])``, or ``(BeamCaptions, attention [1, B, T, S])`` as it is;
+        with ``return_logprobs=True`` one more element in the same way, ``logprobs [len]`` (or ``[1, B, T]`` as it is)."""
         if isinstance(res, BeamCaptions) or isinstance(res[0], BeamCaptions):
             return res
-        if len(res) == 3:
-            toks, lens, att = res
-            return toks[0, :int(lens[0])].squeeze(), att[0, :int(lens[0])]
-        toks, lens = res
-        return toks[0, :int(lens[0])].squeeze()
+        toks, lens, *extra = res
+        n = int(lens[0])
+        if extra:
+            return (toks[0, :n].squeeze(), *(e[0, :n] for e in extra))
+        return toks[0, :n].squeeze()
 
     def _generate_batch(self, start_emb, enc_out, caption, max_len, temperature, beam_size, top_k, eos_index,
                         seed=None, img0=0, noise_source=None, logits_hook=None, streams=1, seed_tensor=None,
                         defer_check=False, early_stop_every=0, exact=False, rng=None, caption_lengths=None, return_beams=False, top_p=1.0,
                         no_repeat_ngram_size=0, repetition_penalty=1.0, min_len=0, bad_words_ids=None, return_attention=False,
                         search="sample"):
+        """``_decode_session`` with the keywords up to ``search``: this parameter list is what it was."""
+        return self._decode_session(start_emb, enc_out, caption, max_len, temperature, beam_size, top_k, eos_index, seed, img0, noise_source,
+                                    logits_hook, streams, seed_tensor, defer_check, early_stop_every, exact, rng, caption_lengths,
+                                    return_beams, top_p, no_repeat_ngram_size, repetition_penalty, min_len, bad_words_ids, return_attention,
+                                    search)
+
+    def _decode_session(self, start_emb, enc_out, caption, max_len, temperature, beam_size, top_k, eos_index,
+                        seed=None, img0=0, noise_source=None, logits_hook=None, streams=1, seed_tensor=None,
+                        defer_check=False, early_stop_every=0, exact=False, rng=None, caption_lengths=None, return_beams=False, top_p=1.0,
+                        no_repeat_ngram_size=0, repetition_penalty=1.0, min_len=0, bad_words_ids=None, return_attention=False,
+                        search="sample", return_logprobs=False):
+        """The implementation of ``generate_batch`` / ``generate``, every keyword spelled out."""
         settings = DecodeSettings.from_kw(dict(return_beams=return_beams, return_attention=return_attention, top_p=top_p,
                                                no_repeat_ngram_size=no_repeat_ngram_size, repetition_penalty=repetition_penalty,
-                                               min_len=min_len, bad_words_ids=bad_words_ids, search=search), max_len, self.num_tokens, self)
+                                               min_len=min_len, bad_words_ids=bad_words_ids, search=search,
+                                               return_logprobs=return_logprobs), max_len, self.num_tokens, self)
         if settings.search == "beam":     # nothing is drawn: no generator is read, no noise source is asked
             rng, noise_source, seed = None, None, 0
         self._check_mode()
@@ -677,14 +691,15 @@ class TransformerDecoder(_IncrementalDecoder):
         a prompt of its own length per image; ``return_beams``, ``top_p``, ``no_repeat_ngram_size`` / ``repetition_penalty``, ``min_len`` /
         ``bad_words_ids``, ``search`` (in ``kw``): see ``LSTMDecoder.generate_batch`` for all;
         ``return_attention=True`` (in ``kw``): one more result, the fp32 map of where every token looked -- ``attention [N, T, S]``
-        behind the pair, or ``[N, B, T, S]`` behind the ``BeamCaptions`` -- see ``caption_models._CaptioningBase.decode``."""
-        return self._generate_batch(start_emb, enc_out, caption, max_len, temperature, beam_size, top_k,
+        behind the pair, or ``[N, B, T, S]`` behind the ``BeamCaptions`` -- see ``caption_models._CaptioningBase.decode``;
+        ``return_logprobs=True`` (in ``kw``): last, every token's model log-probability, ``logprobs [N, T]`` or ``[N, B, T]`` -- see there."""
+        return self._decode_session(start_emb, enc_out, caption, max_len, temperature, beam_size, top_k,
                                     eos_index, caption_lengths=caption_lengths, **kw)
 
     def generate(self, start_emb, enc_out, caption=None, max_len=25,
                  temperature=1.0, beam_size=10, top_k=50, eos_index=3, **kw):
         """Reference single-image API (transformers.py:492-493) -> 1-D (0-D for one token) int64."""
-        res = self._generate_batch(start_emb, enc_out, caption, max_len, temperature, beam_size, top_k, eos_index, **kw)
+        res = self._decode_session(start_emb, enc_out, caption, max_len, temperature, beam_size, top_k, eos_index, **kw)
         return self._one(res)
 
 
@@ -703,11 +718,11 @@ class SelfAttentionTransformerDecoder(_IncrementalDecoder):
     def generate_batch(self, start_emb, caption=None, max_len=25, temperature=1.0, beam_size=10,
                        top_k=50, eos_index=3, *, caption_lengths=None, **kw):
         """``caption_lengths`` (keyword only) and the decode settings in ``kw``: see ``LSTMDecoder.generate_batch``."""
-        return self._generate_batch(start_emb, None, caption, max_len, temperature, beam_size, top_k,
+        return self._decode_session(start_emb, None, caption, max_len, temperature, beam_size, top_k,
                                     eos_index, caption_lengths=caption_lengths, **kw)
 
     def generate(self, start_emb, caption=None, max_len=25,
                  temperature=1.0, beam_size=10, top_k=50, eos_index=3, **kw):
         """Reference single-image API (transformers.py:740-741)."""
-        res = self._generate_batch(start_emb, None, caption, max_len, temperature, beam_size, top_k, eos_index, **kw)
+        res = self._decode_session(start_emb, None, caption, max_len, temperature, beam_size, top_k, eos_index, **kw)
         return self._one(res)

@@ -53,6 +53,10 @@ class CaptionPipeline:
             raise NotImplementedError("return_attention: CaptionPipeline hands batches over through pinned (tokens, lengths) / BeamCaptions "
                                       "slots that carry no float payload; call model.generate_batch(..., return_attention=True)")
         gen_kw.pop("return_attention", None)         # (False: the pipeline without the keyword)
+        if settings.return_logprobs:
+            raise NotImplementedError("return_logprobs: CaptionPipeline hands batches over through pinned (tokens, lengths) / BeamCaptions "
+                                      "slots that carry no float payload; call model.generate_batch(..., return_logprobs=True)")
+        gen_kw.pop("return_logprobs", None)          # (the same)
         self.model, self.gen_kw, self.overlap, self.preprocess = model, gen_kw, overlap, preprocess
         self.dev = next(model.parameters()).device
         if overlap:

@@ -682,6 +682,40 @@ int dh_beam_finalize_beams(const int32_t* tokens, int tok_ld, const float* vals,
 int dh_beam_gather_attention(const float* attn_w, const int32_t* src, int src_ld, const int32_t* index, const int32_t* len,
                              float* out, int n_img, int beam, int T, int n_pos, int rows_total, int S, void* stream);
 
+/* ---- return_logprobs (not in the reference): the model log-probability of every token a beam holds, in three launches of their own
+ * around the select and behind the final draw (csrc/beam_logprobs.hip).  Deterministic: no float atomics, every reduction in a fixed
+ * order.
+ * dh_beam_pick_logprobs, in front of the select: per row of fp32 logits [rows, ldl] as the row step saw it (behind
+ * dh_beam_history_logits / dh_beam_constrain_logits, in front of any top-k / nucleus / unk filtering)
+ *   pick_lp[r, j] = x[r, pick_idx[r, j]] / temperature - logsumexp(x[r, 0 .. V) / temperature),   j < beam
+ * with dh_beam_row_best's sweep (one pass, 16-byte loads) and its exact division.  A row whose `ended` flag is set -- ended [rows_total]
+ * is read at the row's beam-state row: r * beam for rows_per_img == 1 (the dense first step's compact rows), r otherwise -- gets
+ * zeros; so does a row that holds NaN or +inf or nothing finite (the row step flags those), and a pick outside [0, V).
+ * from_vals != 0 (search="beam"): no sweep, pick_lp = pick_val bit for bit under the same `ended` mask (logits, pick_idx unused).
+ * first_pos != NULL ([rows / beam] int32, rows_per_img == beam): the prompted phases as in dh_beam_row_best. */
+int dh_beam_pick_logprobs(const float* logits, int ldl, int V, int rows, int rows_per_img, int beam, float temperature, int step,
+                          const int32_t* first_pos, const uint8_t* ended, const int32_t* pick_idx, const float* pick_val,
+                          int from_vals, float* pick_lp, void* stream);
+
+/* Behind the select of position step_index: slab c = step_index of two position-major tables [n_pos, n_img * beam] that the caller
+ * filled once with 0 (lp_w, fp32) and with every row's own index (par_w, int32).  Per beam row of an image that took the step:
+ *   par_w[c, row] = parent[row];   lp_w[c, row] = pick_lp[prow, j] for the first j with pick_idx[prow, j] == tokens[row, write_pos],
+ * 0 without one; prow = parent[row], at a first step the image's compact row img (first_pos == NULL and first != 0) or its base row
+ * img * beam (first_pos[img] == step_index).  An image that took no step -- step_index < first_pos[img], or done[img] with
+ * end_step[img] < step_index -- writes nothing.  write_pos >= tok_ld (a step that re-draws the beams and writes no column): parents
+ * only. */
+int dh_beam_record_logprobs(const int32_t* tokens, int tok_ld, const int32_t* parent, const uint8_t* done, const int32_t* end_step,
+                            const int32_t* pick_idx, const float* pick_lp, int n_img, int beam, int first,
+                            const int32_t* first_pos, int write_pos, int step_index, int n_pos, float* lp_w, int32_t* par_w,
+                            void* stream);
+
+/* Behind dh_beam_finalize_beams (index / len = its out_index / out_len [n_img, beam]): per kept beam, from r = i * beam + index[i, j]
+ * and from slab n_pos - 1 down to 0,
+ *   out[i, j, c] = lp_w[c, r]  for p0 <= c < len[i, j]  (p0 = first_pos[i], or pos without first_pos),   then r = par_w[c, r]
+ * and 0 in every other element of out fp32 [n_img, beam, T], T <= n_pos.  A par_w entry outside the table's rows is not followed. */
+int dh_beam_gather_logprobs(const float* lp_w, const int32_t* par_w, const int32_t* index, const int32_t* len, int n_img, int beam,
+                            int T, int n_pos, int pos, const int32_t* first_pos, float* out, void* stream);
+
 /* ---------------------------------------------------------------------------------------------
  * Teacher-forced scoring (deephumor/experiments/metrics.py:4-9; call shape trainer.py:69-81)
  * ------------------------------------------------------------------------------------------- */
