@@ -591,6 +591,9 @@ struct SelectParams {
     int beam, first, first_sets_ended, write_pos, t, step_index, eos, img0;
     float temperature; const float* noise; uint64_t seed; const uint64_t* seed_ptr;
     const int32_t* first_pos = nullptr;                 // dh_beam_select_prompted: [n_img] prompt lengths, `first` is then per image
+    float* keys = nullptr;                              // dh_beam_select_best_norm: [rows] the kept candidates' keys (score * len_w[L])
+    const float* len_w = nullptr;                       //   [tok_ld + 1] weights by generated length, len_w[0] = 1
+    int first_col = 0;                                  //   dense: the first generated column (prompted: first_pos[img])
 };
 
 // LDS scratch of one image's candidate draw, carved by the caller (beam_select_kernel's own arrays)
@@ -607,15 +610,22 @@ struct SelLds {
 // (see prompt_row_idle); its first step reads the picks of its logical row img * beam, where the prompted samplers leave them.
 // DT (dh_beam_select_best): no draw -- the `beam` candidates with the largest score stay, equal scores to the lower candidate index,
 // -inf last; hparent is the real parent row.  Neither noise nor temperature is read.
-template <int MB, bool PR = false, bool DT = false>
+// LN (dh_beam_select_best_norm, with DT): the rank runs on key = score * len_w[L] in place of the score -- ONE fp32 multiply; L, the
+// columns the search has written to a live candidate, is write_pos + 1 - (the image's first generated column), the same for every live
+// candidate of the image, so len_w[L] is one wave-uniform load.  An ended beam's candidate keeps the key it was kept with (p.keys,
+// loaded with vals and ended); q holds the keys, the kept ones go to p.keys, and p.vals keeps the raw scores.
+template <int MB, bool PR = false, bool DT = false, bool LN = false>
 __device__ __forceinline__ void beam_select_image(const SelectParams& p, const int img, const int lane, const SelLds& L) {
+    static_assert(DT || !LN, "the length weights rank the deterministic select only");
     int32_t* stage = L.stage;
     int* ctok = L.ctok; int* cpar = L.cpar; int* keep = L.keep; float* cval = L.cval; float* q = L.q; uint8_t* cend = L.cend;
 #define s_n (*L.s_n)
     const int B = p.beam, base = img * B;
     int first = p.first;
+    int first_col = p.first_col;
     if constexpr (PR) {
         const int fp = p.first_pos[img];
+        first_col = fp;
         if (p.step_index < fp) {
             // forced: the token column keeps the prompt's token, scores / ended / done stay 0, nothing is drawn.  Every beam row keeps
             // pointing at the image's base row -- the one row with real history behind it -- for the KV cache and the LSTM state
@@ -653,6 +663,13 @@ __device__ __forceinline__ void beam_select_image(const SelectParams& p, const i
     float val_b[MB];
 #pragma unroll
     for (int b = 0; b < MB; ++b) val_b[b] = p.vals[base + min(b, B - 1)];
+    float key_b[LN ? MB : 1];
+    float w_len = 1.f;
+    if constexpr (LN) {
+#pragma unroll
+        for (int b = 0; b < MB; ++b) key_b[b] = p.keys[base + min(b, B - 1)];
+        w_len = p.len_w[min(max(p.write_pos + 1 - first_col, 0), p.tok_ld)];      // (image-uniform; the table has tok_ld + 1 entries)
+    }
     if (pre) { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); wave_lds_sync(); }
     if (is_done) return;
 
@@ -663,6 +680,7 @@ __device__ __forceinline__ void beam_select_image(const SelectParams& p, const i
             const int tok = pre ? L.pki[j] : p.pick_idx[pk_first + j];
             ctok[j] = tok; cval[j] = pre ? L.pkv[j] : p.pick_val[pk_first + j]; cpar[j] = 0;
             cend[j] = (uint8_t)(p.first_sets_ended && tok == p.eos);
+            if constexpr (LN) q[j] = cval[j] * w_len;
             keep[j] = j;
         }
         if (lane == 0) s_n = B;
@@ -679,11 +697,13 @@ __device__ __forceinline__ void beam_select_image(const SelectParams& p, const i
             for (int k = 1; k < MB; ++k) b += (k < B && c >= off[k]);
             const int j = c - off[b];
             bool was = false; float vb = 0.f;             // (static register indexing: b is a run-time value)
+            [[maybe_unused]] float kb = 0.f;
 #pragma unroll
-            for (int k = 0; k < MB; ++k) if (k == b) { was = was_ended[k] != 0; vb = val_b[k]; }
+            for (int k = 0; k < MB; ++k) if (k == b) { was = was_ended[k] != 0; vb = val_b[k]; if constexpr (LN) kb = key_b[k]; }
             const int tok = was ? 0 : (pre ? L.pki[b * B + j] : p.pick_idx[(size_t)(base + b) * B + j]);
             ctok[c] = tok;
             cval[c] = vb + (was ? 0.f : (pre ? L.pkv[b * B + j] : p.pick_val[(size_t)(base + b) * B + j]));
+            if constexpr (LN) q[c] = was ? kb : cval[c] * w_len;      // an ended beam's key is carried, never recomputed
             cpar[c] = b;
             cend[c] = (uint8_t)(was || tok == p.eos);
         }
@@ -695,10 +715,11 @@ __device__ __forceinline__ void beam_select_image(const SelectParams& p, const i
         if (!first) {
             for (int j = lane; j < B; j += 64) keep[j] = min(j, n - 1);
             wave_lds_sync();
+            const float* rank = LN ? q : cval;
             for (int c = lane; c < n; c += 64) {
-                const float me = cval[c];
+                const float me = rank[c];
                 int r = 0;
-                for (int j = 0; j < n; ++j) r += (cval[j] > me) || (cval[j] == me && j < c);
+                for (int j = 0; j < n; ++j) r += (rank[j] > me) || (rank[j] == me && j < c);
                 if (r < B) keep[r] = c;
             }
         }
@@ -747,6 +768,7 @@ __device__ __forceinline__ void beam_select_image(const SelectParams& p, const i
         }
         if (lane == 0) {
             p.vals[base + b] = cval[c];
+            if constexpr (LN) p.keys[base + b] = q[c];
             p.ended[base + b] = cend[c];
             p.parent[base + b] = base + par;
             p.hparent[base + b] = DT ? base + par : base + c / B;        // rnn_models.py:135-137: dense B*B layout index
@@ -1154,7 +1176,7 @@ extern "C" int dh_beam_constrain_logits(float* logits, int ldl, int V, float* gr
 
 // ------------------------------------------------------------------------------------------------
 
-template <int MB, bool PR, bool DT = false>
+template <int MB, bool PR, bool DT = false, bool LN = false>
 __global__ __launch_bounds__(64) void beam_select_kernel(SelectParams p) {
     extern __shared__ int32_t stage[];
     __shared__ int ctok[MB * MB], cpar[MB * MB], keep[MB];
@@ -1164,27 +1186,30 @@ __global__ __launch_bounds__(64) void beam_select_kernel(SelectParams p) {
     __shared__ int32_t pki[MB * MB];
     __shared__ float pkv[MB * MB];
     const SelLds L{stage, ctok, cpar, keep, cval, q, cend, &s_n, pki, pkv};
-    beam_select_image<MB, PR, DT>(p, blockIdx.x, threadIdx.x, L);
+    beam_select_image<MB, PR, DT, LN>(p, blockIdx.x, threadIdx.x, L);
 }
 
-template <bool PR, bool DT = false>
+template <bool PR, bool DT = false, bool LN = false>
 static int select_launch(const int32_t* pick_idx, const float* pick_val, int32_t* tokens, int tok_ld,
                          float* vals, uint8_t* ended, int32_t* src, int src_ld, int32_t* parent,
                          int32_t* hparent, uint8_t* done, int32_t* end_step, int n_img, int beam,
                          int first, const int32_t* first_pos, int first_sets_ended, int write_pos, int t, int step_index,
                          float temperature, int eos_index, const float* noise, uint64_t seed,
-                         const uint64_t* seed_ptr, int img0, void* stream) {
+                         const uint64_t* seed_ptr, int img0, void* stream, float* keys = nullptr, const float* len_w = nullptr,
+                         int first_col = 0) {
     DH_REQUIRE(pick_idx && pick_val && tokens && vals && ended && parent && hparent && done && end_step);
     DH_REQUIRE(n_img > 0 && beam >= 1 && beam <= DH_BEAM_MAX_BEAMS && tok_ld > 0 && t >= 0 && temperature > 0.f);
     DH_REQUIRE(!src || src_ld > t);
     DH_REQUIRE(!PR || first_pos);
-    DhProfScope prof(DT ? "dh_beam_select_best" : "dh_beam_select", 0.0, 0.0, stream);
+    DH_REQUIRE(!LN || (len_w && keys && first_col >= 0));
+    DhProfScope prof(LN ? "dh_beam_select_best_norm" : DT ? "dh_beam_select_best" : "dh_beam_select", 0.0, 0.0, stream);
     SelectParams p{pick_idx, pick_val, tokens, tok_ld, vals, ended, src, src_ld, parent, hparent, done, end_step,
-                   beam, first, first_sets_ended, write_pos, t, step_index, eos_index, img0, temperature, noise, seed, seed_ptr, first_pos};
+                   beam, first, first_sets_ended, write_pos, t, step_index, eos_index, img0, temperature, noise, seed, seed_ptr, first_pos,
+                   keys, len_w, first_col};
     const size_t lds = (size_t)beam * (tok_ld + (src ? t : 0)) * sizeof(int32_t);
     DH_REQUIRE(lds <= 56 * 1024);                         // beam * (tok_ld + t) ints of staging next to the candidate arrays
-    if (beam <= 16) hipLaunchKernelGGL((beam_select_kernel<16, PR, DT>), dim3(n_img), dim3(64), lds, (hipStream_t)stream, p);
-    else hipLaunchKernelGGL((beam_select_kernel<DH_BEAM_MAX_BEAMS, PR, DT>), dim3(n_img), dim3(64), lds, (hipStream_t)stream, p);   // beam.py:7-9: any beam_size <= top_k
+    if (beam <= 16) hipLaunchKernelGGL((beam_select_kernel<16, PR, DT, LN>), dim3(n_img), dim3(64), lds, (hipStream_t)stream, p);
+    else hipLaunchKernelGGL((beam_select_kernel<DH_BEAM_MAX_BEAMS, PR, DT, LN>), dim3(n_img), dim3(64), lds, (hipStream_t)stream, p);   // beam.py:7-9: any beam_size <= top_k
     DH_LAUNCH_CHECK();
 }
 
@@ -1224,6 +1249,24 @@ extern "C" int dh_beam_select_best(const int32_t* pick_idx, const float* pick_va
     return select_launch<false, true>(pick_idx, pick_val, tokens, tok_ld, vals, ended, src, src_ld, parent, hparent, done, end_step, n_img,
                                       beam, first, nullptr, first_sets_ended, write_pos, t, step_index, 1.f, eos_index, nullptr, 0ull, nullptr,
                                       0, stream);
+}
+
+// dh_beam_select_best with length normalisation (the LN instantiations): the `beam` candidates with the largest key = score *
+// len_w[L] stay -- len_w fp32 [tok_ld + 1], len_w[0] = 1, L = write_pos + 1 - first_col (prompted: - first_pos[img]) for a live
+// candidate; an ended beam's candidate carries the key it was kept with.  keys fp32 [rows] receives the kept candidates' keys (a first
+// step: pick_val * len_w[L]); vals keeps the raw cumulative scores.  Everything else is dh_beam_select_best's.
+extern "C" int dh_beam_select_best_norm(const int32_t* pick_idx, const float* pick_val, int32_t* tokens, int tok_ld,
+                                        float* vals, float* keys, uint8_t* ended, int32_t* src, int src_ld, int32_t* parent,
+                                        int32_t* hparent, uint8_t* done, int32_t* end_step, int n_img, int beam,
+                                        int first, const int32_t* first_pos, int first_col, const float* len_w, int first_sets_ended,
+                                        int write_pos, int t, int step_index, int eos_index, void* stream) {
+    if (first_pos)
+        return select_launch<true, true, true>(pick_idx, pick_val, tokens, tok_ld, vals, ended, src, src_ld, parent, hparent, done, end_step,
+                                               n_img, beam, 0, first_pos, first_sets_ended, write_pos, t, step_index, 1.f, eos_index, nullptr,
+                                               0ull, nullptr, 0, stream, keys, len_w, first_col);
+    return select_launch<false, true, true>(pick_idx, pick_val, tokens, tok_ld, vals, ended, src, src_ld, parent, hparent, done, end_step,
+                                            n_img, beam, first, nullptr, first_sets_ended, write_pos, t, step_index, 1.f, eos_index, nullptr,
+                                            0ull, nullptr, 0, stream, keys, len_w, first_col);
 }
 
 // ---- the reference's METHOD surface (deephumor/models/beam.py:32-108), one kernel per method ------------------------------------

@@ -956,6 +956,21 @@ def beam_select_best(pick_idx, pick_val, tokens, vals, ended, src, parent, hpare
             _ptr(first_pos), int(first_sets_ended), write_pos, t, step_index, eos_index, _stream())
 
 
+def beam_select_best_norm(pick_idx, pick_val, tokens, vals, keys, ended, src, parent, hparent, done, end_step, n_img, beam, first,
+                          first_sets_ended, write_pos, t, step_index, eos_index, len_w, first_col=0, first_pos=None):
+    """``dh_beam_select_best_norm``, ``beam_select_best`` under ``length_penalty != 0``: the candidates are ranked by ``key = score *
+    len_w[L]`` (one fp32 multiply; ``len_w`` fp32 ``[max_len + 1]``, ``L`` the columns the search has written: ``write_pos + 1 -
+    first_col``, or ``- first_pos[img]`` in a prompted batch), an ended beam by the key it was kept with; ``keys`` fp32 ``[rows]``
+    receives the kept candidates' keys, ``vals`` their raw scores."""
+    _dev(pick_idx, pick_val, tokens, vals, keys, ended, src, parent, hparent, done, end_step, len_w, first_pos)
+    assert first_pos is None or (first_pos.dtype == torch.int32 and first_pos.numel() == n_img)
+    assert keys.dtype == torch.float32 and keys.is_contiguous() and keys.numel() >= n_img * beam
+    assert len_w.dtype == torch.float32 and len_w.is_contiguous() and len_w.numel() >= tokens.stride(0) + 1
+    _launch("dh_beam_select_best_norm", _ptr(pick_idx), _ptr(pick_val), _ptr(tokens), tokens.stride(0), _ptr(vals), _ptr(keys), _ptr(ended),
+            _ptr(src), src.stride(0) if src is not None else 0, _ptr(parent), _ptr(hparent), _ptr(done), _ptr(end_step), n_img, beam,
+            int(first), _ptr(first_pos), int(first_col), _ptr(len_w), int(first_sets_ended), write_pos, t, step_index, eos_index, _stream())
+
+
 def beam_history_logits(logits, v, tokens, tok_row_mult, pos, rows, rows_per_img, ngram, penalty, group_max=None, first_pos=None):
     """``dh_beam_history_logits``: the ``no_repeat_ngram_size`` / ``repetition_penalty`` edits of fp32 ``logits [rows, V]`` in place,
     from every row's own history ``tokens[r * tok_row_mult, :pos]`` (int32); with ``group_max`` the 64-column group maxima of every

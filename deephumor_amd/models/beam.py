@@ -137,6 +137,97 @@ def check_search(search, top_p=1.0):
     return search
 
 
+MAX_LENGTH_PENALTY = 8.0
+
+
+def length_weights(length_penalty, max_len):
+    """The weight table of ``length_penalty``: ``w[0] = 1`` and ``w[L] = float32(float64(L) ** -length_penalty)`` for ``L = 1 ..
+    max_len`` -- the power in fp64 on the host, rounded ONCE to fp32 -- as an fp32 CPU tensor of ``max_len + 1`` entries.  The select
+    kernel multiplies by it and computes no power itself, so a CPU restatement is bit-exact."""
+    w = [1.0] + [math.pow(float(n), -float(length_penalty)) for n in range(1, int(max_len) + 1)]
+    return torch.tensor(w, dtype=torch.float64).to(torch.float32)
+
+
+def check_length_penalty(length_penalty, max_len=None, search=None):
+    """``length_penalty`` is a finite real number with ``abs(length_penalty) <= 8`` (0.0: off, the call without it; a ``bool`` or a
+    non-number is a ``TypeError``): checked where ``check_search`` is, before anything runs.  With ``max_len``, a value for which some
+    ``w[1 .. max_len]`` (``length_weights``) is not a normal, finite fp32 number is a ``ValueError``; with ``search``, a non-zero value
+    under anything but ``"beam"`` is one too -- the sampled search draws its candidates and ranks nothing.  Returns it as a float."""
+    lp = length_penalty
+    if isinstance(lp, bool) or not isinstance(lp, numbers.Real):
+        raise TypeError(f"length_penalty must be a real number, not {type(lp).__name__}")
+    lp = float(lp)
+    if not math.isfinite(lp) or abs(lp) > MAX_LENGTH_PENALTY:
+        raise ValueError(f"length_penalty must be finite with abs(length_penalty) <= {MAX_LENGTH_PENALTY:g}, got {lp}")
+    lp += 0.0                                               # (-0.0 is 0.0: one key, one graph)
+    if lp != 0.0 and search is not None and search != "beam":
+        raise ValueError(f'length_penalty={lp} belongs to search="beam" (it ranks the candidates the deterministic search keeps); '
+                         f'search="{search}" draws its candidates and ranks nothing -- use length_penalty=0.0 there')
+    if lp != 0.0 and max_len is not None:
+        w = length_weights(lp, max_len)[1:]
+        tiny = float(torch.finfo(torch.float32).tiny)
+        if not bool((torch.isfinite(w) & (w >= tiny)).all()):
+            raise ValueError(f"length_penalty={lp} at max_len={int(max_len)}: a weight L ** -length_penalty leaves the normal fp32 range")
+    return lp
+
+
+_LEN_W_CACHE = {}               # (device, length_penalty, max_len) -> fp32 device table: uploaded once, not once per session
+_LEN_W_CACHE_SIZE = 16          # least recently used out; a table in use is owned by its helper (and by a captured graph's state)
+
+
+def compile_length_weights(length_penalty, max_len, device="cuda"):
+    """``length_weights`` on ``device``, uploaded once per ``(device, length_penalty, max_len)`` (a small cache, like
+    ``compile_bad_words``; a hit makes the entry the most recently used one).  Not inside a hipGraph capture (a host-to-device copy):
+    ``generate_batch_graphed`` uploads in front of it.  The cache owns a table only until it is evicted: whoever launches with it
+    holds the tensor -- the helper for its session, a captured graph through ``held_length_weights``."""
+    device = torch.device(device)
+    if device.type == "cuda" and device.index is None:
+        device = torch.device("cuda", torch.cuda.current_device())
+    key = (str(device), float(length_penalty), int(max_len))
+    w = _LEN_W_CACHE.get(key)
+    if w is None:
+        if device.type == "cuda" and torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("compile_length_weights inside a hipGraph capture: upload the table before the capture")
+        w = length_weights(length_penalty, max_len).to(device)
+        while len(_LEN_W_CACHE) >= _LEN_W_CACHE_SIZE:
+            _LEN_W_CACHE.pop(next(iter(_LEN_W_CACHE)))
+    else:
+        _LEN_W_CACHE.pop(key)                               # most recently used last
+    _LEN_W_CACHE[key] = w
+    return w
+
+
+def held_length_weights(length_penalty, device):
+    """Every cached table of ``length_penalty`` on ``device``, for a captured hipGraph to keep: its ``dh_beam_select_best_norm`` nodes
+    hold the raw pointer of the table their session found here, and the cache alone would free it at the next eviction.  ``()`` for
+    0.0."""
+    if float(length_penalty) == 0.0:
+        return ()
+    device = torch.device(device)
+    if device.type == "cuda" and device.index is None:
+        device = torch.device("cuda", torch.cuda.current_device())
+    return tuple(w for (dev, lp, _), w in _LEN_W_CACHE.items() if dev == str(device) and lp == float(length_penalty))
+
+
+class _Search(str):
+    """``DecodeSettings.search`` of a call with ``length_penalty != 0``: the same string, with the penalty riding on it -- the record's
+    field list is fixed, and ``dataclasses.replace`` rebuilds a record from its field values alone.  So ``replace(s, search="beam")``
+    (a plain string) is the record WITHOUT the penalty, and the penalty is only ever put here by ``from_kw``, which reads the
+    ``length_penalty`` keyword and takes ``search`` as the plain string it spells.  Copies and pickles like the pair it is."""
+    length_penalty = 0.0
+
+    def __new__(cls, search, length_penalty=0.0):
+        self = str.__new__(cls, search)
+        self.length_penalty = length_penalty
+        return self
+
+    def __getnewargs__(self):
+        return (str.__str__(self), self.length_penalty)
+
+    def __reduce__(self):
+        return (_Search, self.__getnewargs__())
+
+
 def check_repeat(no_repeat_ngram_size=0, repetition_penalty=1.0, max_len=None):
     """``no_repeat_ngram_size`` is an ``int >= 0`` (0: off; a ``bool`` is a misplaced flag, a float a ``TypeError``) and
     ``repetition_penalty`` a finite real number ``> 0`` (1.0: off; no ``bool``): checked where ``check_top_p`` is, before anything
@@ -297,7 +388,9 @@ class DecodeSettings:
     tuple of tuples, or a ``BadWords``), ``num_tokens``, the vocabulary the list was checked against, and ``search`` (``check_search``;
     behind ``num_tokens`` and with a default, so the positional order of the others is what it was) and ``return_logprobs``
     (``check_return_logprobs``; the last one, for the same reason -- the constructor's last parameter, kept by ``replace``, in the key;
-    an init-only field stored by ``__post_init__``, because ``dataclasses.fields`` is pinned to end at ``search``).  Built by
+    an init-only field stored by ``__post_init__``, because ``dataclasses.fields`` is pinned to end at ``search``).
+    ``length_penalty`` (``check_length_penalty``; 0.0: off) is a plain attribute, not a field -- the field list above is fixed --: set by
+    ``from_kw``, carried by ``search`` (``_Search``) so that ``replace`` and ``compiled`` keep it, and in the key.  Built by
     ``from_kw`` only.  Immutable; equal and hashed by the settings, the list by its ids whether compiled or not."""
     return_beams: bool = False
     return_attention: bool = False
@@ -312,25 +405,29 @@ class DecodeSettings:
 
     def __post_init__(self, return_logprobs):
         object.__setattr__(self, "return_logprobs", return_logprobs)
+        object.__setattr__(self, "length_penalty", getattr(self.search, "length_penalty", 0.0))
 
     @classmethod
     def from_kw(cls, kw, max_len, num_tokens=None, model=None):
         """Reads the settings out of the keyword dictionary ``kw`` (which keeps them) and checks them in this order -- ``search``, then
-        ``return_logprobs`` last --, so a call with two bad values raises for the earlier one; ``model``: see
+        ``return_logprobs``, then ``length_penalty`` last --, so a call with two bad values raises for the earlier one; ``model``: see
         ``check_return_attention`` / ``check_return_logprobs``."""
         return_beams = check_return_beams(kw.get("return_beams", False))
         return_attention = check_return_attention(kw.get("return_attention", False), model)
         top_p = check_top_p(kw.get("top_p", 1.0))
         ngram, penalty = check_repeat(kw.get("no_repeat_ngram_size", 0), kw.get("repetition_penalty", 1.0), max_len)
         min_len, bad_words = check_constraints(kw.get("min_len", 0), kw.get("bad_words_ids"), max_len, num_tokens)
-        search = check_search(kw.get("search", "sample"), top_p)
+        search = str(check_search(kw.get("search", "sample"), top_p))      # (the plain string: a penalty comes from its keyword alone)
         return_logprobs = check_return_logprobs(kw.get("return_logprobs", False), model)
+        length_penalty = check_length_penalty(kw.get("length_penalty", 0.0), max_len, search)
+        if length_penalty != 0.0:
+            search = _Search(search, length_penalty)
         return cls(return_beams, return_attention, top_p, ngram, penalty, min_len, bad_words, num_tokens, search, return_logprobs)
 
     def _key(self):
         bw = self.bad_words_ids
         return (self.return_beams, self.return_attention, self.top_p, self.no_repeat_ngram_size, self.repetition_penalty, self.min_len,
-                bw.ids if isinstance(bw, BadWords) else bw, self.return_logprobs, self.search)
+                bw.ids if isinstance(bw, BadWords) else bw, self.length_penalty, self.return_logprobs, self.search)
 
     def __eq__(self, other):
         return isinstance(other, DecodeSettings) and self._key() == other._key()
@@ -340,13 +437,14 @@ class DecodeSettings:
 
     def compiled(self, device):
         """The record with its phrase list uploaded to ``device`` (``compile_bad_words``: once per list, not inside a capture)."""
+        # (``length_penalty`` rides on ``search`` and so stays; its table is uploaded by ``compile_length_weights``, per session length)
         return dataclasses.replace(self, bad_words_ids=compile_bad_words(self.bad_words_ids, self.num_tokens, device))
 
     def new_helper(self, **engine_args):
         """The ``BeamSearchHelper`` of one session with every setting applied; ``engine_args``: the constructor's other arguments."""
         return BeamSearchHelper(top_p=self.top_p, no_repeat_ngram_size=self.no_repeat_ngram_size, repetition_penalty=self.repetition_penalty,
                                 **engine_args).set_constraints(self.min_len, self.bad_words_ids).set_search(self.search).set_logprobs(
-                                    self.return_logprobs)
+                                    self.return_logprobs).set_length_penalty(self.length_penalty)
 
 
 class BeamOverflow(RuntimeError):
@@ -523,9 +621,21 @@ class BeamSearchHelper:
     ``<eos>`` for every decoder kind); ``finalize`` returns the beam with the largest score.  ``top_k`` keeps its assertion and has no
     other effect; ``seed``, ``noise_source`` and ``exact`` have none: no noise is generated or consumed, two calls return the same
     bits, and there is no overflow case.  ``vals`` -- ``BeamCaptions.scores`` -- are cumulative model log-probabilities of the tokens
-    the rows hold: a step that writes no token column (``write_pos`` past the table: the Transformer decoders' last) is skipped.  Length
-    normalisation is out of scope: ``return_beams=True`` plus ``experiments.rank_beams`` re-ranks.  All launch constants, so it
-    captures into a hipGraph like the rest.
+    the rows hold: a step that writes no token column (``write_pos`` past the table: the Transformer decoders' last) is skipped.  All launch
+    constants, so it captures into a hipGraph like the rest.
+
+    ``length_penalty`` (with ``search="beam"`` only; ``helper.set_length_penalty(value)`` after construction, behind ``set_search``):
+    the select ranks by the length-normalised ``key = fp32(score * w[L])`` in place of the score, inside the pruning.  ``L`` is the
+    number of columns the search itself has written to a beam, from the image's first generated column (the dense first step's
+    ``write_pos``; ``first_pos[i]`` in a prompted session) through its own first ``<eos>``; ``w[L] = float32(float64(L) **
+    -length_penalty)``, ``w[0] = 1``, is computed on the host and uploaded once as ``len_w`` fp32 ``[max_len + 1]`` (no power runs on
+    the device).  Scores are ``<= 0``: a value ``> 0`` favours longer captions, ``< 0`` shorter ones.  A live beam's ``beam_size``
+    candidates take ``w[write_pos + 1 - first column]``; an ended beam's candidate carries the key it was kept with, never recomputed.
+    The candidates with the largest key stay, equal keys to the lower candidate index, ``-inf`` last (``dh_beam_select_best_norm`` in
+    place of ``dh_beam_select_best``); the kept keys go to ``keys`` fp32 ``[rows]``, ``vals`` stays the raw cumulative log-probability,
+    and ``finalize`` orders by ``keys``: ``BeamCaptions.scores`` are the keys.  With ``return_logprobs`` the left-to-right fp32 sum of a
+    live beam's own columns, times ``w[L]``, is its score bit for bit.  ``0.0``, the default: no table, no ``keys``, today's launches
+    and bits.
 
     ``return_logprobs`` (not in the reference either; ``helper.set_logprobs(True)`` after construction): the model log-probability of
     every token the search writes, with nothing shuffled per step.  In front of whichever select a step runs, one launch of
@@ -549,6 +659,7 @@ class BeamSearchHelper:
         self.min_len, self.bad_words, self._constraints = 0, None, False      # min_len / bad_words_ids: set_constraints
         self.search = "sample"            # "beam": set_search
         self.logprobs, self.pick_lp, self.lp_w, self.par_w = False, None, None, None      # return_logprobs: set_logprobs
+        self.length_penalty, self.len_w, self.keys, self.first_col = 0.0, None, None, 0   # length_penalty: set_length_penalty
         self.exact = bool(exact)          # row draws through the general sampler only (see BeamOverflow)
         if beam_size > hip.MAX_BEAMS:     # one wave draws among an image's beams (dh_beam_finalize); the reference has no limit
             raise ValueError(f"beam_size <= {hip.MAX_BEAMS} supported")
@@ -619,6 +730,19 @@ class BeamSearchHelper:
             self.par_w = arena[n_pos * r:2 * n_pos * r].view(n_pos, r)
             self.par_w += torch.arange(r, dtype=torch.int32, device=self.device)
             self.pick_lp = arena[2 * n_pos * r:].view(torch.float32).view(r, self.beam_size)
+        return self
+
+    def set_length_penalty(self, length_penalty=0.0):
+        """``length_penalty`` of this session (see the class docstring), validated by ``check_length_penalty`` against the helper's
+        ``max_len`` and ``search`` (so behind ``set_search``).  Non-zero: the weight table ``len_w`` fp32 ``[max_len + 1]``
+        (``compile_length_weights``: one upload per value and length, so not inside a hipGraph capture unless it is cached) and the
+        zeroed per-row state ``keys`` fp32 ``[rows]``.  Zero, the default: nothing is allocated and no launch changes.  A method like
+        ``set_search``: the constructor's parameter list stays as it is.  Returns the helper."""
+        self.length_penalty = check_length_penalty(length_penalty, self.max_len, self.search)
+        self.len_w = self.keys = None
+        if self.length_penalty != 0.0:
+            self.len_w = compile_length_weights(self.length_penalty, self.max_len, self.device)
+            self.keys = torch.zeros((self.n_img * self.beam_size,), dtype=torch.float32, device=self.device)
         return self
 
     def set_prefix(self, caption):
@@ -700,9 +824,18 @@ class BeamSearchHelper:
             if self.logprobs:             # the bits the row step left in pick_val, zero for the rows that have ended
                 hip.beam_pick_logprobs(None, v, rows, rpi, b, self.temperature, step_index, self._ended, self.pick_idx, self.pick_val,
                                        self.pick_lp, from_vals=True, first_pos=first_pos)
-            hip.beam_select_best(self.pick_idx, self.pick_val, self.tokens, self.vals, self._ended, self.src, self.parent, self.hparent,
-                                 self.done, self.end_step, self.n_img, b, first, True, write_pos, t, step_index, self.eos_index,
-                                 first_pos=first_pos)
+            if self.length_penalty != 0.0:
+                # the rank on key = score * len_w[L]; L counts from the image's first generated column: the dense first step's
+                # write_pos, or a prompted session's first_pos (also behind its longest prompt, where the steps are dense again)
+                if first:
+                    self.first_col = write_pos
+                hip.beam_select_best_norm(self.pick_idx, self.pick_val, self.tokens, self.vals, self.keys, self._ended, self.src,
+                                          self.parent, self.hparent, self.done, self.end_step, self.n_img, b, first, True, write_pos, t,
+                                          step_index, self.eos_index, self.len_w, first_col=self.first_col, first_pos=self.first_pos)
+            else:
+                hip.beam_select_best(self.pick_idx, self.pick_val, self.tokens, self.vals, self._ended, self.src, self.parent, self.hparent,
+                                     self.done, self.end_step, self.n_img, b, first, True, write_pos, t, step_index, self.eos_index,
+                                     first_pos=first_pos)
             if self.logprobs:
                 hip.beam_record_logprobs(self.tokens, self.parent, self.done, self.end_step, self.pick_idx, self.pick_lp, self.n_img, b,
                                          first, write_pos, step_index, self.lp_w, self.par_w, first_pos=first_pos)
@@ -775,7 +908,7 @@ class BeamSearchHelper:
             ints = torch.empty((2 * n * b + 2 * n,), dtype=torch.int32, device=dev)
             o_len, o_idx, o_drawn, o_row = ints[:n * b].view(n, b), ints[n * b:2 * n * b].view(n, b), ints[2 * n * b:2 * n * b + n], ints[2 * n * b + n:]
             o_score = torch.empty((n, b), dtype=torch.float32, device=dev)
-            hip.beam_finalize_beams(self.tokens, self.vals, self.done, self.end_step, out, o_len, o_score, o_idx, o_drawn, o_row, n, b,
+            hip.beam_finalize_beams(self.tokens, self.vals if self.keys is None else self.keys, self.done, self.end_step, out, o_len, o_score, o_idx, o_drawn, o_row, n, b,
                                     len_bias_done, full_len, pad_index, self.eos_index, pos, self.first_pos,
                                     self.temperature, noise, self.seed, self.img0, seed_ptr=self.seed_tensor)
             attention = None

@@ -11,7 +11,8 @@ from torch import nn
 
 from .. import hip
 from ._f32x_guard import f32x_guarded
-from .beam import BeamCaptions, BeamOverflow, BeamSearchHelper, DecodeSettings, check_ids, check_prompts, prompts_need_philox, resolve_seed, warn_overflow_retry
+from .beam import (BeamCaptions, BeamOverflow, BeamSearchHelper, DecodeSettings, check_ids, check_prompts, compile_length_weights, held_length_weights, prompts_need_philox,
+                   resolve_seed, warn_overflow_retry)
 from .encoders import ImageEncoder, ImageLabelEncoder, SpatialImageLabelEncoder, _Planned
 from .rnn_models import LSTMDecoder
 from .transformers import SelfAttentionTransformerDecoder, TransformerDecoder, _IncrementalDecoder
@@ -74,7 +75,10 @@ class _CaptioningBase(nn.Module):
         ``(BeamCaptions, logprobs [N, B, T])`` with ``return_beams=True``; ``log_softmax(logits / temperature)`` at the token, on the
         row it was taken from, behind the history edits and the bans and in front of the top-k / nucleus / ``<unk>`` filtering; filled
         from the first generated column up to the beam's own length, exactly 0 elsewhere (``LSTMDecoder.generate_batch`` has the full
-        contract).  It changes no token; ``pad_index == 1`` raises ``NotImplementedError`` (``beam.check_return_logprobs``)."""
+        contract).  It changes no token; ``pad_index == 1`` raises ``NotImplementedError`` (``beam.check_return_logprobs``).
+        ``length_penalty`` (in ``kw``, with ``search="beam"``; default 0.0, the call without it): the search ranks its candidates by the
+        length-normalised ``score * L ** -length_penalty`` inside the pruning, ``L`` the generated length; ``BeamCaptions.scores`` are
+        those keys (``LSTMDecoder.generate_batch`` has the full contract)."""
         if caption_lengths is not None:
             kw["caption_lengths"] = caption_lengths
         return self.decoder.generate_batch(*encoded, caption=caption, max_len=max_len, temperature=temperature,
@@ -89,6 +93,8 @@ class _CaptioningBase(nn.Module):
             kw.pop("return_attention", None)      # (off, it is the call without the keyword -- also for the kinds whose decoders do not know it)
         if not settings.return_logprobs:
             kw.pop("return_logprobs", None)       # (off, it is the call without the keyword)
+        if settings.length_penalty == 0.0:
+            kw.pop("length_penalty", None)        # (the same)
         if caption_lengths is None:
             return None
         if getattr(self.decoder, "pad_index", 0) == 1:
@@ -108,6 +114,13 @@ class _CaptioningBase(nn.Module):
         return tuple(t.data_ptr() for t in ts), tuple(t._version for t in ts), hip.options_epoch
 
     MAX_GRAPHS = 4      # captured graphs kept per model (one per (input shapes, decode settings))
+
+    @staticmethod
+    def _graph_state(graph, static, scap, seed_t, out, sig, plans, slens, length_penalty=0.0, device="cuda"):
+        """What ``generate_batch_graphed`` caches per captured graph: the graph, its static inputs, its outputs, the plan signature and
+        everything the captured nodes point at that nothing else owns -- the weight plans and, last, the ``length_penalty`` weight
+        tables the capture's sessions launched with (``beam.held_length_weights``; ``()`` without a penalty)."""
+        return (graph, static, scap, seed_t, out, sig, plans, slens, held_length_weights(length_penalty, device))
 
     def generate_batch_graphed(self, *inputs, seed=None, caption=None, caption_lengths=None, **kw):
         """``generate_batch`` replayed from a captured hipGraph (torch.cuda.CUDAGraph on ROCm).
@@ -141,6 +154,14 @@ class _CaptioningBase(nn.Module):
             kw.pop("return_attention", None)          # (False is the call without the keyword: the plain graph, not a second one)
         if not settings.return_logprobs:
             kw.pop("return_logprobs", None)           # (the same)
+        # ``length_penalty`` (dh_beam_select_best_norm nodes in place of dh_beam_select_best): 0.0 is the call without the keyword, any
+        # other value -- as the float the check returns -- is in the key below, and its weight table is uploaded HERE, in front of any
+        # capture (the sessions inside find it in ``compile_length_weights``' cache).  The captured nodes hold the table's raw pointer:
+        # the graph's cached state keeps the tensor (``_graph_state``), the cache alone would free it at its next eviction
+        kw.pop("length_penalty", None)
+        if settings.length_penalty != 0.0:
+            kw["length_penalty"] = settings.length_penalty
+            compile_length_weights(settings.length_penalty, kw.get("max_len", 25), inputs[0].device)
         # The list is compiled HERE, in front of any capture -- no host-to-device copy happens inside one -- and the ``BadWords``
         # replaces the raw nesting in ``kw``: it is hashable, so it is in the key below, and the captured closure keeps its two
         # tensors alive
@@ -207,7 +228,8 @@ class _CaptioningBase(nn.Module):
             plans = [m._get_plan() for m in self.modules() if isinstance(m, _Planned)]     # outlive the graph
             while len(cache) >= self.MAX_GRAPHS:          # every graph keeps its activations / KV cache allocated: oldest out
                 cache.pop(next(iter(cache)))
-            state = cache[key] = (graph, static, scap, seed_t, out, sig, plans, slens)
+            state = cache[key] = self._graph_state(graph, static, scap, seed_t, out, sig, plans, slens,
+                                                   length_penalty=settings.length_penalty, device=inputs[0].device)
         else:
             cache[key] = cache.pop(key)                   # most recently used last
         graph, static, scap, seed_t, out = state[:5]

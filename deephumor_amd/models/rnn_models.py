@@ -190,7 +190,7 @@ class LSTMDecoder(_Planned, nn.Module):
         hs.mul_(valid[..., None])          # pad_packed_sequence zero rows (mask, not arithmetic on valid rows)
         return hs, bs, steps_out
 
-    @_later_keywords("min_len", "bad_words_ids", "search", "return_logprobs")
+    @_later_keywords("min_len", "bad_words_ids", "search", "return_logprobs", "length_penalty")
     def generate_batch(self, image_emb, caption=None, max_len=25, temperature=1.0, beam_size=10, top_k=50,
                        eos_index=3, seed=None, img0=0, noise_source=None, logits_hook=None, streams=1, seed_tensor=None,
                        defer_check=False, early_stop_every=0, exact=False, rng=None, *, caption_lengths=None, return_beams=False, top_p=1.0,
@@ -241,8 +241,14 @@ class LSTMDecoder(_Planned, nn.Module):
         whatever ``seed``, ``rng`` and ``noise_source`` are (accepted, unused: no noise is generated or consumed).  ``top_k`` keeps
         its assertion ``beam_size <= top_k`` and filters nothing; ``top_p < 1`` is a ``ValueError``.  With ``return_beams=True`` the
         ``scores`` are cumulative model log-probabilities and ``drawn`` is 0.  Two launches per position (``dh_beam_row_best``,
-        ``dh_beam_select_best``) in place of the sampled pair (``BeamSearchHelper``).  No length normalisation: ``return_beams=True``
-        plus ``experiments.rank_beams`` re-ranks.
+        ``dh_beam_select_best``) in place of the sampled pair (``BeamSearchHelper``).
+        ``length_penalty`` (keyword only, with ``search="beam"``; a finite number, ``abs <= 8``; ``beam.check_length_penalty``): every
+        select ranks its candidates by ``key = fp32(score * w[L])`` in place of the score -- ``L`` the columns the search has written
+        to the beam, from the image's first generated column through its own first ``<eos>``, ``w[L] = float32(float64(L) **
+        -length_penalty)`` from a host-made table --, inside the pruning; an ended beam keeps the key it was kept with.  Scores are
+        ``<= 0``: ``> 0`` favours longer captions, ``< 0`` shorter ones.  ``BeamCaptions.scores`` are the keys, slot 0 the largest.
+        ``dh_beam_select_best_norm`` in place of ``dh_beam_select_best``; ``0.0``, the default, is the call without the keyword: same
+        launches, same bits.  Non-zero with ``search="sample"``: ``ValueError``.
         ``return_logprobs=True`` (keyword only, a plain bool; ``beam.check_return_logprobs``): one more result, last in the tuple, an
         fp32 device tensor with the model's log-probability of every token the search wrote -- ``(tokens, lengths, logprobs [N, T])``,
         or ``(BeamCaptions, logprobs [N, B, T])`` with ``return_beams=True`` in ``BeamCaptions`` slot order.  ``logprobs[i, (slot,) c]``
@@ -255,7 +261,7 @@ class LSTMDecoder(_Planned, nn.Module):
         unspecified values, never NaN.  It changes no token; ``False``, the default, is the call without the keyword: same launches,
         same bits.  On: three launches of their own (``dh_beam_pick_logprobs`` in front of and ``dh_beam_record_logprobs`` behind every
         select, ``dh_beam_gather_logprobs`` behind the final draw; ``BeamSearchHelper``).
-        ``min_len``, ``bad_words_ids``, ``search`` and ``return_logprobs`` are not in the parameter list above, which ends at
+        ``min_len``, ``bad_words_ids``, ``search``, ``return_logprobs`` and ``length_penalty`` are not in the parameter list above, which ends at
         ``repetition_penalty`` as it did: they are taken by name (``_later_keywords``) and handed to ``_decode_session``, the
         implementation, which spells every keyword out."""
         return self._generate_batch(image_emb, caption, max_len, temperature, beam_size, top_k, eos_index, seed, img0, noise_source,
@@ -294,11 +300,12 @@ class LSTMDecoder(_Planned, nn.Module):
                         eos_index=3, seed=None, img0=0, noise_source=None, logits_hook=None, streams=1, seed_tensor=None,
                         defer_check=False, early_stop_every=0, exact=False, rng=None, *, caption_lengths=None, return_beams=False, top_p=1.0,
                         no_repeat_ngram_size=0, repetition_penalty=1.0, min_len=0, bad_words_ids=None, search="sample",
-                        return_logprobs=False):
+                        return_logprobs=False, length_penalty=0.0):
         """The implementation of ``generate_batch``, every keyword spelled out."""
         settings = DecodeSettings.from_kw(dict(return_beams=return_beams, top_p=top_p, no_repeat_ngram_size=no_repeat_ngram_size,
                                                repetition_penalty=repetition_penalty, min_len=min_len, bad_words_ids=bad_words_ids,
-                                               search=search, return_logprobs=return_logprobs), max_len, self.num_tokens)
+                                               search=search, return_logprobs=return_logprobs, length_penalty=length_penalty),
+                                          max_len, self.num_tokens)
         if settings.search == "beam":     # nothing is drawn: no generator is read, no noise source is asked
             rng, noise_source, seed = None, None, 0
         self._check_mode()

@@ -583,6 +583,22 @@ int dh_beam_select_best(const int32_t* pick_idx, const float* pick_val, int32_t*
                         int first, const int32_t* first_pos, int first_sets_ended, int write_pos, int t, int step_index,
                         int eos_index, void* stream);
 
+/* dh_beam_select_best with length normalisation (search="beam", length_penalty != 0): the same candidate list in the same order, ranked
+ * by key = score * len_w[L] (ONE fp32 multiply of the fp32 score; -inf stays -inf) instead of the score.  len_w: fp32 [tok_ld + 1], the
+ * caller's table (len_w[0] = 1, len_w[L] = L ** -length_penalty rounded once from fp64, every entry a positive normal number); no powf
+ * runs on the device.  L = write_pos + 1 - first_col for every live candidate of an image -- first_col the image's first generated
+ * column: the argument for a dense batch, first_pos[img] for a prompted one (first_col is then not read) -- clamped to [0, tok_ld].
+ * An ended beam's candidate carries keys[its row], the key it was kept with, never recomputed at the current L.  The `beam` candidates
+ * with the largest key stay, equal keys to the lower candidate index, -inf last; keys [rows] receives the kept candidates' keys and vals
+ * their raw cumulative scores.  A first step ranks nothing and stores keys = pick_val * len_w[L] (L = 1 there).  A forced or a done image
+ * leaves keys untouched.  ended, done, end_step, parent, hparent, src and the token rows are dh_beam_select_best's.
+ * len_w, keys != NULL and first_col >= 0 are required. */
+int dh_beam_select_best_norm(const int32_t* pick_idx, const float* pick_val, int32_t* tokens, int tok_ld,
+                             float* vals, float* keys, uint8_t* ended, int32_t* src, int src_ld, int32_t* parent,
+                             int32_t* hparent, uint8_t* done, int32_t* end_step, int n_img, int beam,
+                             int first, const int32_t* first_pos, int first_col, const float* len_w, int first_sets_ended,
+                             int write_pos, int t, int step_index, int eos_index, void* stream);
+
 /* ---- History-dependent logit edits in front of a row draw: no_repeat_ngram_size and repetition_penalty, IN PLACE on fp32 logits
  * [rows, ldl], one launch.  Logits row r reads its history h[0 .. pos) from tokens[r * tok_row_mult, 0 .. pos) (int32, row stride tok_ld):
  * tok_row_mult = beam for the dense first step (logits [n_img, V], image i's tokens at row i * beam), 1 otherwise.  Ids outside [0, V)
