@@ -594,6 +594,10 @@ struct SelectParams {
     float* keys = nullptr;                              // dh_beam_select_best_norm: [rows] the kept candidates' keys (score * len_w[L])
     const float* len_w = nullptr;                       //   [tok_ld + 1] weights by generated length, len_w[0] = 1
     int first_col = 0;                                  //   dense: the first generated column (prompted: first_pos[img])
+    int32_t* pool_tokens = nullptr;                     // dh_beam_select_pool: [n_img, beam, tok_ld] the finished hypotheses, slot 0 the best
+    float* pool_keys = nullptr; float* pool_vals = nullptr;     //   [n_img, beam] their keys (descending) and raw scores
+    int32_t* pool_len = nullptr; int32_t* pool_n = nullptr;     //   [n_img, beam] their lengths (<eos> included), [n_img] entries held
+    int stop_when_full = 0;                             //   early_stopping=True: done as soon as the pool is full
 };
 
 // LDS scratch of one image's candidate draw, carved by the caller (beam_select_kernel's own arrays)
@@ -601,6 +605,7 @@ struct SelLds {
     int32_t* stage;                                     // [beam][tok_ld] tokens, then [beam][t] ancestors
     int* ctok; int* cpar; int* keep; float* cval; float* q; uint8_t* cend; int* s_n;
     int32_t* pki = nullptr; float* pkv = nullptr;       // optional [beam * beam]: the image's picks, brought in with the first round trip
+    int* ord = nullptr; int* offer = nullptr;           // dh_beam_select_pool: [2 * beam] candidates by rank, [beam] the <eos> candidates offered
 };
 
 // The candidate draw + in-place rewrite of one image's beam state, executed by ONE wave (lane = 0..63); LDS hand-overs are
@@ -614,9 +619,118 @@ struct SelLds {
 // columns the search has written to a live candidate, is write_pos + 1 - (the image's first generated column), the same for every live
 // candidate of the image, so len_w[L] is one wave-uniform load.  An ended beam's candidate keeps the key it was kept with (p.keys,
 // loaded with vals and ended); q holds the keys, the kept ones go to p.keys, and p.vals keeps the raw scores.
-template <int MB, bool PR = false, bool DT = false, bool LN = false>
+// PL (dh_beam_select_pool, with DT and LN): what follows the candidate list of an image under early_stopping -- the rank, the walk over
+// it, the pool insertion, the rewrite and the done rule.  n candidates stand in ctok / cval / cpar with their keys in q.
+//   rank   : ord[r] = the candidate of rank r for r < min(n, 2 * beam): larger key first, equal keys to the lower candidate index (a first
+//            step keeps pick order).  At most `beam` candidates are <eos> (one per live row), so 2 * beam ranks hold `beam` others.
+//   walk   : 64 ranks per round, a ballot each for "takes a live slot" (not <eos>, key > -inf) and "offered" (<eos>, rank < beam, key >
+//            -inf); a candidate's slot / offer number is the count of set bits below its lane: rank order, no atomics.
+//   rewrite: slot b < taken as the LN select writes a kept candidate, with ended = 0; the others are dead slots -- their own row with
+//            token 0, vals = keys = -inf, ended = 1, parent = hparent = src[.., t] = themselves (at a first step: the image's base row).
+//   pool   : lane j holds entry j's key / score / length in registers; an offer goes behind every entry with key >= its own (ballot),
+//            the entries below move one down (register shuffles; the token rows from the bottom up, each lane its own columns: plain
+//            vector stores in a fixed order) and entry `beam` falls off -- a full pool is entered only strictly above its worst key.
+//   done   : the pool is full, and early_stopping is True or the pool's worst key >= live slot 0's (-inf for a dead slot).
+template <int MB>
+__device__ __forceinline__ void beam_pool_tail(const SelectParams& p, const int img, const int lane, const SelLds& L, const int n,
+                                               const int first, const bool pre) {
+    const int B = p.beam, base = img * B;
+    int* ctok = L.ctok; int* cpar = L.cpar; int* keep = L.keep; float* cval = L.cval; float* q = L.q;
+    int* ord = L.ord; int* offer = L.offer;
+    // the pool's scalars, in flight while the rank runs
+    int n_pool = min(max(p.pool_n[img], 0), B);
+    float pk = -INFINITY, pv = -INFINITY;
+    int pl = 0;
+    if (lane < B) { pk = p.pool_keys[base + lane]; pv = p.pool_vals[base + lane]; pl = p.pool_len[base + lane]; }
+    const int nr = min(n, 2 * B);
+    for (int r = lane; r < nr; r += 64) ord[r] = r;        // (every entry valid whatever the keys are, as `keep` in the other selects)
+    wave_lds_sync();
+    if (!first) {
+        for (int c = lane; c < n; c += 64) {
+            const float me = q[c];
+            int r = 0;
+            for (int j = 0; j < n; ++j) r += (q[j] > me) || (q[j] == me && j < c);
+            if (r < nr) ord[r] = c;
+        }
+        wave_lds_sync();
+    }
+    int taken = 0, n_off = 0;                             // (wave-uniform)
+    const unsigned long long below = (1ull << lane) - 1ull;
+    for (int r0 = 0; r0 < nr; r0 += 64) {
+        const int r = r0 + lane;
+        bool live = false, off = false;
+        int c = 0;
+        if (r < nr) {
+            c = ord[r];
+            const bool fin = q[c] > -INFINITY, eos = ctok[c] == p.eos;
+            live = fin && !eos;
+            off = fin && eos && r < B;
+        }
+        const unsigned long long lb = __ballot(live), ob = __ballot(off);
+        if (live) { const int s = taken + __popcll(lb & below); if (s < B) keep[s] = c; }
+        if (off) offer[n_off + __popcll(ob & below)] = c;  // (only ranks < beam are offered: at most `beam` entries)
+        taken += __popcll(lb); n_off += __popcll(ob);
+    }
+    taken = min(taken, B);
+    int32_t* tokbuf = L.stage;
+    int32_t* srcbuf = L.stage + (size_t)B * p.tok_ld;
+    if (!pre) {
+        for (int i = lane; i < B * p.tok_ld; i += 64) tokbuf[i] = p.tokens[(size_t)base * p.tok_ld + i];
+        if (p.src)
+            for (int b = 0; b < B; ++b)
+                for (int j = lane; j < p.t; j += 64) srcbuf[b * p.t + j] = p.src[(size_t)(base + b) * p.src_ld + j];
+    }
+    wave_lds_sync();
+    for (int b = 0; b < B; ++b) {
+        const bool dead = b >= taken;
+        const int c = dead ? 0 : keep[b];
+        // (a first step: only the image's base row has history behind it -- LSTM state, KV cache --, so a dead slot points there, like
+        //  the rows of a forced image; its token row is the base row's, which holds the same prefix)
+        const int par = dead ? (first ? 0 : b) : cpar[c], tok = dead ? 0 : ctok[c];
+        for (int i = lane; i < p.tok_ld; i += 64)
+            p.tokens[(size_t)(base + b) * p.tok_ld + i] = (i == p.write_pos) ? tok : tokbuf[par * p.tok_ld + i];
+        if (p.src) {
+            for (int j = lane; j < p.t; j += 64) p.src[(size_t)(base + b) * p.src_ld + j] = srcbuf[par * p.t + j];
+            if (lane == 0) p.src[(size_t)(base + b) * p.src_ld + p.t] = base + par;
+        }
+        if (lane == 0) {
+            p.vals[base + b] = dead ? -INFINITY : cval[c];
+            p.keys[base + b] = dead ? -INFINITY : q[c];
+            p.ended[base + b] = (uint8_t)dead;
+            p.parent[base + b] = base + par;
+            p.hparent[base + b] = base + par;
+        }
+    }
+    int32_t* pt = p.pool_tokens + (size_t)base * p.tok_ld;
+    for (int o = 0; o < n_off; ++o) {
+        const int c = offer[o], par = cpar[c];
+        const float ok = q[c];
+        const int at = __popcll(__ballot(lane < n_pool && pk >= ok));
+        if (at >= B) continue;                            // (wave-uniform) a full pool whose worst key is >= this one
+        for (int j = min(n_pool, B - 1); j > at; --j)
+            for (int i = lane; i < p.tok_ld; i += 64) pt[(size_t)j * p.tok_ld + i] = pt[(size_t)(j - 1) * p.tok_ld + i];
+        for (int i = lane; i < p.tok_ld; i += 64) pt[(size_t)at * p.tok_ld + i] = (i == p.write_pos) ? p.eos : tokbuf[par * p.tok_ld + i];
+        const float uk = __shfl_up(pk, 1), uv = __shfl_up(pv, 1);
+        const int ul = __shfl_up(pl, 1);
+        if (lane == at) { pk = ok; pv = cval[c]; pl = p.write_pos + 1; }
+        else if (lane > at) { pk = uk; pv = uv; pl = ul; }
+        n_pool = min(n_pool + 1, B);
+    }
+    if (n_off > 0) {
+        if (lane < B) { p.pool_keys[base + lane] = pk; p.pool_vals[base + lane] = pv; p.pool_len[base + lane] = pl; }
+        if (lane == 0) p.pool_n[img] = n_pool;
+    }
+    if (n_pool == B) {                                    // (wave-uniform)
+        const float worst = __shfl(pk, B - 1);
+        const float top = taken > 0 ? q[keep[0]] : -INFINITY;
+        if (lane == 0 && (p.stop_when_full || worst >= top)) { p.done[img] = 1; p.end_step[img] = p.step_index; }
+    }
+}
+
+template <int MB, bool PR = false, bool DT = false, bool LN = false, bool PL = false>
 __device__ __forceinline__ void beam_select_image(const SelectParams& p, const int img, const int lane, const SelLds& L) {
     static_assert(DT || !LN, "the length weights rank the deterministic select only");
+    static_assert(LN || !PL, "the pool ranks by key");
     int32_t* stage = L.stage;
     int* ctok = L.ctok; int* cpar = L.cpar; int* keep = L.keep; float* cval = L.cval; float* q = L.q; uint8_t* cend = L.cend;
 #define s_n (*L.s_n)
@@ -711,6 +825,10 @@ __device__ __forceinline__ void beam_select_image(const SelectParams& p, const i
     }
     wave_lds_sync();
     const int n = s_n;
+    if constexpr (PL) {
+        beam_pool_tail<MB>(p, img, lane, L, n, first, pre);
+        return;
+    }
     if constexpr (DT) {
         if (!first) {
             for (int j = lane; j < B; j += 64) keep[j] = min(j, n - 1);
@@ -1267,6 +1385,127 @@ extern "C" int dh_beam_select_best_norm(const int32_t* pick_idx, const float* pi
     return select_launch<false, true, true>(pick_idx, pick_val, tokens, tok_ld, vals, ended, src, src_ld, parent, hparent, done, end_step,
                                             n_img, beam, first, nullptr, first_sets_ended, write_pos, t, step_index, 1.f, eos_index, nullptr,
                                             0ull, nullptr, 0, stream, keys, len_w, first_col);
+}
+
+// ---- early_stopping: the finished-hypothesis pool of search="beam" -------------------------------------------------------------------
+template <int MB, bool PR>
+__global__ __launch_bounds__(64) void beam_select_pool_kernel(SelectParams p) {
+    extern __shared__ int32_t stage[];
+    __shared__ int ctok[MB * MB], cpar[MB * MB], keep[MB], ord[2 * MB], offer[MB];
+    __shared__ float cval[MB * MB], q[MB * MB];
+    __shared__ uint8_t cend[MB * MB];
+    __shared__ int s_n;
+    __shared__ int32_t pki[MB * MB];
+    __shared__ float pkv[MB * MB];
+    const SelLds L{stage, ctok, cpar, keep, cval, q, cend, &s_n, pki, pkv, ord, offer};
+    beam_select_image<MB, PR, true, true, true>(p, blockIdx.x, threadIdx.x, L);
+}
+
+// dh_beam_select_best_norm with a finished-hypothesis pool (the PL instantiations; beam_pool_tail has the rules): a candidate whose
+// token is <eos> never takes a beam slot -- among the first `beam` ranks it is offered to the image's pool --, the `beam` best others
+// stay as live beams, and a slot nothing is left for is dead (ended = 1, -inf).  `ended` therefore marks dead slots only.  The pool
+// rows have the token table's stride.  stop_when_full: 1 = early_stopping=True, 0 = False.
+extern "C" int dh_beam_select_pool(const int32_t* pick_idx, const float* pick_val, int32_t* tokens, int tok_ld,
+                                   float* vals, float* keys, uint8_t* ended, int32_t* src, int src_ld, int32_t* parent,
+                                   int32_t* hparent, uint8_t* done, int32_t* end_step, int32_t* pool_tokens, float* pool_keys,
+                                   float* pool_vals, int32_t* pool_len, int32_t* pool_n, int n_img, int beam,
+                                   int first, const int32_t* first_pos, int first_col, const float* len_w, int stop_when_full,
+                                   int write_pos, int t, int step_index, int eos_index, void* stream) {
+    DH_REQUIRE(pick_idx && pick_val && tokens && vals && keys && ended && parent && hparent && done && end_step && len_w);
+    DH_REQUIRE(pool_tokens && pool_keys && pool_vals && pool_len && pool_n);
+    DH_REQUIRE(n_img > 0 && beam >= 1 && beam <= DH_BEAM_MAX_BEAMS && tok_ld > 0 && t >= 0 && first_col >= 0 && step_index >= 0);
+    DH_REQUIRE(write_pos >= 0 && write_pos < tok_ld);    // an offered hypothesis holds <eos> at write_pos
+    DH_REQUIRE(stop_when_full == 0 || stop_when_full == 1);
+    DH_REQUIRE(!src || src_ld > t);
+    DhProfScope prof("dh_beam_select_pool", 0.0, 0.0, stream);
+    SelectParams p{pick_idx, pick_val, tokens, tok_ld, vals, ended, src, src_ld, parent, hparent, done, end_step,
+                   beam, first_pos ? 0 : first, 0, write_pos, t, step_index, eos_index, 0, 1.f, nullptr, 0ull, nullptr, first_pos,
+                   keys, len_w, first_col, pool_tokens, pool_keys, pool_vals, pool_len, pool_n, stop_when_full};
+    const size_t lds = (size_t)beam * (tok_ld + (src ? t : 0)) * sizeof(int32_t);
+    DH_REQUIRE(lds <= 56 * 1024);
+    const dim3 grid(n_img), block(64);
+    if (first_pos) {
+        if (beam <= 16) hipLaunchKernelGGL((beam_select_pool_kernel<16, true>), grid, block, lds, (hipStream_t)stream, p);
+        else hipLaunchKernelGGL((beam_select_pool_kernel<DH_BEAM_MAX_BEAMS, true>), grid, block, lds, (hipStream_t)stream, p);
+    } else {
+        if (beam <= 16) hipLaunchKernelGGL((beam_select_pool_kernel<16, false>), grid, block, lds, (hipStream_t)stream, p);
+        else hipLaunchKernelGGL((beam_select_pool_kernel<DH_BEAM_MAX_BEAMS, false>), grid, block, lds, (hipStream_t)stream, p);
+    }
+    DH_LAUNCH_CHECK();
+}
+
+// One wave per image, lane j = pool entry j and live slot j.  The result is the pool with -- for an image that is not done -- its live
+// slots (ended == 0) offered in slot order through the select's insertion rule: that is the stable descending order of "the pool's
+// entries, then the live slots" by key, cut at `beam` (what falls off during the insertions is never among the best `beam`).  So an
+// entry's output slot is a count: the entries with a larger key, plus those with an equal key that stand in front of it.  Fewer than
+// `beam` entries: the slots that were not offered follow in slot order at score -inf.  Nothing is written to the pool or the state.
+__global__ __launch_bounds__(64) void beam_finalize_pool_kernel(
+    const int32_t* __restrict__ tokens, int tok_ld, const float* __restrict__ keys, const uint8_t* __restrict__ ended,
+    const uint8_t* __restrict__ done, const int32_t* __restrict__ pool_tokens, const float* __restrict__ pool_keys,
+    const int32_t* __restrict__ pool_len, const int32_t* __restrict__ pool_n, int32_t* __restrict__ out_tokens, int out_ld,
+    int32_t* __restrict__ out_len, float* __restrict__ out_score, int32_t* __restrict__ out_index, int32_t* __restrict__ out_drawn,
+    int32_t* __restrict__ out_row_len, int beam, int full_len, int pad_index) {
+    __shared__ int s_from[DH_BEAM_MAX_BEAMS], s_len[DH_BEAM_MAX_BEAMS];      // per output slot: source (pool entry j: -1 - j; slot j: j), length
+    const int img = blockIdx.x, lane = threadIdx.x, B = beam, base = img * B;
+    const int cap = min(out_ld, tok_ld);
+    const int n_pool = min(max(pool_n[img], 0), B);
+    const bool in_pool = lane < n_pool;
+    const bool live = lane < B && !done[img] && !ended[base + lane];
+    float pk = in_pool ? pool_keys[base + lane] : -INFINITY;
+    float lk = live ? keys[base + lane] : -INFINITY;
+    if (!(pk == pk)) pk = -INFINITY;                      // (a NaN orders like -inf: the slots stay a permutation)
+    if (!(lk == lk)) lk = -INFINITY;
+    const int plen = in_pool ? min(max(pool_len[base + lane], 0), cap) : 0;
+    const int llen = min(max(full_len, 0), cap);
+    int prank = lane, lrank = 0;                          // the pool is sorted: entry j has j entries in front of it
+    for (int j = 0; j < B; ++j) {
+        const float opk = __shfl(pk, j), olk = __shfl(lk, j);
+        const bool o_pool = j < n_pool, o_live = __shfl((int)live, j) != 0;
+        prank += o_live && olk > pk;
+        lrank += (o_pool && opk >= lk) + (o_live && (olk > lk || (olk == lk && j < lane)));
+    }
+    const int n_live = __popcll(__ballot(live));
+    const int total = n_pool + n_live;
+    // the slots that were not offered, in slot order, behind the entries
+    const unsigned long long idle = __ballot(lane < B && !live);
+    const int frank = total + __popcll(idle & ((1ull << lane) - 1ull));
+    if (lane < B) { s_from[lane] = lane; s_len[lane] = 0; }     // (a pool that is not sorted leaves a slot out: never an index from nowhere)
+    __syncthreads();
+    if (in_pool && prank < B) {
+        s_from[prank] = -1 - lane; s_len[prank] = plen;
+        out_score[base + prank] = pk; out_index[base + prank] = -1; out_len[base + prank] = plen;
+    }
+    if (live && lrank < B) {
+        s_from[lrank] = lane; s_len[lrank] = llen;
+        out_score[base + lrank] = lk; out_index[base + lrank] = lane; out_len[base + lrank] = llen;
+    }
+    if (lane < B && !live && frank < B) {
+        s_from[frank] = lane; s_len[frank] = llen;
+        out_score[base + frank] = -INFINITY; out_index[base + frank] = lane; out_len[base + frank] = llen;
+    }
+    __syncthreads();
+    if (lane == 0) { out_drawn[img] = 0; out_row_len[img] = s_len[0]; }
+    for (int s = 0; s < B; ++s) {
+        const int from = s_from[s], len = s_len[s];
+        const int32_t* __restrict__ row = from < 0 ? pool_tokens + (size_t)(base + (-1 - from)) * tok_ld : tokens + (size_t)(base + from) * tok_ld;
+        int32_t* __restrict__ dst = out_tokens + (size_t)(base + s) * out_ld;
+        for (int i = lane; i < out_ld; i += 64) dst[i] = i < len ? row[i] : pad_index;
+    }
+}
+
+extern "C" int dh_beam_finalize_pool(const int32_t* tokens, int tok_ld, const float* keys, const uint8_t* ended, const uint8_t* done,
+                                     const int32_t* pool_tokens, const float* pool_keys, const int32_t* pool_len, const int32_t* pool_n,
+                                     int32_t* out_tokens, int out_ld, int32_t* out_len, float* out_score, int32_t* out_index,
+                                     int32_t* out_drawn, int32_t* out_row_len, int n_img, int beam, int full_len, int pad_index,
+                                     void* stream) {
+    DH_REQUIRE(tokens && keys && ended && done && pool_tokens && pool_keys && pool_len && pool_n);
+    DH_REQUIRE(out_tokens && out_len && out_score && out_index && out_drawn && out_row_len);
+    DH_REQUIRE(n_img > 0 && tok_ld > 0 && out_ld > 0 && full_len >= 0 && beam >= 1 && beam <= DH_BEAM_MAX_BEAMS);
+    DhProfScope prof("dh_beam_finalize_pool", 0.0, 0.0, stream);
+    hipLaunchKernelGGL(beam_finalize_pool_kernel, dim3(n_img), dim3(64), 0, (hipStream_t)stream, tokens, tok_ld, keys, ended, done,
+                       pool_tokens, pool_keys, pool_len, pool_n, out_tokens, out_ld, out_len, out_score, out_index, out_drawn, out_row_len,
+                       beam, full_len, pad_index);
+    DH_LAUNCH_CHECK();
 }
 
 // ---- the reference's METHOD surface (deephumor/models/beam.py:32-108), one kernel per method ------------------------------------

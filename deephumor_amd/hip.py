@@ -971,6 +971,41 @@ def beam_select_best_norm(pick_idx, pick_val, tokens, vals, keys, ended, src, pa
             int(first), _ptr(first_pos), int(first_col), _ptr(len_w), int(first_sets_ended), write_pos, t, step_index, eos_index, _stream())
 
 
+def beam_select_pool(pick_idx, pick_val, tokens, vals, keys, ended, src, parent, hparent, done, end_step, pool_tokens, pool_keys, pool_vals,
+                     pool_len, pool_n, n_img, beam, first, stop_when_full, write_pos, t, step_index, eos_index, len_w, first_col=0,
+                     first_pos=None):
+    """``dh_beam_select_pool``, ``beam_select_best_norm`` under ``early_stopping``: a candidate whose token is ``<eos>`` never takes a
+    beam slot -- among the first ``beam`` ranks it is offered to the image's finished-hypothesis pool (``pool_tokens`` int32 ``[n_img,
+    beam, max_len]``, ``pool_keys`` / ``pool_vals`` fp32 and ``pool_len`` int32 ``[n_img, beam]``, ``pool_n`` int32 ``[n_img]``) --, the
+    ``beam`` best others stay live and ``ended`` marks dead slots.  ``stop_when_full``: ``early_stopping`` itself, a bool."""
+    _dev(pick_idx, pick_val, tokens, vals, keys, ended, src, parent, hparent, done, end_step, pool_tokens, pool_keys, pool_vals, pool_len,
+         pool_n, len_w, first_pos)
+    assert first_pos is None or (first_pos.dtype == torch.int32 and first_pos.numel() == n_img)
+    assert keys.dtype == torch.float32 and keys.is_contiguous() and keys.numel() >= n_img * beam
+    assert len_w.dtype == torch.float32 and len_w.is_contiguous() and len_w.numel() >= tokens.stride(0) + 1
+    assert pool_tokens.dtype == torch.int32 and pool_tokens.is_contiguous() and pool_tokens.numel() >= n_img * beam * tokens.stride(0)
+    for x, dt, cnt in ((pool_keys, torch.float32, n_img * beam), (pool_vals, torch.float32, n_img * beam), (pool_len, torch.int32, n_img * beam),
+                       (pool_n, torch.int32, n_img)):
+        assert x.dtype == dt and x.is_contiguous() and x.numel() >= cnt
+    _launch("dh_beam_select_pool", _ptr(pick_idx), _ptr(pick_val), _ptr(tokens), tokens.stride(0), _ptr(vals), _ptr(keys), _ptr(ended),
+            _ptr(src), src.stride(0) if src is not None else 0, _ptr(parent), _ptr(hparent), _ptr(done), _ptr(end_step), _ptr(pool_tokens),
+            _ptr(pool_keys), _ptr(pool_vals), _ptr(pool_len), _ptr(pool_n), n_img, beam, int(first), _ptr(first_pos), int(first_col),
+            _ptr(len_w), int(bool(stop_when_full)), write_pos, t, step_index, eos_index, _stream())
+
+
+def beam_finalize_pool(tokens, keys, ended, done, pool_tokens, pool_keys, pool_len, pool_n, out_tokens, out_len, out_score, out_index,
+                       out_drawn, out_row_len, n_img, beam, full_len, pad_index):
+    """``dh_beam_finalize_pool``: the pool's entries and, for an image that is not done, its live slots, the best ``beam`` by key --
+    rows, own lengths, keys, live slot (-1: from the pool); ``out_drawn`` 0, ``out_row_len`` slot 0's length.  ``out_tokens`` int32
+    ``[n_img, beam, T]``."""
+    _dev(tokens, keys, ended, done, pool_tokens, pool_keys, pool_len, pool_n, out_tokens, out_len, out_score, out_index, out_drawn, out_row_len)
+    assert out_tokens.is_contiguous() and out_tokens.shape[:2] == (n_img, beam) and out_tokens.dtype == torch.int32
+    assert pool_tokens.dtype == torch.int32 and pool_tokens.is_contiguous() and pool_tokens.numel() >= n_img * beam * tokens.stride(0)
+    _launch("dh_beam_finalize_pool", _ptr(tokens), tokens.stride(0), _ptr(keys), _ptr(ended), _ptr(done), _ptr(pool_tokens), _ptr(pool_keys),
+            _ptr(pool_len), _ptr(pool_n), _ptr(out_tokens), out_tokens.shape[2], _ptr(out_len), _ptr(out_score), _ptr(out_index),
+            _ptr(out_drawn), _ptr(out_row_len), n_img, beam, int(full_len), int(pad_index), _stream())
+
+
 def beam_history_logits(logits, v, tokens, tok_row_mult, pos, rows, rows_per_img, ngram, penalty, group_max=None, first_pos=None):
     """``dh_beam_history_logits``: the ``no_repeat_ngram_size`` / ``repetition_penalty`` edits of fp32 ``logits [rows, V]`` in place,
     from every row's own history ``tokens[r * tok_row_mult, :pos]`` (int32); with ``group_max`` the 64-column group maxima of every

@@ -171,6 +171,28 @@ def check_length_penalty(length_penalty, max_len=None, search=None):
     return lp
 
 
+def check_early_stopping(early_stopping, search=None, return_attention=False, return_logprobs=False):
+    """``early_stopping`` is ``None`` (off, the call without it), ``True`` or ``False`` -- both keep a finished-hypothesis pool; ``True``
+    stops an image as soon as its pool is full, ``False`` when no live beam can still enter it --: anything else, 0 and 1 included, is a
+    ``TypeError``; checked where ``check_length_penalty`` is, before anything runs.  With ``search``, a non-``None`` value under
+    anything but ``"beam"`` is a ``ValueError``, like ``length_penalty``.  With ``return_attention`` / ``return_logprobs`` on it is a
+    ``NotImplementedError``: both gathers walk tables from a live engine row, and a pooled hypothesis has none.  Returns it."""
+    es = early_stopping
+    if es is not None and not isinstance(es, bool):
+        raise TypeError(f"early_stopping must be None, True or False, not {type(es).__name__} {es!r}")
+    if es is None:
+        return None
+    if search is not None and search != "beam":
+        raise ValueError(f'early_stopping={es} belongs to search="beam" (it pools the hypotheses the deterministic search finishes); '
+                         f'search="{search}" draws its candidates and finishes none -- use early_stopping=None there')
+    for name, on in (("return_attention", return_attention), ("return_logprobs", return_logprobs)):
+        if on:
+            raise NotImplementedError(f"early_stopping={es} with {name}=True: the gather walks its tables from a live engine row, and a "
+                                      f"hypothesis in the pool has none -- the follow-up is a pool that records each entry's row tables; "
+                                      f"use early_stopping=None with {name}")
+    return es
+
+
 _LEN_W_CACHE = {}               # (device, length_penalty, max_len) -> fp32 device table: uploaded once, not once per session
 _LEN_W_CACHE_SIZE = 16          # least recently used out; a table in use is owned by its helper (and by a captured graph's state)
 
@@ -197,11 +219,11 @@ def compile_length_weights(length_penalty, max_len, device="cuda"):
     return w
 
 
-def held_length_weights(length_penalty, device):
+def held_length_weights(length_penalty, device, early_stopping=None):
     """Every cached table of ``length_penalty`` on ``device``, for a captured hipGraph to keep: its ``dh_beam_select_best_norm`` nodes
     hold the raw pointer of the table their session found here, and the cache alone would free it at the next eviction.  ``()`` for
-    0.0."""
-    if float(length_penalty) == 0.0:
+    0.0 -- unless ``early_stopping`` is on: ``dh_beam_select_pool`` nodes point at the table of ones then."""
+    if float(length_penalty) == 0.0 and early_stopping is None:
         return ()
     device = torch.device(device)
     if device.type == "cuda" and device.index is None:
@@ -213,16 +235,19 @@ class _Search(str):
     """``DecodeSettings.search`` of a call with ``length_penalty != 0``: the same string, with the penalty riding on it -- the record's
     field list is fixed, and ``dataclasses.replace`` rebuilds a record from its field values alone.  So ``replace(s, search="beam")``
     (a plain string) is the record WITHOUT the penalty, and the penalty is only ever put here by ``from_kw``, which reads the
-    ``length_penalty`` keyword and takes ``search`` as the plain string it spells.  Copies and pickles like the pair it is."""
+    ``length_penalty`` keyword and takes ``search`` as the plain string it spells.  Copies and pickles like the pair it is.
+    ``early_stopping`` (``None``, ``True`` or ``False``) rides the same way, one more attribute."""
     length_penalty = 0.0
+    early_stopping = None
 
-    def __new__(cls, search, length_penalty=0.0):
+    def __new__(cls, search, length_penalty=0.0, early_stopping=None):
         self = str.__new__(cls, search)
         self.length_penalty = length_penalty
+        self.early_stopping = early_stopping
         return self
 
     def __getnewargs__(self):
-        return (str.__str__(self), self.length_penalty)
+        return (str.__str__(self), self.length_penalty, self.early_stopping)
 
     def __reduce__(self):
         return (_Search, self.__getnewargs__())
@@ -390,7 +415,8 @@ class DecodeSettings:
     (``check_return_logprobs``; the last one, for the same reason -- the constructor's last parameter, kept by ``replace``, in the key;
     an init-only field stored by ``__post_init__``, because ``dataclasses.fields`` is pinned to end at ``search``).
     ``length_penalty`` (``check_length_penalty``; 0.0: off) is a plain attribute, not a field -- the field list above is fixed --: set by
-    ``from_kw``, carried by ``search`` (``_Search``) so that ``replace`` and ``compiled`` keep it, and in the key.  Built by
+    ``from_kw``, carried by ``search`` (``_Search``) so that ``replace`` and ``compiled`` keep it, and in the key; ``early_stopping``
+    (``check_early_stopping``; ``None``: off) travels the same way, in the key in front of ``length_penalty``.  Built by
     ``from_kw`` only.  Immutable; equal and hashed by the settings, the list by its ids whether compiled or not."""
     return_beams: bool = False
     return_attention: bool = False
@@ -406,12 +432,13 @@ class DecodeSettings:
     def __post_init__(self, return_logprobs):
         object.__setattr__(self, "return_logprobs", return_logprobs)
         object.__setattr__(self, "length_penalty", getattr(self.search, "length_penalty", 0.0))
+        object.__setattr__(self, "early_stopping", getattr(self.search, "early_stopping", None))
 
     @classmethod
     def from_kw(cls, kw, max_len, num_tokens=None, model=None):
         """Reads the settings out of the keyword dictionary ``kw`` (which keeps them) and checks them in this order -- ``search``, then
-        ``return_logprobs``, then ``length_penalty`` last --, so a call with two bad values raises for the earlier one; ``model``: see
-        ``check_return_attention`` / ``check_return_logprobs``."""
+        ``return_logprobs``, then ``length_penalty``, then ``early_stopping`` last --, so a call with two bad values raises for the
+        earlier one; ``model``: see ``check_return_attention`` / ``check_return_logprobs``."""
         return_beams = check_return_beams(kw.get("return_beams", False))
         return_attention = check_return_attention(kw.get("return_attention", False), model)
         top_p = check_top_p(kw.get("top_p", 1.0))
@@ -420,14 +447,15 @@ class DecodeSettings:
         search = str(check_search(kw.get("search", "sample"), top_p))      # (the plain string: a penalty comes from its keyword alone)
         return_logprobs = check_return_logprobs(kw.get("return_logprobs", False), model)
         length_penalty = check_length_penalty(kw.get("length_penalty", 0.0), max_len, search)
-        if length_penalty != 0.0:
-            search = _Search(search, length_penalty)
+        early_stopping = check_early_stopping(kw.get("early_stopping"), search, return_attention, return_logprobs)
+        if length_penalty != 0.0 or early_stopping is not None:
+            search = _Search(search, length_penalty, early_stopping)
         return cls(return_beams, return_attention, top_p, ngram, penalty, min_len, bad_words, num_tokens, search, return_logprobs)
 
     def _key(self):
         bw = self.bad_words_ids
         return (self.return_beams, self.return_attention, self.top_p, self.no_repeat_ngram_size, self.repetition_penalty, self.min_len,
-                bw.ids if isinstance(bw, BadWords) else bw, self.length_penalty, self.return_logprobs, self.search)
+                bw.ids if isinstance(bw, BadWords) else bw, self.early_stopping, self.length_penalty, self.return_logprobs, self.search)
 
     def __eq__(self, other):
         return isinstance(other, DecodeSettings) and self._key() == other._key()
@@ -444,7 +472,7 @@ class DecodeSettings:
         """The ``BeamSearchHelper`` of one session with every setting applied; ``engine_args``: the constructor's other arguments."""
         return BeamSearchHelper(top_p=self.top_p, no_repeat_ngram_size=self.no_repeat_ngram_size, repetition_penalty=self.repetition_penalty,
                                 **engine_args).set_constraints(self.min_len, self.bad_words_ids).set_search(self.search).set_logprobs(
-                                    self.return_logprobs).set_length_penalty(self.length_penalty)
+                                    self.return_logprobs).set_length_penalty(self.length_penalty).set_early_stopping(self.early_stopping)
 
 
 class BeamOverflow(RuntimeError):
@@ -637,6 +665,22 @@ class BeamSearchHelper:
     live beam's own columns, times ``w[L]``, is its score bit for bit.  ``0.0``, the default: no table, no ``keys``, today's launches
     and bits.
 
+    ``early_stopping`` (with ``search="beam"`` only; ``helper.set_early_stopping(True | False)`` after construction, the last of the
+    chain): the finished-hypothesis pool of the usual beam search.  Per image ``beam_size`` entries -- ``pool_tokens`` int32 ``[n_img,
+    beam, max_len]``, ``pool_keys`` / ``pool_vals`` fp32 and ``pool_len`` int32 ``[n_img, beam]``, ``pool_n`` int32 ``[n_img]`` --,
+    physically sorted: slot 0 the largest key, equal keys in order of arrival.  The select (``dh_beam_select_pool`` in place of
+    ``dh_beam_select_best`` / ``_norm``; keys as under ``length_penalty``, from a table of ones without one) ranks the candidates as
+    before; down the ranking a candidate whose token is ``<eos>`` never takes a slot -- with rank ``< beam_size`` and key ``> -inf`` it
+    is offered to the pool: the parent's row with ``<eos>`` at ``write_pos``, inserted behind every entry whose key is ``>=`` its own,
+    entry ``beam_size`` falling off --, the ``beam_size`` best others stay as live beams (``ended = 0``) and a slot nothing is left for
+    is dead: ``ended = 1``, ``vals = keys = -inf``.  So the beam keeps its width and a finished caption is never pushed out by a live
+    prefix.  ``done`` is set when the pool is full and the mode is ``True``, or no live beam kept at this step has a key above the
+    pool's worst (``False``).  ``finalize`` makes ONE launch of ``dh_beam_finalize_pool`` -- never the ``beams`` launch --: the pool
+    and, for an image that is not done, its live slots offered the same way; ``lengths`` are each hypothesis' own (``<eos>``
+    included: the ``len_bias_done`` convention, which cuts a finished Transformer image's last ``<eos>``, is not applied),
+    ``scores`` the keys, ``beam_index`` the live slot or -1 for an entry of the pool.  Refused with ``return_attention`` /
+    ``return_logprobs``: both gathers walk tables from a live engine row.  ``None``, the default: no pool, today's launches and bits.
+
     ``return_logprobs`` (not in the reference either; ``helper.set_logprobs(True)`` after construction): the model log-probability of
     every token the search writes, with nothing shuffled per step.  In front of whichever select a step runs, one launch of
     ``dh_beam_pick_logprobs`` sweeps every logits row once more -- behind the history edits and the bans, in front of the samplers' own
@@ -660,6 +704,8 @@ class BeamSearchHelper:
         self.search = "sample"            # "beam": set_search
         self.logprobs, self.pick_lp, self.lp_w, self.par_w = False, None, None, None      # return_logprobs: set_logprobs
         self.length_penalty, self.len_w, self.keys, self.first_col = 0.0, None, None, 0   # length_penalty: set_length_penalty
+        self.early_stopping = None        # True / False: the finished-hypothesis pool (set_early_stopping)
+        self.pool_tokens = self.pool_keys = self.pool_vals = self.pool_len = self.pool_n = None
         self.exact = bool(exact)          # row draws through the general sampler only (see BeamOverflow)
         if beam_size > hip.MAX_BEAMS:     # one wave draws among an image's beams (dh_beam_finalize); the reference has no limit
             raise ValueError(f"beam_size <= {hip.MAX_BEAMS} supported")
@@ -745,6 +791,35 @@ class BeamSearchHelper:
             self.keys = torch.zeros((self.n_img * self.beam_size,), dtype=torch.float32, device=self.device)
         return self
 
+    def set_early_stopping(self, early_stopping=None):
+        """``early_stopping`` of this session (see the class docstring), validated by ``check_early_stopping`` against the helper's
+        ``search`` and ``logprobs`` (so behind ``set_search``, ``set_logprobs`` and ``set_length_penalty``: the last of the chain).
+        ``True`` / ``False``: the per-image pool in ONE zeroed arena -- ``pool_tokens`` int32 ``[n_img, beam, max_len]``, ``pool_keys``
+        (filled with ``-inf``) and ``pool_vals`` fp32 ``[n_img, beam]``, ``pool_len`` int32 ``[n_img, beam]``, ``pool_n`` int32
+        ``[n_img]`` --, and, where ``set_length_penalty`` left none, the per-row ``keys`` and the weight table of ones
+        (``compile_length_weights(0.0, max_len)``: ``x * 1.0f`` is ``x``, so the one kernel serves both; an upload, so not inside a
+        hipGraph capture unless it is cached).  ``None``, the default: nothing is allocated and no launch changes.  Returns the
+        helper."""
+        self.early_stopping = check_early_stopping(early_stopping, self.search, False, self.logprobs)
+        self.pool_tokens = self.pool_keys = self.pool_vals = self.pool_len = self.pool_n = None
+        if self.early_stopping is None:
+            if self.length_penalty == 0.0:
+                self.len_w = self.keys = None
+            return self
+        n, b, m = self.n_img, self.beam_size, self.max_len
+        if self.len_w is None:
+            self.len_w = compile_length_weights(self.length_penalty, m, self.device)
+            self.keys = torch.zeros((n * b,), dtype=torch.float32, device=self.device)
+        arena = torch.zeros((n * b * m + 3 * n * b + n,), dtype=torch.int32, device=self.device)
+        self.pool_tokens = arena[:n * b * m].view(n, b, m)
+        o = n * b * m
+        self.pool_keys = arena[o:o + n * b].view(torch.float32).view(n, b)
+        self.pool_vals = arena[o + n * b:o + 2 * n * b].view(torch.float32).view(n, b)
+        self.pool_len = arena[o + 2 * n * b:o + 3 * n * b].view(n, b)
+        self.pool_n = arena[o + 3 * n * b:]
+        self.pool_keys.fill_(float("-inf"))
+        return self
+
     def set_prefix(self, caption):
         """caption int64 [n_img, p]: teacher-forced beginning, copied to every beam row."""
         p = caption.shape[1]
@@ -824,7 +899,15 @@ class BeamSearchHelper:
             if self.logprobs:             # the bits the row step left in pick_val, zero for the rows that have ended
                 hip.beam_pick_logprobs(None, v, rows, rpi, b, self.temperature, step_index, self._ended, self.pick_idx, self.pick_val,
                                        self.pick_lp, from_vals=True, first_pos=first_pos)
-            if self.length_penalty != 0.0:
+            if self.early_stopping is not None:
+                # the finished-hypothesis pool: the rank on the keys (a table of ones without a penalty), <eos> candidates to the pool
+                if first:
+                    self.first_col = write_pos
+                hip.beam_select_pool(self.pick_idx, self.pick_val, self.tokens, self.vals, self.keys, self._ended, self.src, self.parent,
+                                     self.hparent, self.done, self.end_step, self.pool_tokens, self.pool_keys, self.pool_vals, self.pool_len,
+                                     self.pool_n, self.n_img, b, first, self.early_stopping, write_pos, t, step_index, self.eos_index,
+                                     self.len_w, first_col=self.first_col, first_pos=self.first_pos)
+            elif self.length_penalty != 0.0:
                 # the rank on key = score * len_w[L]; L counts from the image's first generated column: the dense first step's
                 # write_pos, or a prompted session's first_pos (also behind its longest prompt, where the steps are dense again)
                 if first:
@@ -892,7 +975,13 @@ class BeamSearchHelper:
         ``return_logprobs`` (``set_logprobs``): always the ``beams`` launch too, and one launch of ``dh_beam_gather_logprobs`` behind it
         walks every kept beam's back-pointers (``par_w``) once and leaves the log-probabilities of its own columns -- from the image's
         first generated column up to the beam's own length, zero elsewhere -- in the result's ``logprobs``, fp32 ``[n_img, beam,
-        max_len]``; its ``captions`` are those of ``beams=True``."""
+        max_len]``; its ``captions`` are those of ``beams=True``.
+        ``early_stopping`` (``set_early_stopping``): ONE launch of ``dh_beam_finalize_pool`` and never the ``beams`` launch -- the pool's
+        entries and, for an image that is not done, its live slots offered through the select's insertion rule; always a
+        ``BeamCaptions`` inside (the plain pair is ``(tokens[:, 0], lengths[:, 0])``): ``lengths`` each hypothesis' own with its
+        ``<eos>`` included, ``scores`` the keys, ``beam_index`` the live slot or -1 for an entry of the pool, ``drawn`` 0.
+        ``len_bias_done`` is NOT applied there: that convention cuts the last ``<eos>`` of a finished Transformer image, and here every
+        hypothesis knows its own length."""
         best = self.search == "beam"
         if best:
             noise = None
@@ -902,7 +991,24 @@ class BeamSearchHelper:
         else:
             noise = self._noise("final", 0, (self.n_img, self.beam_size))
         logprobs = None
-        if beams or attn_w is not None or best or self.logprobs:
+        if self.early_stopping is not None:
+            # ``early_stopping``: ONE launch of ``dh_beam_finalize_pool``, never the ``beams`` launch -- the pool's entries and, for an
+            # image that is not done, its live slots, the best ``beam_size`` by key.  Every hypothesis knows its own length (``<eos>``
+            # included), so ``len_bias_done`` -- the convention that cuts a finished Transformer image's last ``<eos>`` -- is NOT applied.
+            if attn_w is not None:
+                raise NotImplementedError("early_stopping with return_attention: a hypothesis in the pool has no live engine row to gather from")
+            n, b, dev = self.n_img, self.beam_size, self.device
+            out = torch.empty((n, b, self.max_len), dtype=torch.int32, device=dev)
+            ints = torch.empty((2 * n * b + 2 * n,), dtype=torch.int32, device=dev)
+            o_len, o_idx, o_drawn, o_row = ints[:n * b].view(n, b), ints[n * b:2 * n * b].view(n, b), ints[2 * n * b:2 * n * b + n], ints[2 * n * b + n:]
+            o_score = torch.empty((n, b), dtype=torch.float32, device=dev)
+            hip.beam_finalize_pool(self.tokens, self.keys, self._ended, self.done, self.pool_tokens, self.pool_keys, self.pool_len,
+                                   self.pool_n, out, o_len, o_score, o_idx, o_drawn, o_row, n, b, full_len, pad_index)
+            attention = None
+            captions = BeamCaptions(out.long(), o_len.long(), o_score, o_idx.long(), o_drawn.long(), o_row.long())
+            if not beams:
+                captions = (captions.tokens[:, 0], captions.row_lengths)
+        elif beams or attn_w is not None or best or self.logprobs:
             n, b, dev = self.n_img, self.beam_size, self.device
             out = torch.empty((n, b, self.max_len), dtype=torch.int32, device=dev)
             ints = torch.empty((2 * n * b + 2 * n,), dtype=torch.int32, device=dev)

@@ -78,7 +78,11 @@ class _CaptioningBase(nn.Module):
         contract).  It changes no token; ``pad_index == 1`` raises ``NotImplementedError`` (``beam.check_return_logprobs``).
         ``length_penalty`` (in ``kw``, with ``search="beam"``; default 0.0, the call without it): the search ranks its candidates by the
         length-normalised ``score * L ** -length_penalty`` inside the pruning, ``L`` the generated length; ``BeamCaptions.scores`` are
-        those keys (``LSTMDecoder.generate_batch`` has the full contract)."""
+        those keys (``LSTMDecoder.generate_batch`` has the full contract).
+        ``early_stopping`` (in ``kw``, with ``search="beam"``; ``None``, the default, is the call without it): ``True`` / ``False`` keep a
+        finished-hypothesis pool per image -- an ``<eos>`` candidate goes there and takes no beam slot -- and stop an image when the pool
+        is full (``True``) or when no live beam can still enter it (``False``); the result's slots are the pool's, each with its own
+        length; refused with ``return_attention`` / ``return_logprobs`` (``LSTMDecoder.generate_batch`` has the full contract)."""
         if caption_lengths is not None:
             kw["caption_lengths"] = caption_lengths
         return self.decoder.generate_batch(*encoded, caption=caption, max_len=max_len, temperature=temperature,
@@ -95,6 +99,8 @@ class _CaptioningBase(nn.Module):
             kw.pop("return_logprobs", None)       # (off, it is the call without the keyword)
         if settings.length_penalty == 0.0:
             kw.pop("length_penalty", None)        # (the same)
+        if settings.early_stopping is None:
+            kw.pop("early_stopping", None)        # (the same)
         if caption_lengths is None:
             return None
         if getattr(self.decoder, "pad_index", 0) == 1:
@@ -116,11 +122,12 @@ class _CaptioningBase(nn.Module):
     MAX_GRAPHS = 4      # captured graphs kept per model (one per (input shapes, decode settings))
 
     @staticmethod
-    def _graph_state(graph, static, scap, seed_t, out, sig, plans, slens, length_penalty=0.0, device="cuda"):
+    def _graph_state(graph, static, scap, seed_t, out, sig, plans, slens, length_penalty=0.0, device="cuda", early_stopping=None):
         """What ``generate_batch_graphed`` caches per captured graph: the graph, its static inputs, its outputs, the plan signature and
         everything the captured nodes point at that nothing else owns -- the weight plans and, last, the ``length_penalty`` weight
-        tables the capture's sessions launched with (``beam.held_length_weights``; ``()`` without a penalty)."""
-        return (graph, static, scap, seed_t, out, sig, plans, slens, held_length_weights(length_penalty, device))
+        tables the capture's sessions launched with (``beam.held_length_weights``; ``()`` without a penalty, the tables of ones under
+        ``early_stopping``)."""
+        return (graph, static, scap, seed_t, out, sig, plans, slens, held_length_weights(length_penalty, device, early_stopping))
 
     def generate_batch_graphed(self, *inputs, seed=None, caption=None, caption_lengths=None, **kw):
         """``generate_batch`` replayed from a captured hipGraph (torch.cuda.CUDAGraph on ROCm).
@@ -161,6 +168,13 @@ class _CaptioningBase(nn.Module):
         kw.pop("length_penalty", None)
         if settings.length_penalty != 0.0:
             kw["length_penalty"] = settings.length_penalty
+            compile_length_weights(settings.length_penalty, kw.get("max_len", 25), inputs[0].device)
+        # ``early_stopping`` (dh_beam_select_pool nodes, and dh_beam_finalize_pool at the end): ``None`` is the call without the keyword,
+        # ``True`` / ``False`` are in the key below; the select reads a weight table whatever the penalty is -- of ones at 0.0 --, which
+        # is uploaded here and held by the graph's state like any other
+        kw.pop("early_stopping", None)
+        if settings.early_stopping is not None:
+            kw["early_stopping"] = settings.early_stopping
             compile_length_weights(settings.length_penalty, kw.get("max_len", 25), inputs[0].device)
         # The list is compiled HERE, in front of any capture -- no host-to-device copy happens inside one -- and the ``BadWords``
         # replaces the raw nesting in ``kw``: it is hashable, so it is in the key below, and the captured closure keeps its two
@@ -229,7 +243,8 @@ class _CaptioningBase(nn.Module):
             while len(cache) >= self.MAX_GRAPHS:          # every graph keeps its activations / KV cache allocated: oldest out
                 cache.pop(next(iter(cache)))
             state = cache[key] = self._graph_state(graph, static, scap, seed_t, out, sig, plans, slens,
-                                                   length_penalty=settings.length_penalty, device=inputs[0].device)
+                                                   length_penalty=settings.length_penalty, device=inputs[0].device,
+                                                   early_stopping=settings.early_stopping)
         else:
             cache[key] = cache.pop(key)                   # most recently used last
         graph, static, scap, seed_t, out = state[:5]

@@ -190,7 +190,7 @@ class LSTMDecoder(_Planned, nn.Module):
         hs.mul_(valid[..., None])          # pad_packed_sequence zero rows (mask, not arithmetic on valid rows)
         return hs, bs, steps_out
 
-    @_later_keywords("min_len", "bad_words_ids", "search", "return_logprobs", "length_penalty")
+    @_later_keywords("min_len", "bad_words_ids", "search", "return_logprobs", "length_penalty", "early_stopping")
     def generate_batch(self, image_emb, caption=None, max_len=25, temperature=1.0, beam_size=10, top_k=50,
                        eos_index=3, seed=None, img0=0, noise_source=None, logits_hook=None, streams=1, seed_tensor=None,
                        defer_check=False, early_stop_every=0, exact=False, rng=None, *, caption_lengths=None, return_beams=False, top_p=1.0,
@@ -261,7 +261,20 @@ class LSTMDecoder(_Planned, nn.Module):
         unspecified values, never NaN.  It changes no token; ``False``, the default, is the call without the keyword: same launches,
         same bits.  On: three launches of their own (``dh_beam_pick_logprobs`` in front of and ``dh_beam_record_logprobs`` behind every
         select, ``dh_beam_gather_logprobs`` behind the final draw; ``BeamSearchHelper``).
-        ``min_len``, ``bad_words_ids``, ``search``, ``return_logprobs`` and ``length_penalty`` are not in the parameter list above, which ends at
+        ``early_stopping`` (keyword only, with ``search="beam"``; ``None``, ``True`` or ``False``; ``beam.check_early_stopping``): the
+        finished-hypothesis pool of the usual beam search.  A candidate whose token is ``<eos>`` takes no beam slot any more: among the
+        step's first ``beam_size`` ranks it goes to the image's pool -- sorted by key, ``beam_size`` entries, entered when full only with
+        a key strictly above its worst -- and the ``beam_size`` best other candidates stay as live beams, so the beam keeps its width.
+        ``True``: an image is done as soon as its pool is full; ``False``: when it is full and no live beam kept at this step has a key
+        above the pool's worst (with ``length_penalty <= 0`` keys only fall as a beam grows and this loses nothing; with
+        ``length_penalty > 0`` it is a heuristic).  ``early_stop_every`` then has something to find.  At the end the live beams of an
+        image that is not done are offered to the pool the same way; the result's slots are the pool's: ``lengths`` each hypothesis'
+        own, its ``<eos>`` included -- the convention that cuts a finished Transformer image's last ``<eos>`` column is NOT applied
+        here --, ``scores`` the keys, ``beam_index`` the live slot or ``-1`` for an entry that came from the pool; the plain pair is
+        slot 0.  ``dh_beam_select_pool`` in place of the select and ``dh_beam_finalize_pool`` in place of the final launch; ``None``,
+        the default, is the call without the keyword: same launches, same bits.  With ``search="sample"``: ``ValueError``; with
+        ``return_attention`` / ``return_logprobs``: ``NotImplementedError`` (a pooled hypothesis has no live engine row to gather from).
+        ``min_len``, ``bad_words_ids``, ``search``, ``return_logprobs``, ``length_penalty`` and ``early_stopping`` are not in the parameter list above, which ends at
         ``repetition_penalty`` as it did: they are taken by name (``_later_keywords``) and handed to ``_decode_session``, the
         implementation, which spells every keyword out."""
         return self._generate_batch(image_emb, caption, max_len, temperature, beam_size, top_k, eos_index, seed, img0, noise_source,
@@ -300,11 +313,12 @@ class LSTMDecoder(_Planned, nn.Module):
                         eos_index=3, seed=None, img0=0, noise_source=None, logits_hook=None, streams=1, seed_tensor=None,
                         defer_check=False, early_stop_every=0, exact=False, rng=None, *, caption_lengths=None, return_beams=False, top_p=1.0,
                         no_repeat_ngram_size=0, repetition_penalty=1.0, min_len=0, bad_words_ids=None, search="sample",
-                        return_logprobs=False, length_penalty=0.0):
+                        return_logprobs=False, length_penalty=0.0, early_stopping=None):
         """The implementation of ``generate_batch``, every keyword spelled out."""
         settings = DecodeSettings.from_kw(dict(return_beams=return_beams, top_p=top_p, no_repeat_ngram_size=no_repeat_ngram_size,
                                                repetition_penalty=repetition_penalty, min_len=min_len, bad_words_ids=bad_words_ids,
-                                               search=search, return_logprobs=return_logprobs, length_penalty=length_penalty),
+                                               search=search, return_logprobs=return_logprobs, length_penalty=length_penalty,
+                                               early_stopping=early_stopping),
                                           max_len, self.num_tokens)
         if settings.search == "beam":     # nothing is drawn: no generator is read, no noise source is asked
             rng, noise_source, seed = None, None, 0

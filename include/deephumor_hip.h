@@ -599,6 +599,40 @@ int dh_beam_select_best_norm(const int32_t* pick_idx, const float* pick_val, int
                              int first, const int32_t* first_pos, int first_col, const float* len_w, int first_sets_ended,
                              int write_pos, int t, int step_index, int eos_index, void* stream);
 
+/* dh_beam_select_best_norm with a finished-hypothesis pool (search="beam", early_stopping True / False).  Per image: pool_tokens int32
+ * [beam, tok_ld], pool_keys / pool_vals fp32 [beam], pool_len int32 [beam], pool_n int32 -- physically sorted, slot 0 the largest key,
+ * equal keys in order of arrival; the caller starts it with pool_n = 0 and pool_keys = -inf.  `ended` marks DEAD slots here (vals = keys =
+ * -inf), which bring one candidate: token 0 at their score and key.  The candidates are built and ranked as dh_beam_select_best_norm
+ * does (key = score * len_w[L]; len_w a table of ones without a length penalty; a first step keeps pick order).  Down the ranking: a
+ * candidate whose token is eos_index never takes a slot -- with rank < beam and key > -inf it is offered to the pool: the parent's token
+ * row with eos_index at write_pos, its key, its raw score, length write_pos + 1, inserted behind every entry whose key is >= its own;
+ * entry `beam` falls off, so a full pool is entered only strictly above its worst key --; every other candidate with key > -inf takes
+ * the next live slot until `beam` are taken, written as dh_beam_select_best_norm writes a kept candidate with ended = 0.  Slots left
+ * over are dead: their own row with token 0 at write_pos, vals = keys = -inf, ended = 1, parent = hparent = src[.., t] = themselves
+ * -- at an image's first step the image's base row instead, the only row with decoder state behind it (its token row holds the same
+ * prefix).  The walk looks at the first 2 * beam ranks: a row's picks are distinct tokens, so at most `beam` candidates are eos_index.
+ * done[img] = 1 and end_step[img] = step_index when the pool holds `beam` entries and stop_when_full is 1, or pool_keys[beam - 1] >=
+ * keys of live slot 0 (-inf for a dead one).  Forced and done images: as dh_beam_select_best.  Plain vector stores in a fixed order, no
+ * atomics.  Required: every pointer but src and first_pos, 0 <= write_pos < tok_ld, first_col >= 0, stop_when_full 0 or 1. */
+int dh_beam_select_pool(const int32_t* pick_idx, const float* pick_val, int32_t* tokens, int tok_ld,
+                        float* vals, float* keys, uint8_t* ended, int32_t* src, int src_ld, int32_t* parent,
+                        int32_t* hparent, uint8_t* done, int32_t* end_step, int32_t* pool_tokens, float* pool_keys,
+                        float* pool_vals, int32_t* pool_len, int32_t* pool_n, int n_img, int beam,
+                        int first, const int32_t* first_pos, int first_col, const float* len_w, int stop_when_full,
+                        int write_pos, int t, int step_index, int eos_index, void* stream);
+
+/* The result of a search with a pool, one launch, nothing written to the pool or the state: per image the pool's entries and -- unless
+ * the image is done -- its live slots (ended == 0), offered in slot order through dh_beam_select_pool's insertion rule with the key
+ * they were kept with and length min(full_len, tok_ld); the best `beam` stay.  Fewer than `beam`: the slots that were not offered follow
+ * in slot order at score -inf with that length.  out_tokens [n_img, beam, out_ld]: every entry's row below its own length, pad_index
+ * behind; out_len its length (<eos> included); out_score its key; out_index its live slot, -1 for an entry of the pool; out_drawn 0;
+ * out_row_len = out_len[:, 0]. */
+int dh_beam_finalize_pool(const int32_t* tokens, int tok_ld, const float* keys, const uint8_t* ended, const uint8_t* done,
+                          const int32_t* pool_tokens, const float* pool_keys, const int32_t* pool_len, const int32_t* pool_n,
+                          int32_t* out_tokens, int out_ld, int32_t* out_len, float* out_score, int32_t* out_index,
+                          int32_t* out_drawn, int32_t* out_row_len, int n_img, int beam, int full_len, int pad_index,
+                          void* stream);
+
 /* ---- History-dependent logit edits in front of a row draw: no_repeat_ngram_size and repetition_penalty, IN PLACE on fp32 logits
  * [rows, ldl], one launch.  Logits row r reads its history h[0 .. pos) from tokens[r * tok_row_mult, 0 .. pos) (int32, row stride tok_ld):
  * tok_row_mult = beam for the dense first step (logits [n_img, V], image i's tokens at row i * beam), 1 otherwise.  Ids outside [0, V)
