@@ -135,6 +135,7 @@ SIGNATURES = {
     "dh_beam_select_best_norm": [_P, _P, _P, _I, _P, _P, _P, _P, _I, _P, _P, _P, _P, _I, _I, _I, _P, _I, _P, _I, _I, _I, _I, _I, _P],
     "dh_beam_select_pool": [_P, _P, _P, _I, _P, _P, _P, _P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P, _I, _P, _I, _I, _I, _I,
                             _I, _P],
+    "dh_beam_select_groups": [_P, _P, _P, _I, _P, _P, _P, _P, _I, _P, _P, _P, _P, _I, _I, _I, _P, _I, _P, _I, _I, _I, _I, _I, _I, _F, _P],
     "dh_beam_finalize_pool": [_P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _I, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P],
     "dh_beam_history_logits": [_P, _I, _I, _P, _I, _I, _I, _P, _I, _I, _I, _I, _I, _P, _I, _F, _P],
     "dh_beam_constrain_logits": [_P, _I, _I, _P, _I, _I, _I, _P, _I, _I, _I, _I, _I, _P, _I, _I, _P, _P, _I, _P],

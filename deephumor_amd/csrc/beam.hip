@@ -598,6 +598,8 @@ struct SelectParams {
     float* pool_keys = nullptr; float* pool_vals = nullptr;     //   [n_img, beam] their keys (descending) and raw scores
     int32_t* pool_len = nullptr; int32_t* pool_n = nullptr;     //   [n_img, beam] their lengths (<eos> included), [n_img] entries held
     int stop_when_full = 0;                             //   early_stopping=True: done as soon as the pool is full
+    int n_groups = 1;                                   // dh_beam_select_groups: slots g * (beam / n_groups) .. are group g
+    float diversity = 0.f;                              //   what every earlier group's use of a token at this position costs its key
 };
 
 // LDS scratch of one image's candidate draw, carved by the caller (beam_select_kernel's own arrays)
@@ -606,6 +608,7 @@ struct SelLds {
     int* ctok; int* cpar; int* keep; float* cval; float* q; uint8_t* cend; int* s_n;
     int32_t* pki = nullptr; float* pkv = nullptr;       // optional [beam * beam]: the image's picks, brought in with the first round trip
     int* ord = nullptr; int* offer = nullptr;           // dh_beam_select_pool: [2 * beam] candidates by rank, [beam] the <eos> candidates offered
+    float* pen = nullptr; int* said = nullptr;          // dh_beam_select_groups: [beam * beam] penalised keys, [2 * beam + 1] tokens taken + group starts
 };
 
 // The candidate draw + in-place rewrite of one image's beam state, executed by ONE wave (lane = 0..63); LDS hand-overs are
@@ -727,10 +730,76 @@ __device__ __forceinline__ void beam_pool_tail(const SelectParams& p, const int 
     }
 }
 
-template <int MB, bool PR = false, bool DT = false, bool LN = false, bool PL = false>
+// GR (dh_beam_select_groups, with DT and LN): the rank of an image whose `beam` slots are p.n_groups groups of Bg = beam / n_groups --
+// slots g * Bg .. g * Bg + Bg - 1 are group g from the first step to the last.  n candidates stand in ctok / cval / cpar with their
+// keys in q; the candidates of group g are those whose parent slot lies in it (one contiguous run: the list is in parent order), at a
+// first step -- one source row -- all of them.  The groups are ranked one after the other, g = 0 first:
+//   said   : the tokens the kept candidates of the groups before g took at this position, in slot order (a kept candidate that is an
+//            ended beam's filler, or whose key is not > -inf, adds nothing).
+//   pen    : a candidate of a live row with a finite key gets q - diversity * (times its token stands in `said`) -- the product and the
+//            difference rounded one by one (no FMA) --, every other pen = q; NaN ranks as -inf.
+//   rank   : the Bg largest pen of the group go to slots g * Bg + rank, equal pen to the lower candidate index.  A slot is a rank and
+//            `said` is appended through a ballot in slot order: no atomics.
+// Only `keep` comes out of it: cval and q are not touched, so what the common rewrite stores is not penalised.
+__device__ __forceinline__ void beam_group_tail(const SelectParams& p, const int lane, const SelLds& L, const int n, const int first) {
+    const int B = p.beam, G = p.n_groups, Bg = B / G;
+    const int* ctok = L.ctok; const int* cpar = L.cpar; int* keep = L.keep; const float* q = L.q;
+    float* pen = L.pen; int* said = L.said; int* gstart = L.said + B;
+    // a row that had ended stands in the list with ONE candidate, a live row with `beam` >= 2 of them (n_groups > 1; with one group
+    // nothing is ever penalised or counted): a candidate whose neighbours both have other parents is an ended beam's filler
+    auto filler = [&](int c) { return !first && (c == 0 || cpar[c - 1] != cpar[c]) && (c + 1 == n || cpar[c + 1] != cpar[c]); };
+    if (!first) {
+        for (int c = lane; c < n; c += 64) {
+            const int g = cpar[c] / Bg;
+            if (c == 0 || cpar[c - 1] / Bg != g) gstart[g] = c;
+        }
+        if (lane == 0) gstart[G] = n;
+        wave_lds_sync();
+    }
+    const unsigned long long below = (1ull << lane) - 1ull;
+    int n_said = 0;                                       // (wave-uniform)
+    for (int g = 0; g < G; ++g) {
+        const int lo = first ? 0 : gstart[g], hi = first ? n : gstart[g + 1];
+        for (int c = lo + lane; c < hi; c += 64) {
+            const float k = q[c];
+            float v = k;
+            if (fabsf(k) < INFINITY && !filler(c)) {
+                const int tok = ctok[c];
+                int cnt = 0;
+                for (int s = 0; s < n_said; ++s) cnt += said[s] == tok;
+                v = __fsub_rn(k, __fmul_rn(p.diversity, (float)cnt));
+            }
+            pen[c] = v != v ? -INFINITY : v;
+        }
+        // (every slot valid whatever the keys are, as in the other selects: a group holds at least Bg candidates)
+        for (int r = lane; r < Bg; r += 64) keep[g * Bg + r] = lo + min(r, hi - lo - 1);
+        wave_lds_sync();
+        for (int c = lo + lane; c < hi; c += 64) {
+            const float me = pen[c];
+            int r = 0;
+            for (int j = lo; j < hi; ++j) r += (pen[j] > me) || (pen[j] == me && j < c);
+            if (r < Bg) keep[g * Bg + r] = c;
+        }
+        wave_lds_sync();
+        bool adds = false;
+        int tok = 0;
+        if (lane < Bg) {
+            const int c = keep[g * Bg + lane];
+            tok = ctok[c];
+            adds = q[c] > -INFINITY && !filler(c);
+        }
+        const unsigned long long ab = __ballot(adds);
+        if (adds) said[n_said + __popcll(ab & below)] = tok;      // (at most Bg per group: never more than `beam` entries)
+        n_said += __popcll(ab);
+        wave_lds_sync();
+    }
+}
+
+template <int MB, bool PR = false, bool DT = false, bool LN = false, bool PL = false, bool GR = false>
 __device__ __forceinline__ void beam_select_image(const SelectParams& p, const int img, const int lane, const SelLds& L) {
     static_assert(DT || !LN, "the length weights rank the deterministic select only");
     static_assert(LN || !PL, "the pool ranks by key");
+    static_assert((DT && LN && !PL) || !GR, "the groups rank the keys of the deterministic select, without a pool");
     int32_t* stage = L.stage;
     int* ctok = L.ctok; int* cpar = L.cpar; int* keep = L.keep; float* cval = L.cval; float* q = L.q; uint8_t* cend = L.cend;
 #define s_n (*L.s_n)
@@ -829,7 +898,9 @@ __device__ __forceinline__ void beam_select_image(const SelectParams& p, const i
         beam_pool_tail<MB>(p, img, lane, L, n, first, pre);
         return;
     }
-    if constexpr (DT) {
+    if constexpr (GR) {
+        beam_group_tail(p, lane, L, n, first);
+    } else if constexpr (DT) {
         if (!first) {
             for (int j = lane; j < B; j += 64) keep[j] = min(j, n - 1);
             wave_lds_sync();
@@ -1430,6 +1501,57 @@ extern "C" int dh_beam_select_pool(const int32_t* pick_idx, const float* pick_va
     } else {
         if (beam <= 16) hipLaunchKernelGGL((beam_select_pool_kernel<16, false>), grid, block, lds, (hipStream_t)stream, p);
         else hipLaunchKernelGGL((beam_select_pool_kernel<DH_BEAM_MAX_BEAMS, false>), grid, block, lds, (hipStream_t)stream, p);
+    }
+    DH_LAUNCH_CHECK();
+}
+
+// ---- num_beam_groups: diverse groups of beams under search="beam" ---------------------------------------------------------------------
+template <int MB, bool PR>
+__global__ __launch_bounds__(64) void beam_select_groups_kernel(SelectParams p) {
+    extern __shared__ int32_t stage[];
+    __shared__ int ctok[MB * MB], cpar[MB * MB], keep[MB];
+    __shared__ float cval[MB * MB], q[MB * MB];
+    __shared__ uint8_t cend[MB * MB];
+    __shared__ int s_n;
+    __shared__ int32_t pki[MB * MB];
+    __shared__ float pkv[MB * MB];
+    static_assert(MB * MB >= 2 * MB + 1, "`said` and the group starts fit the pick indices' array");
+    // the picks are consumed when the candidate list stands: their two arrays then hold the penalised keys and the tokens taken
+    const SelLds L{stage, ctok, cpar, keep, cval, q, cend, &s_n, pki, pkv, nullptr, nullptr, pkv, pki};
+    beam_select_image<MB, PR, true, true, false, true>(p, blockIdx.x, threadIdx.x, L);
+}
+
+// dh_beam_select_best_norm over n_groups groups of beam / n_groups slots each (the GR instantiations; beam_group_tail has the rules):
+// group g ranks the candidates of its own slots' rows -- a first step: of the image's one row -- by key - diversity_penalty * (times the
+// token was taken at this position by the groups before it), keeps the best beam / n_groups of them in its slots, and what is stored
+// (vals, keys) is not penalised.  len_w is the table of ones without a length penalty.  Everything else is dh_beam_select_best_norm's.
+extern "C" int dh_beam_select_groups(const int32_t* pick_idx, const float* pick_val, int32_t* tokens, int tok_ld,
+                                     float* vals, float* keys, uint8_t* ended, int32_t* src, int src_ld, int32_t* parent,
+                                     int32_t* hparent, uint8_t* done, int32_t* end_step, int n_img, int beam,
+                                     int first, const int32_t* first_pos, int first_col, const float* len_w, int first_sets_ended,
+                                     int write_pos, int t, int step_index, int eos_index, int n_groups, float diversity_penalty,
+                                     void* stream) {
+    DH_REQUIRE(pick_idx && pick_val && tokens && vals && ended && parent && hparent && done && end_step);
+    DH_REQUIRE(n_img > 0 && beam >= 1 && beam <= DH_BEAM_MAX_BEAMS && tok_ld > 0 && t >= 0);
+    DH_REQUIRE(!src || src_ld > t);
+    DH_REQUIRE(len_w && keys && first_col >= 0);
+    DH_REQUIRE(n_groups >= 1 && beam % n_groups == 0);
+    DH_REQUIRE(diversity_penalty > 0.f && diversity_penalty < INFINITY);
+    DhProfScope prof("dh_beam_select_groups", 0.0, 0.0, stream);
+    SelectParams p{pick_idx, pick_val, tokens, tok_ld, vals, ended, src, src_ld, parent, hparent, done, end_step,
+                   beam, first_pos ? 0 : first, first_sets_ended, write_pos, t, step_index, eos_index, 0, 1.f, nullptr, 0ull, nullptr, first_pos,
+                   keys, len_w, first_col};
+    p.n_groups = n_groups;
+    p.diversity = diversity_penalty;
+    const size_t lds = (size_t)beam * (tok_ld + (src ? t : 0)) * sizeof(int32_t);
+    DH_REQUIRE(lds <= 56 * 1024);
+    const dim3 grid(n_img), block(64);
+    if (first_pos) {
+        if (beam <= 16) hipLaunchKernelGGL((beam_select_groups_kernel<16, true>), grid, block, lds, (hipStream_t)stream, p);
+        else hipLaunchKernelGGL((beam_select_groups_kernel<DH_BEAM_MAX_BEAMS, true>), grid, block, lds, (hipStream_t)stream, p);
+    } else {
+        if (beam <= 16) hipLaunchKernelGGL((beam_select_groups_kernel<16, false>), grid, block, lds, (hipStream_t)stream, p);
+        else hipLaunchKernelGGL((beam_select_groups_kernel<DH_BEAM_MAX_BEAMS, false>), grid, block, lds, (hipStream_t)stream, p);
     }
     DH_LAUNCH_CHECK();
 }

@@ -84,6 +84,31 @@ def beams_to_texts(beams, vocab, delimiter=' '):
             for i in range(toks.shape[0])]
 
 
+def group_best(beams, num_beam_groups):
+    """The best beam of every group of ``generate_batch(..., search="beam", num_beam_groups=G, diversity_penalty=lam,
+    return_beams=True)``'s ``BeamCaptions``: the ``G`` DIFFERENT captions per image that diverse beam search is asked for.  Engine beam
+    ``k`` belongs to group ``k // Bg``, ``Bg = B // G`` (``beams.beam_index``), and the slots are in score order, so a group's best
+    beam is its first slot.  Returns a ``BeamCaptions`` with ``G`` slots per image, slot ``g`` group ``g``'s best -- ``tokens [N, G,
+    T]``, ``lengths`` / ``scores`` / ``beam_index [N, G]``, ``drawn`` the group whose best is the plain call's caption,
+    ``row_lengths`` as they were --, which ``beams_to_texts`` reads like any other (in GROUP order, not score order)."""
+    from ..models.beam import BeamCaptions
+    g = num_beam_groups
+    n, b, t = beams.tokens.shape
+    if isinstance(g, bool) or not isinstance(g, int) or g < 1 or b % g != 0:
+        raise ValueError(f"num_beam_groups must be an int >= 1 that divides the {b} beams, got {g!r}")
+    if bool((beams.beam_index < 0).any()):
+        raise ValueError("group_best: a slot with beam_index -1 comes from an early_stopping pool and belongs to no group")
+    dev = beams.tokens.device
+    group = beams.beam_index // (b // g)                                         # [N, B]
+    slots = torch.arange(b, device=dev)[None, None, :].expand(n, g, b)
+    mine = group[:, None, :] == torch.arange(g, device=dev)[None, :, None]
+    first = torch.where(mine, slots, torch.full((), b, device=dev)).min(-1).values  # [N, G]: every group holds Bg >= 1 beams
+    take = lambda x: torch.gather(x, 1, first)
+    tokens = torch.gather(beams.tokens, 1, first[:, :, None].expand(n, g, t))
+    drawn = group[torch.arange(n, device=dev), beams.drawn]
+    return BeamCaptions(tokens, take(beams.lengths), take(beams.scores), take(beams.beam_index), drawn, beams.row_lengths)
+
+
 def rank_beams(model, inputs, beams, labels=None):
     """Ranks every image's candidates by MODEL probability: ``beams.scores`` cannot do that -- the search re-normalises them over
     the drawn candidates at every step (``log_softmax`` over each row's ``beam_size`` picks, reference beam.py:79), so they are not

@@ -993,6 +993,25 @@ def beam_select_pool(pick_idx, pick_val, tokens, vals, keys, ended, src, parent,
             _ptr(len_w), int(bool(stop_when_full)), write_pos, t, step_index, eos_index, _stream())
 
 
+def beam_select_groups(pick_idx, pick_val, tokens, vals, keys, ended, src, parent, hparent, done, end_step, n_img, beam, first,
+                       first_sets_ended, write_pos, t, step_index, eos_index, len_w, first_col=0, first_pos=None, n_groups=1,
+                       diversity_penalty=1.0):
+    """``dh_beam_select_groups``, ``beam_select_best_norm`` under ``num_beam_groups > 1``: the image's slots are ``n_groups`` groups of
+    ``beam // n_groups``, ranked one after the other -- group ``g`` among the candidates of its own slots' rows (a first step: all of
+    them) by ``key - diversity_penalty * count``, ``count`` the times the candidate's token was kept at this position by the groups before
+    it (two separately rounded fp32 operations); equal values to the lower candidate index.  ``vals`` / ``keys`` receive the kept
+    candidates' raw scores and unpenalised keys; ``len_w`` is the table of ones without a ``length_penalty``."""
+    _dev(pick_idx, pick_val, tokens, vals, keys, ended, src, parent, hparent, done, end_step, len_w, first_pos)
+    assert first_pos is None or (first_pos.dtype == torch.int32 and first_pos.numel() == n_img)
+    assert keys.dtype == torch.float32 and keys.is_contiguous() and keys.numel() >= n_img * beam
+    assert len_w.dtype == torch.float32 and len_w.is_contiguous() and len_w.numel() >= tokens.stride(0) + 1
+    assert int(n_groups) >= 1 and beam % int(n_groups) == 0
+    _launch("dh_beam_select_groups", _ptr(pick_idx), _ptr(pick_val), _ptr(tokens), tokens.stride(0), _ptr(vals), _ptr(keys), _ptr(ended),
+            _ptr(src), src.stride(0) if src is not None else 0, _ptr(parent), _ptr(hparent), _ptr(done), _ptr(end_step), n_img, beam,
+            int(first), _ptr(first_pos), int(first_col), _ptr(len_w), int(first_sets_ended), write_pos, t, step_index, eos_index,
+            int(n_groups), float(diversity_penalty), _stream())
+
+
 def beam_finalize_pool(tokens, keys, ended, done, pool_tokens, pool_keys, pool_len, pool_n, out_tokens, out_len, out_score, out_index,
                        out_drawn, out_row_len, n_img, beam, full_len, pad_index):
     """``dh_beam_finalize_pool``: the pool's entries and, for an image that is not done, its live slots, the best ``beam`` by key --

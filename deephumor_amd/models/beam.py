@@ -193,6 +193,43 @@ def check_early_stopping(early_stopping, search=None, return_attention=False, re
     return es
 
 
+MAX_DIVERSITY_PENALTY = 1e6     # times at most MAX_BEAMS earlier uses of a token: finite in fp32
+
+
+def check_beam_groups(num_beam_groups=1, diversity_penalty=0.0, search=None, beam_size=None, early_stopping=None):
+    """``num_beam_groups`` is an ``int >= 1`` (1: off, the call without it; a ``bool`` or a float is a ``TypeError``) and
+    ``diversity_penalty`` a real number (no ``bool``; 0.0 with one group): checked behind ``check_early_stopping``, before anything
+    runs.  With more than one group the penalty must be finite with ``0 < diversity_penalty <= 1e6`` -- without one every group
+    repeats group 0 for ever, and the cap keeps ``diversity_penalty * beam_size`` finite in fp32 --; with one group a non-zero penalty
+    is a ``ValueError`` (there is no earlier group to differ from).  With ``beam_size``, ``num_beam_groups`` must divide it (so it is
+    ``<= beam_size``); with ``search``, more than one group under anything but ``"beam"`` is a ``ValueError``; with ``early_stopping``
+    not ``None`` it is a ``NotImplementedError``: a pool per group is the follow-up.  Returns ``(int, float)``."""
+    g, lam = num_beam_groups, diversity_penalty
+    if isinstance(g, bool) or not isinstance(g, numbers.Integral):
+        raise TypeError(f"num_beam_groups must be an int >= 1, not {type(g).__name__}")
+    if isinstance(lam, bool) or not isinstance(lam, numbers.Real):
+        raise TypeError(f"diversity_penalty must be a real number, not {type(lam).__name__}")
+    g, lam = int(g), float(lam)
+    if g < 1:
+        raise ValueError(f"num_beam_groups must be >= 1, got {g}")
+    if beam_size is not None and (g > int(beam_size) or int(beam_size) % g != 0):
+        raise ValueError(f"num_beam_groups must divide beam_size: num_beam_groups={g}, beam_size={int(beam_size)}")
+    if g == 1:
+        if lam != 0.0:
+            raise ValueError(f"diversity_penalty={lam} needs num_beam_groups > 1: with one group there is no earlier group to differ from")
+        return 1, 0.0
+    if search is not None and search != "beam":
+        raise ValueError(f'num_beam_groups={g} belongs to search="beam" (it splits the beams the deterministic search keeps into groups); '
+                         f'search="{search}" draws its candidates -- use num_beam_groups=1 there')
+    if not (math.isfinite(lam) and 0.0 < lam <= MAX_DIVERSITY_PENALTY):
+        raise ValueError(f"num_beam_groups={g} needs a finite diversity_penalty with 0 < diversity_penalty <= {MAX_DIVERSITY_PENALTY:g} "
+                         f"(without one every group repeats the first), got {lam}")
+    if early_stopping is not None:
+        raise NotImplementedError(f"num_beam_groups={g} with early_stopping={early_stopping}: the finished-hypothesis pool is one per image, "
+                                  "and groups need one per group -- that is the follow-up; use early_stopping=None with groups")
+    return g, lam
+
+
 _LEN_W_CACHE = {}               # (device, length_penalty, max_len) -> fp32 device table: uploaded once, not once per session
 _LEN_W_CACHE_SIZE = 16          # least recently used out; a table in use is owned by its helper (and by a captured graph's state)
 
@@ -219,11 +256,12 @@ def compile_length_weights(length_penalty, max_len, device="cuda"):
     return w
 
 
-def held_length_weights(length_penalty, device, early_stopping=None):
+def held_length_weights(length_penalty, device, early_stopping=None, num_beam_groups=1):
     """Every cached table of ``length_penalty`` on ``device``, for a captured hipGraph to keep: its ``dh_beam_select_best_norm`` nodes
     hold the raw pointer of the table their session found here, and the cache alone would free it at the next eviction.  ``()`` for
-    0.0 -- unless ``early_stopping`` is on: ``dh_beam_select_pool`` nodes point at the table of ones then."""
-    if float(length_penalty) == 0.0 and early_stopping is None:
+    0.0 -- unless ``early_stopping`` is on or ``num_beam_groups > 1``: ``dh_beam_select_pool`` / ``dh_beam_select_groups`` nodes point
+    at the table of ones then."""
+    if float(length_penalty) == 0.0 and early_stopping is None and int(num_beam_groups) == 1:
         return ()
     device = torch.device(device)
     if device.type == "cuda" and device.index is None:
@@ -236,18 +274,23 @@ class _Search(str):
     field list is fixed, and ``dataclasses.replace`` rebuilds a record from its field values alone.  So ``replace(s, search="beam")``
     (a plain string) is the record WITHOUT the penalty, and the penalty is only ever put here by ``from_kw``, which reads the
     ``length_penalty`` keyword and takes ``search`` as the plain string it spells.  Copies and pickles like the pair it is.
-    ``early_stopping`` (``None``, ``True`` or ``False``) rides the same way, one more attribute."""
+    ``early_stopping`` (``None``, ``True`` or ``False``) rides the same way, one more attribute; so do ``num_beam_groups`` and
+    ``diversity_penalty`` (``check_beam_groups``; 1 and 0.0: off)."""
     length_penalty = 0.0
     early_stopping = None
+    num_beam_groups = 1
+    diversity_penalty = 0.0
 
-    def __new__(cls, search, length_penalty=0.0, early_stopping=None):
+    def __new__(cls, search, length_penalty=0.0, early_stopping=None, num_beam_groups=1, diversity_penalty=0.0):
         self = str.__new__(cls, search)
         self.length_penalty = length_penalty
         self.early_stopping = early_stopping
+        self.num_beam_groups = num_beam_groups
+        self.diversity_penalty = diversity_penalty
         return self
 
     def __getnewargs__(self):
-        return (str.__str__(self), self.length_penalty, self.early_stopping)
+        return (str.__str__(self), self.length_penalty, self.early_stopping, self.num_beam_groups, self.diversity_penalty)
 
     def __reduce__(self):
         return (_Search, self.__getnewargs__())
@@ -416,7 +459,9 @@ class DecodeSettings:
     an init-only field stored by ``__post_init__``, because ``dataclasses.fields`` is pinned to end at ``search``).
     ``length_penalty`` (``check_length_penalty``; 0.0: off) is a plain attribute, not a field -- the field list above is fixed --: set by
     ``from_kw``, carried by ``search`` (``_Search``) so that ``replace`` and ``compiled`` keep it, and in the key; ``early_stopping``
-    (``check_early_stopping``; ``None``: off) travels the same way, in the key in front of ``length_penalty``.  Built by
+    (``check_early_stopping``; ``None``: off) travels the same way, in the key in front of ``length_penalty``; ``num_beam_groups`` /
+    ``diversity_penalty`` (``check_beam_groups``; 1 / 0.0: off) too -- their pair is ONE more key element, in front of all the others
+    and only with more than one group, so the key of a record without groups is what it was.  Built by
     ``from_kw`` only.  Immutable; equal and hashed by the settings, the list by its ids whether compiled or not."""
     return_beams: bool = False
     return_attention: bool = False
@@ -433,12 +478,14 @@ class DecodeSettings:
         object.__setattr__(self, "return_logprobs", return_logprobs)
         object.__setattr__(self, "length_penalty", getattr(self.search, "length_penalty", 0.0))
         object.__setattr__(self, "early_stopping", getattr(self.search, "early_stopping", None))
+        object.__setattr__(self, "num_beam_groups", getattr(self.search, "num_beam_groups", 1))
+        object.__setattr__(self, "diversity_penalty", getattr(self.search, "diversity_penalty", 0.0))
 
     @classmethod
     def from_kw(cls, kw, max_len, num_tokens=None, model=None):
         """Reads the settings out of the keyword dictionary ``kw`` (which keeps them) and checks them in this order -- ``search``, then
         ``return_logprobs``, then ``length_penalty``, then ``early_stopping`` last --, so a call with two bad values raises for the
-        earlier one; ``model``: see ``check_return_attention`` / ``check_return_logprobs``."""
+        earlier one; ``num_beam_groups`` / ``diversity_penalty`` (``check_beam_groups``) behind them all; ``model``: see ``check_return_attention`` / ``check_return_logprobs``."""
         return_beams = check_return_beams(kw.get("return_beams", False))
         return_attention = check_return_attention(kw.get("return_attention", False), model)
         top_p = check_top_p(kw.get("top_p", 1.0))
@@ -448,13 +495,16 @@ class DecodeSettings:
         return_logprobs = check_return_logprobs(kw.get("return_logprobs", False), model)
         length_penalty = check_length_penalty(kw.get("length_penalty", 0.0), max_len, search)
         early_stopping = check_early_stopping(kw.get("early_stopping"), search, return_attention, return_logprobs)
-        if length_penalty != 0.0 or early_stopping is not None:
-            search = _Search(search, length_penalty, early_stopping)
+        groups, diversity = check_beam_groups(kw.get("num_beam_groups", 1), kw.get("diversity_penalty", 0.0), search, kw.get("beam_size"),
+                                              early_stopping)
+        if length_penalty != 0.0 or early_stopping is not None or groups > 1:
+            search = _Search(search, length_penalty, early_stopping, groups, diversity)
         return cls(return_beams, return_attention, top_p, ngram, penalty, min_len, bad_words, num_tokens, search, return_logprobs)
 
     def _key(self):
         bw = self.bad_words_ids
-        return (self.return_beams, self.return_attention, self.top_p, self.no_repeat_ngram_size, self.repetition_penalty, self.min_len,
+        groups = ((self.num_beam_groups, self.diversity_penalty),) if self.num_beam_groups > 1 else ()
+        return groups + (self.return_beams, self.return_attention, self.top_p, self.no_repeat_ngram_size, self.repetition_penalty, self.min_len,
                 bw.ids if isinstance(bw, BadWords) else bw, self.early_stopping, self.length_penalty, self.return_logprobs, self.search)
 
     def __eq__(self, other):
@@ -472,7 +522,8 @@ class DecodeSettings:
         """The ``BeamSearchHelper`` of one session with every setting applied; ``engine_args``: the constructor's other arguments."""
         return BeamSearchHelper(top_p=self.top_p, no_repeat_ngram_size=self.no_repeat_ngram_size, repetition_penalty=self.repetition_penalty,
                                 **engine_args).set_constraints(self.min_len, self.bad_words_ids).set_search(self.search).set_logprobs(
-                                    self.return_logprobs).set_length_penalty(self.length_penalty).set_early_stopping(self.early_stopping)
+                                    self.return_logprobs).set_length_penalty(self.length_penalty).set_early_stopping(self.early_stopping).set_beam_groups(
+                                        self.num_beam_groups, self.diversity_penalty)
 
 
 class BeamOverflow(RuntimeError):
@@ -681,6 +732,18 @@ class BeamSearchHelper:
     ``scores`` the keys, ``beam_index`` the live slot or -1 for an entry of the pool.  Refused with ``return_attention`` /
     ``return_logprobs``: both gathers walk tables from a live engine row.  ``None``, the default: no pool, today's launches and bits.
 
+    ``num_beam_groups`` / ``diversity_penalty`` (with ``search="beam"`` only; ``helper.set_beam_groups(G, lam)`` after construction,
+    behind ``set_early_stopping``): diverse beam search (Vijayakumar et al. 2016).  Engine slots ``g * Bg .. g * Bg + Bg - 1``, ``Bg =
+    beam_size // G``, are group ``g`` from the first step to the last; a beam never changes group.  The select
+    (``dh_beam_select_groups`` in place of ``dh_beam_select_best`` / ``_norm``; candidates and keys as under ``length_penalty``, from a
+    table of ones without one) ranks the groups one after the other: group ``g`` among the candidates of its own rows (an image's
+    first step, with one row: all ``beam_size`` picks) by ``fp32(key - fp32(lam * count))``, ``count`` the times the candidate's token
+    was kept at this position by groups ``0 .. g - 1``; an ended beam's candidate and one at ``-inf`` are neither penalised nor
+    counted; equal values to the lower candidate index.  The penalty shapes each step's choice and is never stored: ``vals`` and
+    ``keys`` hold what they hold without groups, ``BeamCaptions.scores`` stay model log-probabilities (times ``w[L]`` under a
+    ``length_penalty``), and ``finalize`` is unchanged -- all beams in score order, ``beam_index // Bg`` a beam's group.  Refused with
+    ``early_stopping``.  ``1``, the default: today's launches and bits.
+
     ``return_logprobs`` (not in the reference either; ``helper.set_logprobs(True)`` after construction): the model log-probability of
     every token the search writes, with nothing shuffled per step.  In front of whichever select a step runs, one launch of
     ``dh_beam_pick_logprobs`` sweeps every logits row once more -- behind the history edits and the bans, in front of the samplers' own
@@ -706,6 +769,7 @@ class BeamSearchHelper:
         self.length_penalty, self.len_w, self.keys, self.first_col = 0.0, None, None, 0   # length_penalty: set_length_penalty
         self.early_stopping = None        # True / False: the finished-hypothesis pool (set_early_stopping)
         self.pool_tokens = self.pool_keys = self.pool_vals = self.pool_len = self.pool_n = None
+        self.num_beam_groups, self.diversity_penalty = 1, 0.0      # diverse groups of beams: set_beam_groups
         self.exact = bool(exact)          # row draws through the general sampler only (see BeamOverflow)
         if beam_size > hip.MAX_BEAMS:     # one wave draws among an image's beams (dh_beam_finalize); the reference has no limit
             raise ValueError(f"beam_size <= {hip.MAX_BEAMS} supported")
@@ -820,6 +884,24 @@ class BeamSearchHelper:
         self.pool_keys.fill_(float("-inf"))
         return self
 
+    def set_beam_groups(self, num_beam_groups=1, diversity_penalty=0.0):
+        """``num_beam_groups`` / ``diversity_penalty`` of this session (see the class docstring), validated by ``check_beam_groups``
+        against the helper's ``search``, ``beam_size`` and ``early_stopping`` (so the last of the chain, behind
+        ``set_early_stopping``).  More than one group: where ``set_length_penalty`` left none, the per-row ``keys`` and the weight
+        table of ones (``compile_length_weights(0.0, max_len)``, as ``set_early_stopping`` takes it: an upload, so not inside a
+        hipGraph capture unless it is cached).  One group, the default: nothing is allocated and no launch changes.  Returns the
+        helper."""
+        had = self.num_beam_groups > 1
+        self.num_beam_groups, self.diversity_penalty = check_beam_groups(num_beam_groups, diversity_penalty, self.search, self.beam_size,
+                                                                         self.early_stopping)
+        if self.num_beam_groups > 1:
+            if self.len_w is None:
+                self.len_w = compile_length_weights(self.length_penalty, self.max_len, self.device)
+                self.keys = torch.zeros((self.n_img * self.beam_size,), dtype=torch.float32, device=self.device)
+        elif had and self.length_penalty == 0.0 and self.early_stopping is None:
+            self.len_w = self.keys = None
+        return self
+
     def set_prefix(self, caption):
         """caption int64 [n_img, p]: teacher-forced beginning, copied to every beam row."""
         p = caption.shape[1]
@@ -907,6 +989,15 @@ class BeamSearchHelper:
                                      self.hparent, self.done, self.end_step, self.pool_tokens, self.pool_keys, self.pool_vals, self.pool_len,
                                      self.pool_n, self.n_img, b, first, self.early_stopping, write_pos, t, step_index, self.eos_index,
                                      self.len_w, first_col=self.first_col, first_pos=self.first_pos)
+            elif self.num_beam_groups > 1:
+                # diverse groups: the rank of every group on its own rows' keys less what the groups before it took at this position
+                # (the keys as below; a table of ones without a length penalty)
+                if first:
+                    self.first_col = write_pos
+                hip.beam_select_groups(self.pick_idx, self.pick_val, self.tokens, self.vals, self.keys, self._ended, self.src,
+                                       self.parent, self.hparent, self.done, self.end_step, self.n_img, b, first, True, write_pos, t,
+                                       step_index, self.eos_index, self.len_w, first_col=self.first_col, first_pos=self.first_pos,
+                                       n_groups=self.num_beam_groups, diversity_penalty=self.diversity_penalty)
             elif self.length_penalty != 0.0:
                 # the rank on key = score * len_w[L]; L counts from the image's first generated column: the dense first step's
                 # write_pos, or a prompted session's first_pos (also behind its longest prompt, where the steps are dense again)

@@ -82,7 +82,12 @@ class _CaptioningBase(nn.Module):
         ``early_stopping`` (in ``kw``, with ``search="beam"``; ``None``, the default, is the call without it): ``True`` / ``False`` keep a
         finished-hypothesis pool per image -- an ``<eos>`` candidate goes there and takes no beam slot -- and stop an image when the pool
         is full (``True``) or when no live beam can still enter it (``False``); the result's slots are the pool's, each with its own
-        length; refused with ``return_attention`` / ``return_logprobs`` (``LSTMDecoder.generate_batch`` has the full contract)."""
+        length; refused with ``return_attention`` / ``return_logprobs`` (``LSTMDecoder.generate_batch`` has the full contract).
+        ``num_beam_groups`` / ``diversity_penalty`` (in ``kw``, with ``search="beam"``; 1 / 0.0, the defaults, are the call without them):
+        diverse beam search -- the beams are ``num_beam_groups`` groups that choose one after the other at every position, a group's
+        candidates losing ``diversity_penalty`` for every earlier group that took the same token there; scores stay model
+        log-probabilities, ``beam_index // (beam_size // num_beam_groups)`` is a beam's group and ``experiments.group_best`` returns
+        each group's best beam; refused with ``early_stopping`` (``LSTMDecoder.generate_batch`` has the full contract)."""
         if caption_lengths is not None:
             kw["caption_lengths"] = caption_lengths
         return self.decoder.generate_batch(*encoded, caption=caption, max_len=max_len, temperature=temperature,
@@ -93,6 +98,9 @@ class _CaptioningBase(nn.Module):
         the options it cannot be combined with); ``defer_check`` callers (graph capture, the pipeline) with device-resident lengths
         have done so themselves.  So are the decode settings in ``kw`` (``beam.DecodeSettings``), for every batch."""
         settings = DecodeSettings.from_kw(kw, max_len, self._hp["num_tokens"], self)
+        if settings.num_beam_groups == 1:         # (off, it is the call without the keywords)
+            kw.pop("num_beam_groups", None)
+            kw.pop("diversity_penalty", None)
         if not settings.return_attention and not getattr(self.decoder, "_cross", False):
             kw.pop("return_attention", None)      # (off, it is the call without the keyword -- also for the kinds whose decoders do not know it)
         if not settings.return_logprobs:
@@ -122,12 +130,14 @@ class _CaptioningBase(nn.Module):
     MAX_GRAPHS = 4      # captured graphs kept per model (one per (input shapes, decode settings))
 
     @staticmethod
-    def _graph_state(graph, static, scap, seed_t, out, sig, plans, slens, length_penalty=0.0, device="cuda", early_stopping=None):
+    def _graph_state(graph, static, scap, seed_t, out, sig, plans, slens, length_penalty=0.0, device="cuda", early_stopping=None,
+                     num_beam_groups=1):
         """What ``generate_batch_graphed`` caches per captured graph: the graph, its static inputs, its outputs, the plan signature and
         everything the captured nodes point at that nothing else owns -- the weight plans and, last, the ``length_penalty`` weight
         tables the capture's sessions launched with (``beam.held_length_weights``; ``()`` without a penalty, the tables of ones under
-        ``early_stopping``)."""
-        return (graph, static, scap, seed_t, out, sig, plans, slens, held_length_weights(length_penalty, device, early_stopping))
+        ``early_stopping`` or ``num_beam_groups > 1``)."""
+        return (graph, static, scap, seed_t, out, sig, plans, slens,
+                held_length_weights(length_penalty, device, early_stopping, num_beam_groups))
 
     def generate_batch_graphed(self, *inputs, seed=None, caption=None, caption_lengths=None, **kw):
         """``generate_batch`` replayed from a captured hipGraph (torch.cuda.CUDAGraph on ROCm).
@@ -175,6 +185,14 @@ class _CaptioningBase(nn.Module):
         kw.pop("early_stopping", None)
         if settings.early_stopping is not None:
             kw["early_stopping"] = settings.early_stopping
+            compile_length_weights(settings.length_penalty, kw.get("max_len", 25), inputs[0].device)
+        # ``num_beam_groups`` / ``diversity_penalty`` (dh_beam_select_groups nodes): 1 is the call without the keywords; more groups --
+        # as the values the check returns -- are in the key below, so two group counts never share a graph; the select reads a weight
+        # table here too (of ones at 0.0), uploaded in front of the capture and held by the graph's state
+        kw.pop("num_beam_groups", None)
+        kw.pop("diversity_penalty", None)
+        if settings.num_beam_groups > 1:
+            kw["num_beam_groups"], kw["diversity_penalty"] = settings.num_beam_groups, settings.diversity_penalty
             compile_length_weights(settings.length_penalty, kw.get("max_len", 25), inputs[0].device)
         # The list is compiled HERE, in front of any capture -- no host-to-device copy happens inside one -- and the ``BadWords``
         # replaces the raw nesting in ``kw``: it is hashable, so it is in the key below, and the captured closure keeps its two
@@ -244,7 +262,7 @@ class _CaptioningBase(nn.Module):
                 cache.pop(next(iter(cache)))
             state = cache[key] = self._graph_state(graph, static, scap, seed_t, out, sig, plans, slens,
                                                    length_penalty=settings.length_penalty, device=inputs[0].device,
-                                                   early_stopping=settings.early_stopping)
+                                                   early_stopping=settings.early_stopping, num_beam_groups=settings.num_beam_groups)
         else:
             cache[key] = cache.pop(key)                   # most recently used last
         graph, static, scap, seed_t, out = state[:5]

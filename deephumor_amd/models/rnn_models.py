@@ -190,7 +190,8 @@ class LSTMDecoder(_Planned, nn.Module):
         hs.mul_(valid[..., None])          # pad_packed_sequence zero rows (mask, not arithmetic on valid rows)
         return hs, bs, steps_out
 
-    @_later_keywords("min_len", "bad_words_ids", "search", "return_logprobs", "length_penalty", "early_stopping")
+    @_later_keywords("min_len", "bad_words_ids", "search", "return_logprobs", "num_beam_groups", "diversity_penalty", "length_penalty",
+                     "early_stopping")
     def generate_batch(self, image_emb, caption=None, max_len=25, temperature=1.0, beam_size=10, top_k=50,
                        eos_index=3, seed=None, img0=0, noise_source=None, logits_hook=None, streams=1, seed_tensor=None,
                        defer_check=False, early_stop_every=0, exact=False, rng=None, *, caption_lengths=None, return_beams=False, top_p=1.0,
@@ -274,7 +275,18 @@ class LSTMDecoder(_Planned, nn.Module):
         slot 0.  ``dh_beam_select_pool`` in place of the select and ``dh_beam_finalize_pool`` in place of the final launch; ``None``,
         the default, is the call without the keyword: same launches, same bits.  With ``search="sample"``: ``ValueError``; with
         ``return_attention`` / ``return_logprobs``: ``NotImplementedError`` (a pooled hypothesis has no live engine row to gather from).
-        ``min_len``, ``bad_words_ids``, ``search``, ``return_logprobs``, ``length_penalty`` and ``early_stopping`` are not in the parameter list above, which ends at
+        ``num_beam_groups`` / ``diversity_penalty`` (keyword only, with ``search="beam"``; an int ``G >= 1`` that divides ``beam_size``
+        and a number ``0 < lam <= 1e6``; ``beam.check_beam_groups``): diverse beam search.  The ``beam_size`` beams are ``G`` groups of
+        ``Bg = beam_size // G`` -- engine beams ``g * Bg .. g * Bg + Bg - 1`` are group ``g`` for the whole search -- and at every
+        position the groups choose one after the other: group ``g`` ranks the candidates of its own beams by ``key - lam * count``,
+        ``count`` the times the candidate's token was taken at this position by the groups before it (an ended beam is neither
+        penalised nor counted).  The penalty shapes the choice and is never stored: ``BeamCaptions.scores`` stay model
+        log-probabilities (length-normalised under ``length_penalty``), all ``beam_size`` beams come back in score order,
+        ``beam_index // Bg`` is a beam's group (``experiments.group_best`` picks each group's best) and the plain pair is slot 0.
+        ``dh_beam_select_groups`` in place of the select, one launch per position for all groups; ``1`` / ``0.0``, the defaults, are
+        the call without the keywords: same launches, same bits.  ``G > 1`` with ``search="sample"`` or without a penalty:
+        ``ValueError``; with ``early_stopping``: ``NotImplementedError`` (a pool per group is the follow-up).
+        ``min_len``, ``bad_words_ids``, ``search``, ``return_logprobs``, ``num_beam_groups``, ``diversity_penalty``, ``length_penalty`` and ``early_stopping`` are not in the parameter list above, which ends at
         ``repetition_penalty`` as it did: they are taken by name (``_later_keywords``) and handed to ``_decode_session``, the
         implementation, which spells every keyword out."""
         return self._generate_batch(image_emb, caption, max_len, temperature, beam_size, top_k, eos_index, seed, img0, noise_source,
@@ -313,12 +325,13 @@ class LSTMDecoder(_Planned, nn.Module):
                         eos_index=3, seed=None, img0=0, noise_source=None, logits_hook=None, streams=1, seed_tensor=None,
                         defer_check=False, early_stop_every=0, exact=False, rng=None, *, caption_lengths=None, return_beams=False, top_p=1.0,
                         no_repeat_ngram_size=0, repetition_penalty=1.0, min_len=0, bad_words_ids=None, search="sample",
-                        return_logprobs=False, length_penalty=0.0, early_stopping=None):
+                        return_logprobs=False, num_beam_groups=1, diversity_penalty=0.0, length_penalty=0.0, early_stopping=None):
         """The implementation of ``generate_batch``, every keyword spelled out."""
         settings = DecodeSettings.from_kw(dict(return_beams=return_beams, top_p=top_p, no_repeat_ngram_size=no_repeat_ngram_size,
                                                repetition_penalty=repetition_penalty, min_len=min_len, bad_words_ids=bad_words_ids,
                                                search=search, return_logprobs=return_logprobs, length_penalty=length_penalty,
-                                               early_stopping=early_stopping),
+                                               early_stopping=early_stopping, num_beam_groups=num_beam_groups,
+                                               diversity_penalty=diversity_penalty, beam_size=beam_size),
                                           max_len, self.num_tokens)
         if settings.search == "beam":     # nothing is drawn: no generator is read, no noise source is asked
             rng, noise_source, seed = None, None, 0

@@ -41,7 +41,8 @@ class CaptionPipeline:
         """``return_beams=True`` (one of ``gen_kw``): every batch comes out as a ``beam.BeamCaptions`` instead of the pair.
         ``search="beam"`` (one of ``gen_kw``): every batch is decoded by the deterministic search (``LSTMDecoder.generate_batch``);
         ``length_penalty`` (beside it): its candidates are ranked by length-normalised score (see there); ``early_stopping`` (beside
-        it, ``True`` / ``False``): finished hypotheses go to a pool and an image stops when it is full (see there).
+        it, ``True`` / ``False``): finished hypotheses go to a pool and an image stops when it is full (see there);
+        ``num_beam_groups`` / ``diversity_penalty`` (beside it): the beams are diverse groups (see there).
         ``preprocess``: optional callable mapping the staged device tensors of a batch to ``model.encode``'s inputs
         (e.g. ``u8_preprocess(model)``); it runs on the encode stream in front of the encoder.  ``gen_kw`` goes to every batch's
         ``model.decode`` unchanged: ``caption`` -- and with it ``caption_lengths``, one prompt length per image -- is per pipeline,

@@ -621,6 +621,25 @@ int dh_beam_select_pool(const int32_t* pick_idx, const float* pick_val, int32_t*
                         int first, const int32_t* first_pos, int first_col, const float* len_w, int stop_when_full,
                         int write_pos, int t, int step_index, int eos_index, void* stream);
 
+/* dh_beam_select_best_norm over diverse groups of beams (search="beam", num_beam_groups > 1; Vijayakumar et al. 2016).  The `beam` slots
+ * of an image are n_groups groups of Bg = beam / n_groups: slots g * Bg .. g * Bg + Bg - 1 are group g at every step.  The candidate list
+ * and the keys q = score * len_w[L] are dh_beam_select_best_norm's (len_w a table of ones without a length penalty); candidate c belongs to
+ * group (its parent slot) / Bg, at an image's first step -- one source row -- to every group.  For g = 0 .. n_groups - 1 in order: `said`
+ * holds the tokens the kept candidates of the groups before g took at this position; a candidate of a live row with a finite key gets
+ * pen = fp32(q - fp32(diversity_penalty * fp32(times its token stands in said))) -- two separately rounded operations, no FMA --, an ended
+ * beam's single candidate and a -inf candidate keep pen = q; the group's Bg candidates with the largest pen go to slots g * Bg + rank,
+ * equal pen to the lower candidate index, -inf (and NaN) last; their tokens are appended to said (an ended beam's candidate and a
+ * candidate at -inf add nothing).  What is stored is NOT penalised: vals gets the raw cumulative score, keys gets q.  ended, done,
+ * end_step, parent, hparent, src, the token rows, forced and done images are dh_beam_select_best_norm's.  One wave per image does all its
+ * groups; no atomics.  Required: what dh_beam_select_best_norm requires, n_groups >= 1 with beam % n_groups == 0, and a finite
+ * diversity_penalty > 0. */
+int dh_beam_select_groups(const int32_t* pick_idx, const float* pick_val, int32_t* tokens, int tok_ld,
+                          float* vals, float* keys, uint8_t* ended, int32_t* src, int src_ld, int32_t* parent,
+                          int32_t* hparent, uint8_t* done, int32_t* end_step, int n_img, int beam,
+                          int first, const int32_t* first_pos, int first_col, const float* len_w, int first_sets_ended,
+                          int write_pos, int t, int step_index, int eos_index, int n_groups, float diversity_penalty,
+                          void* stream);
+
 /* The result of a search with a pool, one launch, nothing written to the pool or the state: per image the pool's entries and -- unless
  * the image is done -- its live slots (ended == 0), offered in slot order through dh_beam_select_pool's insertion rule with the key
  * they were kept with and length min(full_len, tok_ld); the best `beam` stay.  Fewer than `beam`: the slots that were not offered follow
