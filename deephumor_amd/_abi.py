@@ -139,6 +139,7 @@ SIGNATURES = {
     "dh_beam_finalize_pool": [_P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _I, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P],
     "dh_beam_history_logits": [_P, _I, _I, _P, _I, _I, _I, _P, _I, _I, _I, _I, _I, _P, _I, _F, _P],
     "dh_beam_constrain_logits": [_P, _I, _I, _P, _I, _I, _I, _P, _I, _I, _I, _I, _I, _P, _I, _I, _P, _P, _I, _P],
+    "dh_beam_bias_logits": [_P, _I, _I, _P, _I, _I, _I, _P, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _I, _I, _P],
     "dh_transformer_decode_position": [_c.POINTER(TrModel), _c.POINTER(TrScratch), _P, _P, _I, _P, _I, _I, _I, _I, _I, _I,
                                        _P, _P, _I, _P, _I, _P],
     "dh_transformer_decode_position_attn": [_c.POINTER(TrModel), _c.POINTER(TrScratch), _P, _P, _I, _P, _I, _I, _I, _I, _I, _I,

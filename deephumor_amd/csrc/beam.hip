@@ -1363,6 +1363,107 @@ extern "C" int dh_beam_constrain_logits(float* logits, int ldl, int V, float* gr
     DH_LAUNCH_CHECK();
 }
 
+// ---- history-dependent biases (sequence_bias) in front of the row draw ----------------------------------------------------------
+// One workgroup per logits row, on the row geometry of beam_constrain_logits_kernel (history h[0 .. pos) = columns < pos of token row
+// r * tok_row_mult; forced / idle rows of a prompted launch leave before the first barrier).  The phrases are one list for the whole
+// launch, STABLY SORTED BY LAST ID on the host: phrase w is words[word_off[w] .. word_off[w + 1]) with bias[w] (fp32), and run q is
+// the phrases run_off[q] .. run_off[q + 1) -- all the phrases of one last id, in the order the caller listed them.  A column
+// belongs to one run and a run to one thread, so no two threads read-modify-write one column.  Phases:
+//   1. the last min(pos, DH_BEAM_MAX_BAD_LEN - 1) tokens of the history go to LDS; flags cleared;
+//   2. thread tid walks runs tid, tid + 256, ...: it loads the run's column once, walks the run's phrases in order -- a phrase of
+//      l ids with l - 1 <= pos whose first l - 1 ids equal the history's last l - 1 tokens fires (compared from the phrase's last
+//      prefix id backwards; l == 1 always fires) -- and adds the bias of each one that fires, every addition its own
+//      round-to-nearest fp32 add (__fadd_rn: never contracted, never re-associated), x = ((x + b1) + b2) ...; -inf stays -inf.  It
+//      stores the column once if any phrase fired.  A last id outside [0, V) is never a column; a phrase whose last id is not its
+//      run's (a list that was not sorted) is skipped, so the ownership holds whatever the list is;
+//   3. group_max != NULL: the repair of beam_constrain_logits_kernel's phase 4, same CONVENTION (exact fp32 maximum over the
+//      group's REAL columns < V, pads never read, groups without a store not written).  A raised column and a lowered one are the
+//      same case: the group is read back.
+__global__ __launch_bounds__(256) void beam_bias_logits_kernel(
+    float* logits, int ldl, int V, float* gmax, int gm_ld, int n_groups, int gcols, const int32_t* __restrict__ tokens, int tok_ld,
+    int tok_row_mult, int pos, int rows_per_img, const int32_t* __restrict__ first_pos, const int32_t* __restrict__ words,
+    const int32_t* __restrict__ word_off, const float* __restrict__ bias, const int32_t* __restrict__ run_off, int n_words, int n_runs) {
+    constexpr int NT = 256, MAXG = 1024, TAIL = DH_BEAM_MAX_BAD_LEN - 1;
+    __shared__ int tail[TAIL];                       // tail[T - 1] is the row's latest token
+    __shared__ int gflag[MAXG], glist[MAXG];
+    __shared__ int s_ng;
+    const int rc = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    if (first_pos && prompt_row_idle(first_pos, rc, rows_per_img, pos)) return;
+    float* row = logits + (size_t)rc * ldl;
+    const int32_t* h = tokens + (size_t)rc * tok_row_mult * tok_ld;
+    const int T = pos < TAIL ? pos : TAIL;
+    if (tid < T) tail[tid] = h[pos - T + tid];
+    if (gmax)
+        for (int g = tid; g < n_groups; g += NT) gflag[g] = 0;
+    if (tid == 0) s_ng = 0;
+    __syncthreads();
+    for (int q = tid; q < n_runs; q += NT) {
+        const int w0 = run_off[q], w1 = run_off[q + 1];
+        if (w0 < 0 || w1 > n_words || w0 >= w1) continue;
+        const int o0 = word_off[w0], l0 = word_off[w0 + 1] - o0;
+        if (l0 < 1 || l0 > DH_BEAM_MAX_BAD_LEN) continue;
+        const int t = words[o0 + l0 - 1];                // the run's column
+        if (t < 0 || t >= V) continue;
+        float x = row[t];
+        bool any = false;
+        for (int w = w0; w < w1; ++w) {
+            const int o = word_off[w], l = word_off[w + 1] - o;
+            if (l < 1 || l > DH_BEAM_MAX_BAD_LEN || l - 1 > pos || words[o + l - 1] != t) continue;
+            bool eq = true;
+            for (int k = 1; k < l && eq; ++k) eq = words[o + l - 1 - k] == tail[T - k];
+            if (eq) { x = __fadd_rn(x, bias[w]); any = true; }
+        }
+        if (any) {
+            row[t] = x;
+            if (gmax) {                   // (t < V <= n_groups * gcols) the column's group is listed once
+                const int g = t / gcols;
+                if (atomicExch(&gflag[g], 1) == 0) glist[atomicAdd(&s_ng, 1)] = g;
+            }
+        }
+    }
+    if (gmax) {
+        __threadfence_block();
+        __syncthreads();
+        // a list of single-id biases edits many groups of every row: each wave takes U listed groups at a time and issues their U
+        // loads before the first reduction, so a trip costs one memory latency, not U (beam_constrain_logits_kernel)
+        constexpr int U = 4;
+        const int ng = s_ng;
+        for (int q0 = wave * U; q0 < ng; q0 += (NT / 64) * U) {
+            float v[U];
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+                const bool on = q0 + u < ng;                         // (wave-uniform)
+                const int c = (on ? glist[q0 + u] : 0) * gcols + lane;
+                v[u] = (on && lane < gcols && c < V) ? row[c] : -INFINITY;
+            }
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+#pragma unroll
+                for (int s = 32; s > 0; s >>= 1) v[u] = fmaxf(v[u], __shfl_xor(v[u], s, 64));
+                if (lane == 0 && q0 + u < ng) gmax[(size_t)rc * gm_ld + glist[q0 + u]] = v[u];
+            }
+        }
+    }
+}
+
+extern "C" int dh_beam_bias_logits(float* logits, int ldl, int V, float* group_max, int gm_ld, int n_groups, int group_cols,
+                                   const int32_t* tokens, int tok_ld, int tok_row_mult, int pos, int rows, int rows_per_img,
+                                   const int32_t* first_pos, const int32_t* words, const int32_t* word_off, const float* bias,
+                                   const int32_t* run_off, int n_words, int n_runs, void* stream) {
+    DH_REQUIRE(logits && tokens && rows > 0 && rows_per_img > 0 && V > 0 && ldl >= V && tok_row_mult >= 1);
+    DH_REQUIRE(pos >= 0 && pos <= tok_ld);
+    DH_REQUIRE(n_words >= 1 && n_words <= DH_BEAM_MAX_BAD_WORDS && words && word_off && bias && run_off);   // an empty list: no launch
+    DH_REQUIRE(n_runs >= 1 && n_runs <= n_words);
+    DH_REQUIRE(!group_max || (n_groups > 0 && n_groups <= 1024 && gm_ld >= n_groups && group_cols > 0 && group_cols <= 64 &&
+                              (long long)n_groups * group_cols >= V));         // dh_beam_row_sample_groups' contract
+    DH_REQUIRE(!first_pos || rows % rows_per_img == 0);
+    DhProfScope prof("dh_beam_bias_logits", 0.0, 0.0, stream);
+    hipLaunchKernelGGL(beam_bias_logits_kernel, dim3(rows), dim3(256), 0, (hipStream_t)stream, logits, ldl, V, group_max, gm_ld,
+                       n_groups, group_cols, tokens, tok_ld, tok_row_mult, pos, rows_per_img, first_pos, words, word_off, bias, run_off,
+                       n_words, n_runs);
+    DH_LAUNCH_CHECK();
+}
+
 // ------------------------------------------------------------------------------------------------
 
 template <int MB, bool PR, bool DT = false, bool LN = false>

@@ -129,7 +129,7 @@ def generate_sharded(generate_fn, n_total, group=None, always=None):
             return model.generate_batch(images[lo:hi], caption=C[lo:hi], caption_lengths=L[lo:hi], img0=lo, seed=seed, **kw)
 
     Decode settings that look at nothing but a row's own logits and history (``top_p``, ``no_repeat_ngram_size``,
-    ``repetition_penalty``, ``min_len``, ``bad_words_ids``, ``search``, ``length_penalty``, ``early_stopping``, ``num_beam_groups`` / ``diversity_penalty``) ride in ``kw`` unchanged: a shard's captions are those of the
+    ``repetition_penalty``, ``min_len``, ``bad_words_ids``, ``sequence_bias``, ``search``, ``length_penalty``, ``early_stopping``, ``num_beam_groups`` / ``diversity_penalty``) ride in ``kw`` unchanged: a shard's captions are those of the
     whole batch."""
     rank = dist.get_rank(group) if dist.is_available() and dist.is_initialized() else 0
     world = dist.get_world_size(group) if dist.is_available() and dist.is_initialized() else 1

@@ -46,6 +46,36 @@ def bad_words_to_ids(words, vocab, tokenizer):
     return out
 
 
+def sequence_bias_from_words(word_bias, vocab, tokenizer):
+    """Words or phrases with a bias each, ``{"cat": 4.0, "damn": -3.0}`` or a list of ``(string, bias)`` pairs -> the list of
+    ``(token ids, bias)`` pairs ``generate_batch(..., sequence_bias=)`` takes, in the order given.  Every string goes through
+    ``text_to_seq`` (same lower-casing, same tokenizer, as ``bad_words_to_ids``); no ``<eos>`` is added.  A string with a token
+    outside the vocabulary maps to ``<unk>`` there; it is skipped, with ONE warning for all of them, because ``<unk>`` is never drawn
+    and such a phrase could never be completed.  An empty string is skipped too.  The biases are passed on as they are
+    (``beam.check_sequence_bias`` checks them with the call).
+
+    What a MULTI-TOKEN phrase means: the bias lands on the phrase's LAST token, and only once the other tokens are in place --
+    ``"hot dog": 5.0`` makes "dog" likelier behind "hot" and leaves "hot" alone (bias "hot" as well to steer a caption to the whole
+    phrase).  With the CHARACTER tokenizer a word is a run of characters, so it is such a phrase, and it matches as a SUBSTRING:
+    a bias on "cat" raises "t" behind "ca", inside "scatter" too."""
+    import warnings
+    unk = vocab.stoi[SPECIAL_TOKENS['UNK']]
+    items = list(word_bias.items()) if hasattr(word_bias, "items") else list(word_bias)
+    out, skipped = [], []
+    for word, bias in items:
+        ids = text_to_seq(word, vocab, tokenizer)[0].tolist() if word else []
+        if not ids:
+            continue
+        if unk in ids:
+            skipped.append(word)
+            continue
+        out.append((tuple(int(t) for t in ids), bias))
+    if skipped:
+        warnings.warn(f"sequence_bias_from_words: {len(skipped)} of {len(items)} strings hold a token outside the vocabulary (<unk> is "
+                      f"never drawn, nothing to steer) and are skipped: {skipped[:8]!r}", stacklevel=2)
+    return out
+
+
 def prompts_to_batch(texts, vocab, tokenizer):
     """The host text step in front of ``generate_batch(..., caption=C, caption_lengths=L)``: one optional caption beginning per
     image -> ``(C int64 [N, P], L int64 [N])``.  Every text goes through ``text_to_seq``; a trailing ``<eos>`` is dropped, as the

@@ -1059,6 +1059,27 @@ def beam_constrain_logits(logits, v, tokens, tok_row_mult, pos, rows, rows_per_i
             _ptr(word_off) if n_words else 0, int(n_words), _stream())
 
 
+def beam_bias_logits(logits, v, tokens, tok_row_mult, pos, rows, rows_per_img, words, word_off, bias, run_off, n_words, n_runs,
+                     group_max=None, first_pos=None):
+    """``dh_beam_bias_logits``: the ``sequence_bias`` of fp32 ``logits [rows, V]`` in place -- ``bias[w]`` (fp32) is added to the last
+    id of every phrase (``words`` int32 flat, ``word_off`` int32 ``[n_words + 1]``) whose other ids end the row's history
+    ``tokens[r * tok_row_mult, :pos]``; the list is stably sorted by last id and ``run_off`` (int32 ``[n_runs + 1]``) holds the starts
+    of the runs of phrases that share one (``beam.compile_sequence_bias`` makes all four).  ``group_max`` / ``first_pos``: as
+    ``beam_history_logits``."""
+    _dev(logits, tokens, group_max, first_pos, words, word_off, bias, run_off)
+    assert logits.dtype == torch.float32 and logits.stride(1) == 1 and tokens.dtype == torch.int32 and tokens.stride(1) == 1
+    assert group_max is None or group_max.dtype == torch.float32
+    assert first_pos is None or (first_pos.dtype == torch.int32 and first_pos.numel() * rows_per_img == rows)
+    assert (rows - 1) * tok_row_mult < tokens.shape[0]
+    assert words.dtype == torch.int32 and word_off.dtype == torch.int32 and run_off.dtype == torch.int32 and bias.dtype == torch.float32
+    assert words.is_contiguous() and word_off.is_contiguous() and bias.is_contiguous() and run_off.is_contiguous()
+    assert word_off.numel() == n_words + 1 and bias.numel() == n_words and run_off.numel() == n_runs + 1
+    _launch("dh_beam_bias_logits", _ptr(logits), logits.stride(0), v, _ptr(group_max),
+            group_max.stride(0) if group_max is not None else 0, n_groups(v), GROUP_COLS, _ptr(tokens), tokens.stride(0), tok_row_mult,
+            pos, rows, rows_per_img, _ptr(first_pos), _ptr(words), _ptr(word_off), _ptr(bias), _ptr(run_off), int(n_words), int(n_runs),
+            _stream())
+
+
 def beam_select_prompted(pick_idx, pick_val, tokens, vals, ended, src, parent, hparent, done, end_step, n_img, beam, first_pos,
                          first_sets_ended, write_pos, t, step_index, temperature, eos_index, noise, seed, img0, seed_ptr=None):
     """``beam_select`` with the phase of every image taken from ``first_pos`` (int32 ``[n_img]``) against ``step_index``."""

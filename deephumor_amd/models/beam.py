@@ -275,22 +275,26 @@ class _Search(str):
     (a plain string) is the record WITHOUT the penalty, and the penalty is only ever put here by ``from_kw``, which reads the
     ``length_penalty`` keyword and takes ``search`` as the plain string it spells.  Copies and pickles like the pair it is.
     ``early_stopping`` (``None``, ``True`` or ``False``) rides the same way, one more attribute; so do ``num_beam_groups`` and
-    ``diversity_penalty`` (``check_beam_groups``; 1 and 0.0: off)."""
+    ``diversity_penalty`` (``check_beam_groups``; 1 and 0.0: off), and ``sequence_bias`` (``check_sequence_bias``; ``None``: off) --
+    the one of them that also rides on ``"sample"``."""
     length_penalty = 0.0
     early_stopping = None
     num_beam_groups = 1
     diversity_penalty = 0.0
+    sequence_bias = None
 
-    def __new__(cls, search, length_penalty=0.0, early_stopping=None, num_beam_groups=1, diversity_penalty=0.0):
+    def __new__(cls, search, length_penalty=0.0, early_stopping=None, num_beam_groups=1, diversity_penalty=0.0, sequence_bias=None):
         self = str.__new__(cls, search)
         self.length_penalty = length_penalty
         self.early_stopping = early_stopping
         self.num_beam_groups = num_beam_groups
         self.diversity_penalty = diversity_penalty
+        self.sequence_bias = sequence_bias
         return self
 
     def __getnewargs__(self):
-        return (str.__str__(self), self.length_penalty, self.early_stopping, self.num_beam_groups, self.diversity_penalty)
+        return (str.__str__(self), self.length_penalty, self.early_stopping, self.num_beam_groups, self.diversity_penalty,
+                self.sequence_bias)
 
     def __reduce__(self):
         return (_Search, self.__getnewargs__())
@@ -356,8 +360,9 @@ class BadWords:
         return f"BadWords({len(self.ids)} phrases, device={self.device})"
 
 
-def _phrases(bad_words_ids, num_tokens=None):
-    """``bad_words_ids`` as a tuple of tuples of ints, every rule of ``check_constraints`` applied."""
+def _phrases(bad_words_ids, num_tokens=None, what="bad_words_ids"):
+    """``bad_words_ids`` as a tuple of tuples of ints, every rule of ``check_constraints`` applied (``what``: the keyword the
+    messages name -- ``check_sequence_bias`` checks its phrases here too)."""
     if isinstance(bad_words_ids, (str, bytes)) or not hasattr(bad_words_ids, "__iter__"):
         raise TypeError(f"bad_words_ids must be None or a sequence of sequences of token ids, not {type(bad_words_ids).__name__} "
                         "(strings go through experiments.bad_words_to_ids)")
@@ -366,21 +371,21 @@ def _phrases(bad_words_ids, num_tokens=None):
         if hasattr(phrase, "tolist"):                       # (a tensor or an array: its Python numbers)
             phrase = phrase.tolist()
         if isinstance(phrase, (str, bytes)) or not hasattr(phrase, "__iter__"):
-            raise ValueError(f"bad_words_ids: phrase {w} ({phrase!r}) is not a sequence of token ids")
+            raise ValueError(f"{what}: phrase {w} ({phrase!r}) is not a sequence of token ids")
         phrase = tuple(phrase)
         if not phrase:
-            raise ValueError(f"bad_words_ids: phrase {w} is empty")
+            raise ValueError(f"{what}: phrase {w} is empty")
         if len(phrase) > hip.MAX_BAD_LEN:
-            raise ValueError(f"bad_words_ids: phrase {w} has {len(phrase)} tokens, more than {hip.MAX_BAD_LEN} (DH_BEAM_MAX_BAD_LEN)")
+            raise ValueError(f"{what}: phrase {w} has {len(phrase)} tokens, more than {hip.MAX_BAD_LEN} (DH_BEAM_MAX_BAD_LEN)")
         for t in phrase:
             if isinstance(t, bool) or not isinstance(t, numbers.Integral):
-                raise ValueError(f"bad_words_ids: phrase {w} {phrase!r} holds {t!r}, which is not an integer token id")
+                raise ValueError(f"{what}: phrase {w} {phrase!r} holds {t!r}, which is not an integer token id")
             if t < 0 or (num_tokens is not None and t >= num_tokens):
-                raise ValueError(f"bad_words_ids: phrase {w} {phrase!r} holds id {int(t)} outside [0, "
+                raise ValueError(f"{what}: phrase {w} {phrase!r} holds id {int(t)} outside [0, "
                                  f"{'num_tokens' if num_tokens is None else num_tokens})")
         out.append(tuple(int(t) for t in phrase))
         if len(out) > hip.MAX_BAD_WORDS:
-            raise ValueError(f"bad_words_ids: phrase {w} is one more than the {hip.MAX_BAD_WORDS} a list may hold (DH_BEAM_MAX_BAD_WORDS)")
+            raise ValueError(f"{what}: phrase {w} is one more than the {hip.MAX_BAD_WORDS} a list may hold (DH_BEAM_MAX_BAD_WORDS)")
     return tuple(out)
 
 
@@ -449,6 +454,141 @@ def compile_bad_words(ids, num_tokens=None, device="cuda"):
     return bw
 
 
+MAX_SEQUENCE_BIAS = 1e4         # |bias| <= 1e4: 4,096 of them on one column sum to 4.1e7, far inside fp32
+
+
+class SequenceBias:
+    """A phrase-to-bias list compiled for ``dh_beam_bias_logits`` (``compile_sequence_bias``): ``pairs`` -- a tuple of ``(phrase,
+    bias)`` pairs, the phrases tuples of ints and the biases floats, in the order given, duplicates kept --, and four tensors on
+    ``device``, uploaded once, that hold the list STABLY SORTED BY LAST ID (so the phrases of one column are neighbours, in the order
+    given): ``words`` int32 (the phrases flat), ``offsets`` int32 (``n + 1`` entries), ``bias`` fp32 ``[n]`` and ``run_off`` int32
+    (``n_runs + 1`` entries: the starts of the runs of phrases that share a last id).  ``order``: the sort as a tuple of list
+    indices.  Immutable; hashable and equal by ``pairs`` and device, so it can sit in a graph cache key, and whoever holds it keeps
+    the tensors alive."""
+    __slots__ = ("pairs", "num_tokens", "device", "order", "words", "offsets", "bias", "run_off")
+
+    def __init__(self, pairs, num_tokens, device, order, words, offsets, bias, run_off):
+        for name, val in zip(self.__slots__, (pairs, num_tokens, device, order, words, offsets, bias, run_off)):
+            object.__setattr__(self, name, val)
+
+    def __setattr__(self, name, value):
+        raise AttributeError("SequenceBias is immutable")
+
+    def __delattr__(self, name):
+        raise AttributeError("SequenceBias is immutable")
+
+    @property
+    def n_words(self):
+        return len(self.pairs)
+
+    @property
+    def n_runs(self):
+        return self.run_off.numel() - 1
+
+    def __len__(self):
+        return len(self.pairs)
+
+    def __hash__(self):
+        return hash((self.pairs, str(self.device)))
+
+    def __eq__(self, other):
+        return isinstance(other, SequenceBias) and self.pairs == other.pairs and str(self.device) == str(other.device)
+
+    def __repr__(self):
+        return f"SequenceBias({len(self.pairs)} phrases, {self.n_runs} columns, device={self.device})"
+
+
+def check_sequence_bias(sequence_bias=None, num_tokens=None, model=None):
+    """ALL validation of ``sequence_bias``, checked where ``check_constraints`` is, before anything runs.
+
+    ``None`` (off, the call without the keyword), a ``SequenceBias``, a mapping ``{tuple of token ids: bias}`` or a sequence of
+    ``(phrase, bias)`` pairs -- in a defined order: the dict's insertion order, the list's own.  The phrases obey ``bad_words_ids``'
+    limits (at most ``hip.MAX_BAD_WORDS`` phrases of at most ``hip.MAX_BAD_LEN`` ids, every id an integer in ``[0, num_tokens)``);
+    every bias is a finite real number with ``abs(bias) <= MAX_SEQUENCE_BIAS`` -- a ``bool``, NaN or an infinity is a ``ValueError``
+    that names the phrase (a ban is ``bad_words_ids``' business).  Duplicated phrases are allowed and each one counts; an empty
+    mapping is ``None``.  With ``model`` (a captioning model or its decoder) and a list that is not empty, ``pad_index == 1`` is
+    refused: that decoder re-runs the whole sequence per token on the module path -- ``NotImplementedError``, as ``return_logprobs``
+    there.  Returns ``None | SequenceBias | tuple of (tuple of ints, float) pairs``."""
+    sb = _checked_sequence_bias(sequence_bias, num_tokens)
+    if sb is not None and model is not None and getattr(getattr(model, "decoder", model), "pad_index", 0) == 1:
+        raise NotImplementedError("sequence_bias with pad_index == 1: that decoder re-runs the whole sequence per token on the module "
+                                  "path (_generate_reforward); the biases live in the batched engine's per-position row draw")
+    return sb
+
+
+def _checked_sequence_bias(sb, num_tokens):
+    if sb is None:
+        return None
+    if isinstance(sb, SequenceBias):
+        if num_tokens is not None and (sb.num_tokens is None or sb.num_tokens > num_tokens):
+            _phrases([w for w, _ in sb.pairs], num_tokens, "sequence_bias")      # compiled for a larger vocabulary: the ids against this one
+        return sb if len(sb) else None
+    if isinstance(sb, (str, bytes)) or not hasattr(sb, "__iter__"):
+        raise TypeError(f"sequence_bias must be None, a mapping {{tuple of token ids: bias}} or a sequence of (phrase, bias) pairs, not "
+                        f"{type(sb).__name__} (strings go through experiments.sequence_bias_from_words)")
+    items = list(sb.items()) if hasattr(sb, "items") else list(sb)
+    for w, item in enumerate(items):
+        if isinstance(item, (str, bytes)) or not hasattr(item, "__len__") or len(item) != 2:
+            raise ValueError(f"sequence_bias: entry {w} ({item!r}) is not a (phrase, bias) pair")
+    phrases = _phrases([item[0] for item in items], num_tokens, "sequence_bias")
+    out = []
+    for w, (phrase, (_, b)) in enumerate(zip(phrases, items)):
+        if hasattr(b, "item") and getattr(b, "ndim", 1) == 0:              # (a 0-d tensor or a numpy scalar: its Python number)
+            b = b.item()
+        if isinstance(b, bool) or not isinstance(b, numbers.Real) or not math.isfinite(b) or abs(b) > MAX_SEQUENCE_BIAS:
+            raise ValueError(f"sequence_bias: phrase {w} {phrase!r} has bias {b!r}: a bias is a finite real number with abs(bias) <= "
+                             f"{MAX_SEQUENCE_BIAS:g} (to forbid a phrase outright, list it in bad_words_ids)")
+        out.append((phrase, float(b)))
+    return tuple(out) or None
+
+
+def sort_sequence_bias(pairs):
+    """The host side of ``dh_beam_bias_logits``' layout: ``(order, run_off)`` -- the indices of ``pairs`` stably sorted by the
+    phrases' last ids, and the starts of the runs of equal last ids in that order, with the list's length as the last entry."""
+    order = sorted(range(len(pairs)), key=lambda i: pairs[i][0][-1])            # (sorted is stable)
+    run_off = [i for i in range(len(order)) if i == 0 or pairs[order[i]][0][-1] != pairs[order[i - 1]][0][-1]]
+    return tuple(order), run_off + [len(order)]
+
+
+_SEQ_BIAS_CACHE = {}            # (device, num_tokens, pairs) -> SequenceBias: a list is uploaded once, not once per call
+_SEQ_BIAS_CACHE_SIZE = 16
+
+
+def compile_sequence_bias(sequence_bias, num_tokens=None, device="cuda"):
+    """``sequence_bias`` -> ``SequenceBias`` on ``device`` (``None`` for ``None`` / an empty mapping; a ``SequenceBias`` of that
+    device as it is).  Validates like ``check_sequence_bias``, sorts the list (``sort_sequence_bias``) and uploads it once; a small
+    per-device cache keyed by the pairs gives repeated calls with one list the same tensors.  Not inside a hipGraph capture (a
+    host-to-device copy): ``generate_batch_graphed`` compiles in front of it."""
+    pairs = check_sequence_bias(sequence_bias, num_tokens)
+    if pairs is None:
+        return None
+    device = torch.device(device)
+    if device.type == "cuda" and device.index is None:
+        device = torch.device("cuda", torch.cuda.current_device())
+    if isinstance(pairs, SequenceBias):
+        if str(pairs.device) == str(device):
+            return pairs
+        pairs = pairs.pairs
+    key = (str(device), num_tokens, pairs)
+    sb = _SEQ_BIAS_CACHE.get(key)
+    if sb is None:
+        if device.type == "cuda" and torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("compile_sequence_bias inside a hipGraph capture: compile the list before the capture and pass the "
+                               "SequenceBias")
+        order, run_off = sort_sequence_bias(pairs)
+        offs = [0]
+        for i in order:
+            offs.append(offs[-1] + len(pairs[i][0]))
+        words = torch.tensor([t for i in order for t in pairs[i][0]], dtype=torch.int32).to(device)
+        offsets = torch.tensor(offs, dtype=torch.int32).to(device)
+        bias = torch.tensor([pairs[i][1] for i in order], dtype=torch.float64).to(torch.float32).to(device)
+        sb = SequenceBias(pairs, num_tokens, device, order, words, offsets, bias, torch.tensor(run_off, dtype=torch.int32).to(device))
+        while len(_SEQ_BIAS_CACHE) >= _SEQ_BIAS_CACHE_SIZE:
+            _SEQ_BIAS_CACHE.pop(next(iter(_SEQ_BIAS_CACHE)))
+        _SEQ_BIAS_CACHE[key] = sb
+    return sb
+
+
 @dataclasses.dataclass(frozen=True, eq=False)
 class DecodeSettings:
     """The validated decode settings of one call -- ``return_beams``, ``return_attention``, ``top_p``, ``no_repeat_ngram_size``,
@@ -461,7 +601,9 @@ class DecodeSettings:
     ``from_kw``, carried by ``search`` (``_Search``) so that ``replace`` and ``compiled`` keep it, and in the key; ``early_stopping``
     (``check_early_stopping``; ``None``: off) travels the same way, in the key in front of ``length_penalty``; ``num_beam_groups`` /
     ``diversity_penalty`` (``check_beam_groups``; 1 / 0.0: off) too -- their pair is ONE more key element, in front of all the others
-    and only with more than one group, so the key of a record without groups is what it was.  Built by
+    and only with more than one group, so the key of a record without groups is what it was; ``sequence_bias``
+    (``check_sequence_bias``; ``None``: off) the same -- carried by ``search`` under ``"sample"`` as well, compiled by ``compiled``, and
+    in the key only when set, as ``("sequence_bias", pairs)`` in front of everything else.  Built by
     ``from_kw`` only.  Immutable; equal and hashed by the settings, the list by its ids whether compiled or not."""
     return_beams: bool = False
     return_attention: bool = False
@@ -480,6 +622,7 @@ class DecodeSettings:
         object.__setattr__(self, "early_stopping", getattr(self.search, "early_stopping", None))
         object.__setattr__(self, "num_beam_groups", getattr(self.search, "num_beam_groups", 1))
         object.__setattr__(self, "diversity_penalty", getattr(self.search, "diversity_penalty", 0.0))
+        object.__setattr__(self, "sequence_bias", getattr(self.search, "sequence_bias", None))
 
     @classmethod
     def from_kw(cls, kw, max_len, num_tokens=None, model=None):
@@ -497,13 +640,16 @@ class DecodeSettings:
         early_stopping = check_early_stopping(kw.get("early_stopping"), search, return_attention, return_logprobs)
         groups, diversity = check_beam_groups(kw.get("num_beam_groups", 1), kw.get("diversity_penalty", 0.0), search, kw.get("beam_size"),
                                               early_stopping)
-        if length_penalty != 0.0 or early_stopping is not None or groups > 1:
-            search = _Search(search, length_penalty, early_stopping, groups, diversity)
+        bias = check_sequence_bias(kw.get("sequence_bias"), num_tokens, model)     # (the newest control: checked last)
+        if length_penalty != 0.0 or early_stopping is not None or groups > 1 or bias is not None:
+            search = _Search(search, length_penalty, early_stopping, groups, diversity, bias)
         return cls(return_beams, return_attention, top_p, ngram, penalty, min_len, bad_words, num_tokens, search, return_logprobs)
 
     def _key(self):
-        bw = self.bad_words_ids
+        bw, sb = self.bad_words_ids, self.sequence_bias
         groups = ((self.num_beam_groups, self.diversity_penalty),) if self.num_beam_groups > 1 else ()
+        if sb is not None:                # one more element at the very front, only when set: ("sequence_bias", pairs)
+            groups = (("sequence_bias", sb.pairs if isinstance(sb, SequenceBias) else sb),) + groups
         return groups + (self.return_beams, self.return_attention, self.top_p, self.no_repeat_ngram_size, self.repetition_penalty, self.min_len,
                 bw.ids if isinstance(bw, BadWords) else bw, self.early_stopping, self.length_penalty, self.return_logprobs, self.search)
 
@@ -516,14 +662,17 @@ class DecodeSettings:
     def compiled(self, device):
         """The record with its phrase list uploaded to ``device`` (``compile_bad_words``: once per list, not inside a capture)."""
         # (``length_penalty`` rides on ``search`` and so stays; its table is uploaded by ``compile_length_weights``, per session length)
-        return dataclasses.replace(self, bad_words_ids=compile_bad_words(self.bad_words_ids, self.num_tokens, device))
+        search = self.search
+        if self.sequence_bias is not None:                 # the bias list rides on ``search`` too: the same string with the compiled list
+            search = _Search(*search.__getnewargs__()[:-1], compile_sequence_bias(self.sequence_bias, self.num_tokens, device))
+        return dataclasses.replace(self, bad_words_ids=compile_bad_words(self.bad_words_ids, self.num_tokens, device), search=search)
 
     def new_helper(self, **engine_args):
         """The ``BeamSearchHelper`` of one session with every setting applied; ``engine_args``: the constructor's other arguments."""
         return BeamSearchHelper(top_p=self.top_p, no_repeat_ngram_size=self.no_repeat_ngram_size, repetition_penalty=self.repetition_penalty,
                                 **engine_args).set_constraints(self.min_len, self.bad_words_ids).set_search(self.search).set_logprobs(
                                     self.return_logprobs).set_length_penalty(self.length_penalty).set_early_stopping(self.early_stopping).set_beam_groups(
-                                        self.num_beam_groups, self.diversity_penalty)
+                                        self.num_beam_groups, self.diversity_penalty).set_sequence_bias(self.sequence_bias)
 
 
 class BeamOverflow(RuntimeError):
@@ -692,6 +841,15 @@ class BeamSearchHelper:
     defaults ``0`` / ``None`` make none.  Both are set with ``helper.set_constraints(min_len=, bad_words_ids=)`` after construction
     (``bad_words_ids``: the raw nesting, compiled there by ``compile_bad_words``, or a ``BadWords``).
 
+    ``sequence_bias`` (not in the reference either; Hugging Face's name): between those two launches, one launch of
+    ``dh_beam_bias_logits`` -- for every ``(phrase, bias)`` pair of the list whose first ``l - 1`` ids end the row's own history
+    (a single id: at every position), ``bias`` is added to the logit of the phrase's last id; several pairs on one column are added
+    one after the other in list order, each addition its own fp32 add; ``-inf`` stays ``-inf``, so a banned token stays banned.
+    Behind the history edits because the penalty scales the model's logit; the maxima are repaired on the same condition as
+    above.  Under ``search="beam"`` the scores, and with ``logprobs`` the log-probabilities, are taken on the biased rows.  A launch
+    is made only with a list; ``None``, the default, makes none.  Set with ``helper.set_sequence_bias(mapping or pairs or
+    SequenceBias)`` after construction.
+
     ``search="beam"`` (not in the reference either; ``helper.set_search("beam")`` after construction): nothing is drawn.  Behind the
     history edits and the bans every live row keeps the ``beam_size`` columns with the largest logit (never ``unk_index``; equal
     logits to the lower index), each with its log-probability ``x / temperature - logsumexp(x / temperature)`` over the whole row
@@ -770,7 +928,8 @@ class BeamSearchHelper:
         self.early_stopping = None        # True / False: the finished-hypothesis pool (set_early_stopping)
         self.pool_tokens = self.pool_keys = self.pool_vals = self.pool_len = self.pool_n = None
         self.num_beam_groups, self.diversity_penalty = 1, 0.0      # diverse groups of beams: set_beam_groups
-        self.exact = bool(exact)          # row draws through the general sampler only (see BeamOverflow)
+        self.sequence_bias = None         # a compiled SequenceBias: set_sequence_bias
+        self.exact = bool(exact)         # row draws through the general sampler only (see BeamOverflow)
         if beam_size > hip.MAX_BEAMS:     # one wave draws among an image's beams (dh_beam_finalize); the reference has no limit
             raise ValueError(f"beam_size <= {hip.MAX_BEAMS} supported")
         self.temperature, self.beam_size, self.top_k = float(temperature), int(beam_size), int(top_k)
@@ -902,6 +1061,14 @@ class BeamSearchHelper:
             self.len_w = self.keys = None
         return self
 
+    def set_sequence_bias(self, sequence_bias=None):
+        """``sequence_bias`` of this session (see the class docstring), validated by ``check_sequence_bias``; a mapping or a list of
+        pairs is compiled here (``compile_sequence_bias``: one upload, so not inside a hipGraph capture), a ``SequenceBias`` is taken
+        as it is.  ``None``, the default: no launch is made.  A method like ``set_constraints``: the constructor's parameter list
+        stays as it is.  Returns the helper."""
+        self.sequence_bias = compile_sequence_bias(sequence_bias, None, self.device)
+        return self
+
     def set_prefix(self, caption):
         """caption int64 [n_img, p]: teacher-forced beginning, copied to every beam row."""
         p = caption.shape[1]
@@ -950,7 +1117,7 @@ class BeamSearchHelper:
         self._draw_and_select(logits, first, write_pos, t, step_index, first_sets_ended, group_max)
 
     def _draw_and_select(self, logits, first, write_pos, t, step_index, first_sets_ended, group_max, prompted=False):
-        """``step`` and ``step_prompted``: the history edits, the bans, the row draw and the select, in that order."""
+        """``step`` and ``step_prompted``: the history edits, the biases, the bans, the row draw and the select, in that order."""
         rows, v = logits.shape
         b = self.beam_size
         rpi = 1 if first else b
@@ -968,6 +1135,12 @@ class BeamSearchHelper:
         if self._history_edits:           # no_repeat_ngram_size / repetition_penalty: the row's own history edits its logits first
             hip.beam_history_logits(logits, v, self.tokens, mult, write_pos, rows, rpi, self.no_repeat_ngram_size,
                                     self.repetition_penalty, group_max=gm, first_pos=first_pos)
+        # sequence_bias: behind the history edits (the penalty scales the MODEL's logit) and in front of the bans (they commute:
+        # -inf + b = -inf).  A launch only with a list; the maxima are repaired on the same condition
+        sb = self.sequence_bias
+        if sb is not None:
+            hip.beam_bias_logits(logits, v, self.tokens, mult, write_pos, rows, rpi, sb.words, sb.offsets, sb.bias, sb.run_off, len(sb),
+                                 sb.n_runs, group_max=gm, first_pos=first_pos)
         # min_len / bad_words_ids: the bans behind the history edits (both store ``-inf`` or map it to itself, so the order does not
         # show).  A launch only when there is something to ban at this position
         bw = self.bad_words
@@ -1184,6 +1357,9 @@ class BeamSearchHelper:
                                       "engine's row draw (step / step_prompted); the reference-style method surface has none")
         if self._constraints:
             raise NotImplementedError(f"{what} with min_len / bad_words_ids: the bans live in the batched engine's row draw (step / "
+                                      "step_prompted); the reference-style method surface has none")
+        if self.sequence_bias is not None:
+            raise NotImplementedError(f"{what} with sequence_bias: the biases live in the batched engine's row draw (step / "
                                       "step_prompted); the reference-style method surface has none")
         if self.search == "beam":
             raise NotImplementedError(f'{what} with search="beam": the deterministic search lives in the batched engine\'s steps (step / '

@@ -87,7 +87,12 @@ class _CaptioningBase(nn.Module):
         diverse beam search -- the beams are ``num_beam_groups`` groups that choose one after the other at every position, a group's
         candidates losing ``diversity_penalty`` for every earlier group that took the same token there; scores stay model
         log-probabilities, ``beam_index // (beam_size // num_beam_groups)`` is a beam's group and ``experiments.group_best`` returns
-        each group's best beam; refused with ``early_stopping`` (``LSTMDecoder.generate_batch`` has the full contract)."""
+        each group's best beam; refused with ``early_stopping`` (``LSTMDecoder.generate_batch`` has the full contract).
+        ``sequence_bias`` (in ``kw``; ``None``, the default, is the call without it): a mapping ``{tuple of token ids: bias}`` or a list
+        of ``(phrase, bias)`` pairs -- the bias is added to the logit of a phrase's last id wherever the phrase's other ids end the
+        row's history, a single id everywhere: positive steers towards a token, negative away from it without forbidding it;
+        ``experiments.sequence_bias_from_words`` makes one from strings; ``pad_index == 1`` raises ``NotImplementedError``
+        (``LSTMDecoder.generate_batch`` has the full contract)."""
         if caption_lengths is not None:
             kw["caption_lengths"] = caption_lengths
         return self.decoder.generate_batch(*encoded, caption=caption, max_len=max_len, temperature=temperature,
@@ -109,6 +114,8 @@ class _CaptioningBase(nn.Module):
             kw.pop("length_penalty", None)        # (the same)
         if settings.early_stopping is None:
             kw.pop("early_stopping", None)        # (the same)
+        if settings.sequence_bias is None:
+            kw.pop("sequence_bias", None)         # (the same: ``None`` or an empty mapping)
         if caption_lengths is None:
             return None
         if getattr(self.decoder, "pad_index", 0) == 1:
@@ -199,6 +206,12 @@ class _CaptioningBase(nn.Module):
         # tensors alive
         if "bad_words_ids" in kw:
             kw["bad_words_ids"] = settings.compiled(inputs[0].device).bad_words_ids
+        # ``sequence_bias`` (one dh_beam_bias_logits node per position): the same -- ``None`` / an empty mapping is the call without the
+        # keyword, a list is compiled in front of the capture and its hashable ``SequenceBias`` is in the key below, which keeps the
+        # four tensors the captured nodes point at alive for as long as the graph is cached
+        kw.pop("sequence_bias", None)
+        if settings.sequence_bias is not None:
+            kw["sequence_bias"] = settings.compiled(inputs[0].device).sequence_bias
         if settings.search == "sample":
             kw.pop("search", None)                    # (the default is the call without the keyword: the plain graph, not a second one)
         if kw.get("rng") == "torch" and settings.search != "beam":      # host-generated noise (parity mode): nothing to replay

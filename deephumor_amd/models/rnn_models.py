@@ -191,7 +191,7 @@ class LSTMDecoder(_Planned, nn.Module):
         return hs, bs, steps_out
 
     @_later_keywords("min_len", "bad_words_ids", "search", "return_logprobs", "num_beam_groups", "diversity_penalty", "length_penalty",
-                     "early_stopping")
+                     "early_stopping", "sequence_bias")
     def generate_batch(self, image_emb, caption=None, max_len=25, temperature=1.0, beam_size=10, top_k=50,
                        eos_index=3, seed=None, img0=0, noise_source=None, logits_hook=None, streams=1, seed_tensor=None,
                        defer_check=False, early_stop_every=0, exact=False, rng=None, *, caption_lengths=None, return_beams=False, top_p=1.0,
@@ -286,7 +286,17 @@ class LSTMDecoder(_Planned, nn.Module):
         ``dh_beam_select_groups`` in place of the select, one launch per position for all groups; ``1`` / ``0.0``, the defaults, are
         the call without the keywords: same launches, same bits.  ``G > 1`` with ``search="sample"`` or without a penalty:
         ``ValueError``; with ``early_stopping``: ``NotImplementedError`` (a pool per group is the follow-up).
-        ``min_len``, ``bad_words_ids``, ``search``, ``return_logprobs``, ``num_beam_groups``, ``diversity_penalty``, ``length_penalty`` and ``early_stopping`` are not in the parameter list above, which ends at
+        ``sequence_bias`` (keyword only; ``None``, a mapping ``{tuple of token ids: bias}``, a sequence of ``(phrase, bias)`` pairs, or
+        a ``beam.SequenceBias`` from ``beam.compile_sequence_bias``; one list for the batch; ``beam.check_sequence_bias``): the soft
+        counterpart of ``bad_words_ids`` -- ``bias`` is added to the logit of a phrase's last id in every row whose own history
+        (prompt included, per beam row) ends with the phrase's other ids; a single id is biased at every position.  Positive values
+        steer captions towards a token, negative ones away from it without forbidding it; every bias is finite with ``abs(bias) <=
+        1e4``.  Pairs that meet on one column are added in list order, each its own fp32 add; ``-inf`` stays ``-inf`` (a banned
+        token stays banned).  One launch of ``dh_beam_bias_logits`` behind the history edits and in front of the bans; under
+        ``search="beam"`` the scores, and with ``return_logprobs`` the log-probabilities, are those of the biased rows;
+        ``logits_hook`` still sees the raw logits.  ``None`` or an empty mapping is the call without the keyword: same launches,
+        same bits.
+        ``min_len``, ``bad_words_ids``, ``search``, ``return_logprobs``, ``num_beam_groups``, ``diversity_penalty``, ``length_penalty``, ``early_stopping`` and ``sequence_bias`` are not in the parameter list above, which ends at
         ``repetition_penalty`` as it did: they are taken by name (``_later_keywords``) and handed to ``_decode_session``, the
         implementation, which spells every keyword out."""
         return self._generate_batch(image_emb, caption, max_len, temperature, beam_size, top_k, eos_index, seed, img0, noise_source,
@@ -325,13 +335,14 @@ class LSTMDecoder(_Planned, nn.Module):
                         eos_index=3, seed=None, img0=0, noise_source=None, logits_hook=None, streams=1, seed_tensor=None,
                         defer_check=False, early_stop_every=0, exact=False, rng=None, *, caption_lengths=None, return_beams=False, top_p=1.0,
                         no_repeat_ngram_size=0, repetition_penalty=1.0, min_len=0, bad_words_ids=None, search="sample",
-                        return_logprobs=False, num_beam_groups=1, diversity_penalty=0.0, length_penalty=0.0, early_stopping=None):
+                        return_logprobs=False, sequence_bias=None, num_beam_groups=1, diversity_penalty=0.0, length_penalty=0.0,
+                        early_stopping=None):
         """The implementation of ``generate_batch``, every keyword spelled out."""
         settings = DecodeSettings.from_kw(dict(return_beams=return_beams, top_p=top_p, no_repeat_ngram_size=no_repeat_ngram_size,
                                                repetition_penalty=repetition_penalty, min_len=min_len, bad_words_ids=bad_words_ids,
                                                search=search, return_logprobs=return_logprobs, length_penalty=length_penalty,
                                                early_stopping=early_stopping, num_beam_groups=num_beam_groups,
-                                               diversity_penalty=diversity_penalty, beam_size=beam_size),
+                                               diversity_penalty=diversity_penalty, beam_size=beam_size, sequence_bias=sequence_bias),
                                           max_len, self.num_tokens)
         if settings.search == "beam":     # nothing is drawn: no generator is read, no noise source is asked
             rng, noise_source, seed = None, None, 0

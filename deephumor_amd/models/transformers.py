@@ -554,15 +554,15 @@ class _IncrementalDecoder(_Planned, nn.Module):
                         seed=None, img0=0, noise_source=None, logits_hook=None, streams=1, seed_tensor=None,
                         defer_check=False, early_stop_every=0, exact=False, rng=None, caption_lengths=None, return_beams=False, top_p=1.0,
                         no_repeat_ngram_size=0, repetition_penalty=1.0, min_len=0, bad_words_ids=None, return_attention=False,
-                        search="sample", return_logprobs=False, num_beam_groups=1, diversity_penalty=0.0, length_penalty=0.0,
-                        early_stopping=None):
+                        search="sample", return_logprobs=False, sequence_bias=None, num_beam_groups=1, diversity_penalty=0.0,
+                        length_penalty=0.0, early_stopping=None):
         """The implementation of ``generate_batch`` / ``generate``, every keyword spelled out."""
         settings = DecodeSettings.from_kw(dict(return_beams=return_beams, return_attention=return_attention, top_p=top_p,
                                                no_repeat_ngram_size=no_repeat_ngram_size, repetition_penalty=repetition_penalty,
                                                min_len=min_len, bad_words_ids=bad_words_ids, search=search,
                                                return_logprobs=return_logprobs, length_penalty=length_penalty,
                                                early_stopping=early_stopping, num_beam_groups=num_beam_groups,
-                                               diversity_penalty=diversity_penalty, beam_size=beam_size),
+                                               diversity_penalty=diversity_penalty, beam_size=beam_size, sequence_bias=sequence_bias),
                                           max_len, self.num_tokens, self)
         if settings.search == "beam":     # nothing is drawn: no generator is read, no noise source is asked
             rng, noise_source, seed = None, None, 0
@@ -693,7 +693,7 @@ class TransformerDecoder(_IncrementalDecoder):
                        top_k=50, eos_index=3, *, caption_lengths=None, **kw):
         """``start_emb [N, D]``, ``enc_out [N, S, D]`` -> ``(tokens [N, max_len], lengths [N])``.  ``caption_lengths`` (keyword only):
         a prompt of its own length per image; ``return_beams``, ``top_p``, ``no_repeat_ngram_size`` / ``repetition_penalty``, ``min_len`` /
-        ``bad_words_ids``, ``search`` (in ``kw``): see ``LSTMDecoder.generate_batch`` for all;
+        ``bad_words_ids``, ``sequence_bias``, ``search`` (in ``kw``): see ``LSTMDecoder.generate_batch`` for all;
         ``return_attention=True`` (in ``kw``): one more result, the fp32 map of where every token looked -- ``attention [N, T, S]``
         behind the pair, or ``[N, B, T, S]`` behind the ``BeamCaptions`` -- see ``caption_models._CaptioningBase.decode``;
         ``return_logprobs=True`` (in ``kw``): last, every token's model log-probability, ``logprobs [N, T]`` or ``[N, B, T]`` -- see there."""

@@ -43,6 +43,7 @@ class CaptionPipeline:
         ``length_penalty`` (beside it): its candidates are ranked by length-normalised score (see there); ``early_stopping`` (beside
         it, ``True`` / ``False``): finished hypotheses go to a pool and an image stops when it is full (see there);
         ``num_beam_groups`` / ``diversity_penalty`` (beside it): the beams are diverse groups (see there).
+        ``sequence_bias`` (one of ``gen_kw``): every batch is steered towards or away from the listed phrases (see there).
         ``preprocess``: optional callable mapping the staged device tensors of a batch to ``model.encode``'s inputs
         (e.g. ``u8_preprocess(model)``); it runs on the encode stream in front of the encoder.  ``gen_kw`` goes to every batch's
         ``model.decode`` unchanged: ``caption`` -- and with it ``caption_lengths``, one prompt length per image -- is per pipeline,
@@ -60,6 +61,8 @@ class CaptionPipeline:
             raise NotImplementedError("return_logprobs: CaptionPipeline hands batches over through pinned (tokens, lengths) / BeamCaptions "
                                       "slots that carry no float payload; call model.generate_batch(..., return_logprobs=True)")
         gen_kw.pop("return_logprobs", None)          # (the same)
+        if settings.sequence_bias is None:
+            gen_kw.pop("sequence_bias", None)        # (``None`` / an empty mapping: the same; a list is compiled once, by the first batch)
         self.model, self.gen_kw, self.overlap, self.preprocess = model, gen_kw, overlap, preprocess
         self.dev = next(model.parameters()).device
         if overlap:

@@ -690,6 +690,27 @@ int dh_beam_constrain_logits(float* logits, int ldl, int V, float* group_max, in
                              const int32_t* first_pos, int eos_index, int min_len, const int32_t* words, const int32_t* word_off,
                              int n_words, void* stream);
 
+/* ---- Biases in front of a row draw: sequence_bias, a finite number added to a token's logit when the token would complete a phrase,
+ * IN PLACE on fp32 logits [rows, ldl], one launch, on the row geometry of dh_beam_constrain_logits (history h[0 .. pos) =
+ * tokens[r * tok_row_mult, 0 .. pos); first_pos: idle rows untouched).  The list is shared by all rows and is STABLY SORTED BY LAST
+ * ID by the caller: phrase w is words[word_off[w] .. word_off[w+1]) (int32, device; n_words + 1 offsets; 1 .. DH_BEAM_MAX_BAD_LEN
+ * ids, n_words in 1 .. DH_BEAM_MAX_BAD_WORDS) with bias[w] (fp32, device); run q is the phrases run_off[q] .. run_off[q+1) (int32,
+ * device; n_runs + 1 entries): all the phrases of one last id, in the caller's list order.  Per row:
+ *   1. for every run, x = logits[last id]; for every phrase w of the run IN ORDER, of l ids with l - 1 <= pos and
+ *      h[pos-l+1 .. pos) == w[0 .. l-1) (l == 1: at every pos): x = x + bias[w], each addition one round-to-nearest fp32 add; the
+ *      column is stored once if any phrase fired (-inf stays -inf).  A last id outside [0, V) is never a column; prefix ids are
+ *      compared as they are; a phrase whose last id is not its run's is skipped;
+ *   2. group_max != NULL: as dh_beam_history_logits' step 3 -- every group holding a column that 1 stored to is recomputed as the
+ *      exact fp32 maximum over its real columns (< V); no other group, no other logit is written.  Pass group_max exactly when the
+ *      sampler that follows reads it.
+ * Behind dh_beam_history_logits (the penalty scales the model's logit) and on either side of dh_beam_constrain_logits (-inf + b =
+ * -inf).  pos <= tok_ld; an empty list is DH_ERR_BAD_ARG: the caller makes no launch then.  pos is a launch constant, so the call
+ * can be captured into a hipGraph. */
+int dh_beam_bias_logits(float* logits, int ldl, int V, float* group_max, int gm_ld, int n_groups, int group_cols,
+                        const int32_t* tokens, int tok_ld, int tok_row_mult, int pos, int rows, int rows_per_img,
+                        const int32_t* first_pos, const int32_t* words, const int32_t* word_off, const float* bias,
+                        const int32_t* run_off, int n_words, int n_runs, void* stream);
+
 /* ---- BeamSearchHelper's METHOD surface (deephumor/models/beam.py:32-108), for callers that drive the helper the way the
  * reference's own generate() loops do (rnn_models.py:87-128, transformers.py:532-569): one image, host-driven, tensors of the
  * reference's shapes and dtypes.  The batched engine (dh_beam_row_sample / dh_beam_select above) does not need them. */
