@@ -1293,7 +1293,10 @@ __global__ __launch_bounds__(512, 1) void vocab256_kernel(VocabParams p) {
                 }
                 mxv = fmaxf(mxv, __shfl_xor(mxv, 16, 64));
                 mxv = fmaxf(mxv, __shfl_xor(mxv, 32, 64));
-                if (lq == 0 && m < p.M && p.gmax && n0 + wn0 < ((p.N + 63) / 64) * 64 + 64) {
+                // the row holds 2 * ceil(V / 128) groups, as on every other route: a 256-column tile's groups behind them belong to
+                // the caller (a bound of one group past V's own stored -inf into the caller's next word when gm_ld had room for it
+                // and V % 256 was in 65..128)
+                if (lq == 0 && m < p.M && p.gmax && n0 + wn0 < ((p.N + 127) / 128) * 128) {
                     const int gidx = (n0 + wn0) / 64;
                     if (gidx < p.gmax_ld) p.gmax[(size_t)m * p.gmax_ld + gidx] = mxv;       // -inf for a group past V
                 }

@@ -226,12 +226,14 @@ def test_vocab_logits_full_size_repeatable(hip):
             assert torch.equal(gmax, want_g), (rep, ld)
 
 
-@pytest.mark.parametrize("rows,v", [(512, 5000), (768, 36541), (2560, 4100), (1280, 8192)])
+@pytest.mark.parametrize("rows,v", [(512, 5000),      # the abandoned plan: a two-tile launch needs 128 panels, V = 5000 has 40 -> vocab_logits_kernel
+                                    (512, 16300), (768, 36541), (2560, 4100), (1280, 8192)])
 def test_vocab_logits_256_row_tiles(hip, rows, v):
-    """vocab_areg256_kernel (A-stationary, 256-row tiles, no edge path): bit-equal to dh_linear for row counts that are
-    multiples of 256, vocabularies that end inside a panel / inside a 64-column group (clamped weight rows must not disturb
-    the boundary group's maximum) and exact multiples of 128; padding columns of the row stride are the only bytes it may
-    write besides the logits."""
+    """Row counts that are multiples of 256 on a row stride of whole panels -- vocab_areg256_kernel (A-stationary, 256-row tiles,
+    no edge path) wherever its launch plan holds, (512, 5000) the tile kernel (which kernel ran is asserted in
+    test_vocab_routes_gpu.py): bit-equal to dh_linear for vocabularies that end inside a panel / inside a 64-column group
+    (clamped weight rows must not disturb the boundary group's maximum) and exact multiples of 128; padding columns of the row
+    stride are the only bytes a call may write besides the logits."""
     k = 512
     a, w, b = bf(rnd(rows, k, seed=31)).cuda(), bf(rnd(v, k, seed=32) * 0.1).cuda(), rnd(v, seed=33).cuda()
     ref = hip.linear(a, w, b, out_dtype=torch.float32)
