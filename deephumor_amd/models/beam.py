@@ -269,37 +269,6 @@ def held_length_weights(length_penalty, device, early_stopping=None, num_beam_gr
     return tuple(w for (dev, lp, _), w in _LEN_W_CACHE.items() if dev == str(device) and lp == float(length_penalty))
 
 
-class _Search(str):
-    """``DecodeSettings.search`` of a call with ``length_penalty != 0``: the same string, with the penalty riding on it -- the record's
-    field list is fixed, and ``dataclasses.replace`` rebuilds a record from its field values alone.  So ``replace(s, search="beam")``
-    (a plain string) is the record WITHOUT the penalty, and the penalty is only ever put here by ``from_kw``, which reads the
-    ``length_penalty`` keyword and takes ``search`` as the plain string it spells.  Copies and pickles like the pair it is.
-    ``early_stopping`` (``None``, ``True`` or ``False``) rides the same way, one more attribute; so do ``num_beam_groups`` and
-    ``diversity_penalty`` (``check_beam_groups``; 1 and 0.0: off), and ``sequence_bias`` (``check_sequence_bias``; ``None``: off) --
-    the one of them that also rides on ``"sample"``."""
-    length_penalty = 0.0
-    early_stopping = None
-    num_beam_groups = 1
-    diversity_penalty = 0.0
-    sequence_bias = None
-
-    def __new__(cls, search, length_penalty=0.0, early_stopping=None, num_beam_groups=1, diversity_penalty=0.0, sequence_bias=None):
-        self = str.__new__(cls, search)
-        self.length_penalty = length_penalty
-        self.early_stopping = early_stopping
-        self.num_beam_groups = num_beam_groups
-        self.diversity_penalty = diversity_penalty
-        self.sequence_bias = sequence_bias
-        return self
-
-    def __getnewargs__(self):
-        return (str.__str__(self), self.length_penalty, self.early_stopping, self.num_beam_groups, self.diversity_penalty,
-                self.sequence_bias)
-
-    def __reduce__(self):
-        return (_Search, self.__getnewargs__())
-
-
 def check_repeat(no_repeat_ngram_size=0, repetition_penalty=1.0, max_len=None):
     """``no_repeat_ngram_size`` is an ``int >= 0`` (0: off; a ``bool`` is a misplaced flag, a float a ``TypeError``) and
     ``repetition_penalty`` a finite real number ``> 0`` (1.0: off; no ``bool``): checked where ``check_top_p`` is, before anything
@@ -591,20 +560,10 @@ def compile_sequence_bias(sequence_bias, num_tokens=None, device="cuda"):
 
 @dataclasses.dataclass(frozen=True, eq=False)
 class DecodeSettings:
-    """The validated decode settings of one call -- ``return_beams``, ``return_attention``, ``top_p``, ``no_repeat_ngram_size``,
-    ``repetition_penalty``, ``min_len``, ``bad_words_ids`` -- as the ``check_*`` functions return them (``bad_words_ids``: ``None``, a
-    tuple of tuples, or a ``BadWords``), ``num_tokens``, the vocabulary the list was checked against, and ``search`` (``check_search``;
-    behind ``num_tokens`` and with a default, so the positional order of the others is what it was) and ``return_logprobs``
-    (``check_return_logprobs``; the last one, for the same reason -- the constructor's last parameter, kept by ``replace``, in the key;
-    an init-only field stored by ``__post_init__``, because ``dataclasses.fields`` is pinned to end at ``search``).
-    ``length_penalty`` (``check_length_penalty``; 0.0: off) is a plain attribute, not a field -- the field list above is fixed --: set by
-    ``from_kw``, carried by ``search`` (``_Search``) so that ``replace`` and ``compiled`` keep it, and in the key; ``early_stopping``
-    (``check_early_stopping``; ``None``: off) travels the same way, in the key in front of ``length_penalty``; ``num_beam_groups`` /
-    ``diversity_penalty`` (``check_beam_groups``; 1 / 0.0: off) too -- their pair is ONE more key element, in front of all the others
-    and only with more than one group, so the key of a record without groups is what it was; ``sequence_bias``
-    (``check_sequence_bias``; ``None``: off) the same -- carried by ``search`` under ``"sample"`` as well, compiled by ``compiled``, and
-    in the key only when set, as ``("sequence_bias", pairs)`` in front of everything else.  Built by
-    ``from_kw`` only.  Immutable; equal and hashed by the settings, the list by its ids whether compiled or not."""
+    """The validated decode settings of one call, one field each, as the ``check_*`` functions return them (``bad_words_ids``:
+    ``None``, a tuple of tuples or a ``BadWords``; ``sequence_bias``: ``None``, a tuple of pairs or a ``SequenceBias``), and
+    ``num_tokens``, the vocabulary the lists were checked against.  The defaults are the settings switched off.  Built by
+    ``from_kw`` / ``from_call``.  Immutable; equal and hashed by the settings, a list by its ids or pairs whether compiled or not."""
     return_beams: bool = False
     return_attention: bool = False
     top_p: float = 1.0
@@ -612,46 +571,70 @@ class DecodeSettings:
     repetition_penalty: float = 1.0
     min_len: int = 0
     bad_words_ids: object = None
-    num_tokens: object = None
+    num_tokens: object = dataclasses.field(default=None, compare=False)
     search: str = "sample"
-    return_logprobs: dataclasses.InitVar[bool] = False
+    return_logprobs: bool = False
+    length_penalty: float = 0.0
+    early_stopping: object = None
+    num_beam_groups: int = 1
+    diversity_penalty: float = 0.0
+    sequence_bias: object = None
 
-    def __post_init__(self, return_logprobs):
-        object.__setattr__(self, "return_logprobs", return_logprobs)
-        object.__setattr__(self, "length_penalty", getattr(self.search, "length_penalty", 0.0))
-        object.__setattr__(self, "early_stopping", getattr(self.search, "early_stopping", None))
-        object.__setattr__(self, "num_beam_groups", getattr(self.search, "num_beam_groups", 1))
-        object.__setattr__(self, "diversity_penalty", getattr(self.search, "diversity_penalty", 0.0))
-        object.__setattr__(self, "sequence_bias", getattr(self.search, "sequence_bias", None))
+    @classmethod
+    def names(cls):
+        """The keywords that are decode settings: every field but ``num_tokens``."""
+        return tuple(f.name for f in dataclasses.fields(cls) if f.compare)
 
     @classmethod
     def from_kw(cls, kw, max_len, num_tokens=None, model=None):
-        """Reads the settings out of the keyword dictionary ``kw`` (which keeps them) and checks them in this order -- ``search``, then
-        ``return_logprobs``, then ``length_penalty``, then ``early_stopping`` last --, so a call with two bad values raises for the
-        earlier one; ``num_beam_groups`` / ``diversity_penalty`` (``check_beam_groups``) behind them all; ``model``: see ``check_return_attention`` / ``check_return_logprobs``."""
+        """Reads the settings out of the keyword dictionary ``kw`` (which keeps them; ``beam_size`` is read for the groups) and checks
+        them in the order below, so a call with two bad values raises for the earlier one; ``model``: see ``check_return_attention``
+        / ``check_return_logprobs``."""
         return_beams = check_return_beams(kw.get("return_beams", False))
         return_attention = check_return_attention(kw.get("return_attention", False), model)
         top_p = check_top_p(kw.get("top_p", 1.0))
         ngram, penalty = check_repeat(kw.get("no_repeat_ngram_size", 0), kw.get("repetition_penalty", 1.0), max_len)
         min_len, bad_words = check_constraints(kw.get("min_len", 0), kw.get("bad_words_ids"), max_len, num_tokens)
-        search = str(check_search(kw.get("search", "sample"), top_p))      # (the plain string: a penalty comes from its keyword alone)
+        search = check_search(kw.get("search", "sample"), top_p)
         return_logprobs = check_return_logprobs(kw.get("return_logprobs", False), model)
         length_penalty = check_length_penalty(kw.get("length_penalty", 0.0), max_len, search)
         early_stopping = check_early_stopping(kw.get("early_stopping"), search, return_attention, return_logprobs)
         groups, diversity = check_beam_groups(kw.get("num_beam_groups", 1), kw.get("diversity_penalty", 0.0), search, kw.get("beam_size"),
                                               early_stopping)
-        bias = check_sequence_bias(kw.get("sequence_bias"), num_tokens, model)     # (the newest control: checked last)
-        if length_penalty != 0.0 or early_stopping is not None or groups > 1 or bias is not None:
-            search = _Search(search, length_penalty, early_stopping, groups, diversity, bias)
-        return cls(return_beams, return_attention, top_p, ngram, penalty, min_len, bad_words, num_tokens, search, return_logprobs)
+        bias = check_sequence_bias(kw.get("sequence_bias"), num_tokens, model)
+        return cls(return_beams, return_attention, top_p, ngram, penalty, min_len, bad_words, num_tokens, str(search), return_logprobs,
+                   length_penalty, early_stopping, groups, diversity, bias)
+
+    @classmethod
+    def from_call(cls, kw, beam_size, max_len, decoder):
+        """``from_kw`` for a decoder's ``generate_batch(..., **kw)``: ``kw`` holds settings only -- any other name is the ``TypeError`` of
+        an unexpected keyword argument, and so is ``return_attention`` for a decoder kind without attention maps (no ``_cross``)."""
+        for name in kw:
+            if name not in cls.names() or (name == "return_attention" and not hasattr(decoder, "_cross")):
+                raise TypeError(f"generate_batch() got an unexpected keyword argument {name!r}")
+        return cls.from_kw(dict(kw, beam_size=beam_size), max_len, decoder.num_tokens, decoder)
+
+    def call_kw(self, kw):
+        """``kw`` as the call that means the same spells it with the fewest keywords: every setting read by ``from_kw`` that is off --
+        ``return_attention`` / ``return_logprobs`` ``False``, ``length_penalty`` 0.0, ``early_stopping`` ``None``, one beam group,
+        ``sequence_bias`` ``None`` or empty, ``search`` ``"sample"`` -- is removed, and ``length_penalty``, ``early_stopping`` and the
+        group pair are the checked values.  One call, one spelling: one graph-cache key.  Returns ``kw``."""
+        for name in ("return_attention", "return_logprobs", "length_penalty", "early_stopping", "sequence_bias"):
+            if getattr(self, name) == getattr(type(self), name):
+                kw.pop(name, None)
+            elif name in ("length_penalty", "early_stopping"):
+                kw[name] = getattr(self, name)
+        if self.search == "sample":
+            kw.pop("search", None)
+        kw.pop("num_beam_groups", None)
+        kw.pop("diversity_penalty", None)
+        if self.num_beam_groups > 1:
+            kw["num_beam_groups"], kw["diversity_penalty"] = self.num_beam_groups, self.diversity_penalty
+        return kw
 
     def _key(self):
-        bw, sb = self.bad_words_ids, self.sequence_bias
-        groups = ((self.num_beam_groups, self.diversity_penalty),) if self.num_beam_groups > 1 else ()
-        if sb is not None:                # one more element at the very front, only when set: ("sequence_bias", pairs)
-            groups = (("sequence_bias", sb.pairs if isinstance(sb, SequenceBias) else sb),) + groups
-        return groups + (self.return_beams, self.return_attention, self.top_p, self.no_repeat_ngram_size, self.repetition_penalty, self.min_len,
-                bw.ids if isinstance(bw, BadWords) else bw, self.early_stopping, self.length_penalty, self.return_logprobs, self.search)
+        vals = (getattr(self, name) for name in self.names())
+        return tuple(v.ids if isinstance(v, BadWords) else v.pairs if isinstance(v, SequenceBias) else v for v in vals)
 
     def __eq__(self, other):
         return isinstance(other, DecodeSettings) and self._key() == other._key()
@@ -660,12 +643,10 @@ class DecodeSettings:
         return hash(self._key())
 
     def compiled(self, device):
-        """The record with its phrase list uploaded to ``device`` (``compile_bad_words``: once per list, not inside a capture)."""
-        # (``length_penalty`` rides on ``search`` and so stays; its table is uploaded by ``compile_length_weights``, per session length)
-        search = self.search
-        if self.sequence_bias is not None:                 # the bias list rides on ``search`` too: the same string with the compiled list
-            search = _Search(*search.__getnewargs__()[:-1], compile_sequence_bias(self.sequence_bias, self.num_tokens, device))
-        return dataclasses.replace(self, bad_words_ids=compile_bad_words(self.bad_words_ids, self.num_tokens, device), search=search)
+        """The record with its two lists uploaded to ``device`` (``compile_bad_words`` / ``compile_sequence_bias``: once per list, not
+        inside a capture).  The ``length_penalty`` table is per session length: ``compile_length_weights``."""
+        return dataclasses.replace(self, bad_words_ids=compile_bad_words(self.bad_words_ids, self.num_tokens, device),
+                                   sequence_bias=compile_sequence_bias(self.sequence_bias, self.num_tokens, device))
 
     def new_helper(self, **engine_args):
         """The ``BeamSearchHelper`` of one session with every setting applied; ``engine_args``: the constructor's other arguments."""
@@ -1003,36 +984,38 @@ class BeamSearchHelper:
 
     def set_length_penalty(self, length_penalty=0.0):
         """``length_penalty`` of this session (see the class docstring), validated by ``check_length_penalty`` against the helper's
-        ``max_len`` and ``search`` (so behind ``set_search``).  Non-zero: the weight table ``len_w`` fp32 ``[max_len + 1]``
-        (``compile_length_weights``: one upload per value and length, so not inside a hipGraph capture unless it is cached) and the
-        zeroed per-row state ``keys`` fp32 ``[rows]``.  Zero, the default: nothing is allocated and no launch changes.  A method like
-        ``set_search``: the constructor's parameter list stays as it is.  Returns the helper."""
+        ``max_len`` and ``search`` (so behind ``set_search``).  Non-zero: the weight table ``len_w`` fp32 ``[max_len + 1]`` and the
+        zeroed per-row state ``keys`` fp32 ``[rows]`` (``_set_keys``).  Zero, the default: nothing is allocated and no launch changes.
+        Returns the helper."""
         self.length_penalty = check_length_penalty(length_penalty, self.max_len, self.search)
-        self.len_w = self.keys = None
-        if self.length_penalty != 0.0:
+        self.len_w = self.keys = None     # (another penalty: another table)
+        return self._set_keys()
+
+    def _set_keys(self):
+        """``len_w`` / ``keys`` for the three settings whose selects rank by key: with a length penalty, a pool or groups on, the weight
+        table of the penalty -- of ones at 0.0: ``x * 1.0f`` is ``x``, so one kernel serves both -- and the zeroed per-row keys, made
+        where there are none (``compile_length_weights``: one upload per value and length, so not inside a hipGraph capture unless it
+        is cached); with all three off, neither.  Returns the helper."""
+        if self.length_penalty == 0.0 and self.early_stopping is None and self.num_beam_groups == 1:
+            self.len_w = self.keys = None
+        elif self.len_w is None:
             self.len_w = compile_length_weights(self.length_penalty, self.max_len, self.device)
             self.keys = torch.zeros((self.n_img * self.beam_size,), dtype=torch.float32, device=self.device)
         return self
 
     def set_early_stopping(self, early_stopping=None):
         """``early_stopping`` of this session (see the class docstring), validated by ``check_early_stopping`` against the helper's
-        ``search`` and ``logprobs`` (so behind ``set_search``, ``set_logprobs`` and ``set_length_penalty``: the last of the chain).
-        ``True`` / ``False``: the per-image pool in ONE zeroed arena -- ``pool_tokens`` int32 ``[n_img, beam, max_len]``, ``pool_keys``
-        (filled with ``-inf``) and ``pool_vals`` fp32 ``[n_img, beam]``, ``pool_len`` int32 ``[n_img, beam]``, ``pool_n`` int32
-        ``[n_img]`` --, and, where ``set_length_penalty`` left none, the per-row ``keys`` and the weight table of ones
-        (``compile_length_weights(0.0, max_len)``: ``x * 1.0f`` is ``x``, so the one kernel serves both; an upload, so not inside a
-        hipGraph capture unless it is cached).  ``None``, the default: nothing is allocated and no launch changes.  Returns the
+        ``search`` and ``logprobs`` (so behind ``set_search``, ``set_logprobs`` and ``set_length_penalty``).  ``True`` / ``False``: the
+        per-image pool in ONE zeroed arena -- ``pool_tokens`` int32 ``[n_img, beam, max_len]``, ``pool_keys`` (filled with ``-inf``)
+        and ``pool_vals`` fp32 ``[n_img, beam]``, ``pool_len`` int32 ``[n_img, beam]``, ``pool_n`` int32 ``[n_img]`` --, and the keys
+        and their weight table (``_set_keys``).  ``None``, the default: nothing is allocated and no launch changes.  Returns the
         helper."""
         self.early_stopping = check_early_stopping(early_stopping, self.search, False, self.logprobs)
         self.pool_tokens = self.pool_keys = self.pool_vals = self.pool_len = self.pool_n = None
+        self._set_keys()
         if self.early_stopping is None:
-            if self.length_penalty == 0.0:
-                self.len_w = self.keys = None
             return self
         n, b, m = self.n_img, self.beam_size, self.max_len
-        if self.len_w is None:
-            self.len_w = compile_length_weights(self.length_penalty, m, self.device)
-            self.keys = torch.zeros((n * b,), dtype=torch.float32, device=self.device)
         arena = torch.zeros((n * b * m + 3 * n * b + n,), dtype=torch.int32, device=self.device)
         self.pool_tokens = arena[:n * b * m].view(n, b, m)
         o = n * b * m
@@ -1045,21 +1028,12 @@ class BeamSearchHelper:
 
     def set_beam_groups(self, num_beam_groups=1, diversity_penalty=0.0):
         """``num_beam_groups`` / ``diversity_penalty`` of this session (see the class docstring), validated by ``check_beam_groups``
-        against the helper's ``search``, ``beam_size`` and ``early_stopping`` (so the last of the chain, behind
-        ``set_early_stopping``).  More than one group: where ``set_length_penalty`` left none, the per-row ``keys`` and the weight
-        table of ones (``compile_length_weights(0.0, max_len)``, as ``set_early_stopping`` takes it: an upload, so not inside a
-        hipGraph capture unless it is cached).  One group, the default: nothing is allocated and no launch changes.  Returns the
-        helper."""
-        had = self.num_beam_groups > 1
+        against the helper's ``search``, ``beam_size`` and ``early_stopping`` (so behind ``set_early_stopping``).  More than one group:
+        the keys and their weight table (``_set_keys``).  One group, the default: nothing is allocated and no launch changes.
+        Returns the helper."""
         self.num_beam_groups, self.diversity_penalty = check_beam_groups(num_beam_groups, diversity_penalty, self.search, self.beam_size,
                                                                          self.early_stopping)
-        if self.num_beam_groups > 1:
-            if self.len_w is None:
-                self.len_w = compile_length_weights(self.length_penalty, self.max_len, self.device)
-                self.keys = torch.zeros((self.n_img * self.beam_size,), dtype=torch.float32, device=self.device)
-        elif had and self.length_penalty == 0.0 and self.early_stopping is None:
-            self.len_w = self.keys = None
-        return self
+        return self._set_keys()
 
     def set_sequence_bias(self, sequence_bias=None):
         """``sequence_bias`` of this session (see the class docstring), validated by ``check_sequence_bias``; a mapping or a list of
@@ -1255,17 +1229,20 @@ class BeamSearchHelper:
         else:
             noise = self._noise("final", 0, (self.n_img, self.beam_size))
         logprobs = None
+        n, b, dev = self.n_img, self.beam_size, self.device
+
+        def beam_outputs():               # what a launch that keeps every beam writes: tokens, four int32 pieces of one buffer, scores
+            out = torch.empty((n, b, self.max_len), dtype=torch.int32, device=dev)
+            ints = torch.empty((2 * n * b + 2 * n,), dtype=torch.int32, device=dev)
+            return (out, ints[:n * b].view(n, b), ints[n * b:2 * n * b].view(n, b), ints[2 * n * b:2 * n * b + n], ints[2 * n * b + n:],
+                    torch.empty((n, b), dtype=torch.float32, device=dev))
         if self.early_stopping is not None:
             # ``early_stopping``: ONE launch of ``dh_beam_finalize_pool``, never the ``beams`` launch -- the pool's entries and, for an
             # image that is not done, its live slots, the best ``beam_size`` by key.  Every hypothesis knows its own length (``<eos>``
             # included), so ``len_bias_done`` -- the convention that cuts a finished Transformer image's last ``<eos>`` -- is NOT applied.
             if attn_w is not None:
                 raise NotImplementedError("early_stopping with return_attention: a hypothesis in the pool has no live engine row to gather from")
-            n, b, dev = self.n_img, self.beam_size, self.device
-            out = torch.empty((n, b, self.max_len), dtype=torch.int32, device=dev)
-            ints = torch.empty((2 * n * b + 2 * n,), dtype=torch.int32, device=dev)
-            o_len, o_idx, o_drawn, o_row = ints[:n * b].view(n, b), ints[n * b:2 * n * b].view(n, b), ints[2 * n * b:2 * n * b + n], ints[2 * n * b + n:]
-            o_score = torch.empty((n, b), dtype=torch.float32, device=dev)
+            out, o_len, o_idx, o_drawn, o_row, o_score = beam_outputs()
             hip.beam_finalize_pool(self.tokens, self.keys, self._ended, self.done, self.pool_tokens, self.pool_keys, self.pool_len,
                                    self.pool_n, out, o_len, o_score, o_idx, o_drawn, o_row, n, b, full_len, pad_index)
             attention = None
@@ -1273,11 +1250,7 @@ class BeamSearchHelper:
             if not beams:
                 captions = (captions.tokens[:, 0], captions.row_lengths)
         elif beams or attn_w is not None or best or self.logprobs:
-            n, b, dev = self.n_img, self.beam_size, self.device
-            out = torch.empty((n, b, self.max_len), dtype=torch.int32, device=dev)
-            ints = torch.empty((2 * n * b + 2 * n,), dtype=torch.int32, device=dev)
-            o_len, o_idx, o_drawn, o_row = ints[:n * b].view(n, b), ints[n * b:2 * n * b].view(n, b), ints[2 * n * b:2 * n * b + n], ints[2 * n * b + n:]
-            o_score = torch.empty((n, b), dtype=torch.float32, device=dev)
+            out, o_len, o_idx, o_drawn, o_row, o_score = beam_outputs()
             hip.beam_finalize_beams(self.tokens, self.vals if self.keys is None else self.keys, self.done, self.end_step, out, o_len, o_score, o_idx, o_drawn, o_row, n, b,
                                     len_bias_done, full_len, pad_index, self.eos_index, pos, self.first_pos,
                                     self.temperature, noise, self.seed, self.img0, seed_ptr=self.seed_tensor)
@@ -1512,6 +1485,24 @@ def prompt_session_inputs(caption, caption_lengths, max_len, num_tokens, device,
     pw = max(0, min(caption.shape[1], max_len - 2))
     first_pos = lens.to(device=device, dtype=torch.int32).contiguous()
     return caption[:, :pw].to(device), first_pos, host
+
+
+def session_inputs(settings, caption, caption_lengths, max_len, num_embeddings, device, seed, rng, noise_source, defer_check):
+    """What both decoders' sessions settle before their first launch: ``(prompts, rng, noise_source, rng_seed, seed, rng_state0)``.
+    ``search="beam"`` draws nothing, so no generator is read and no noise source is asked; ``prompts``: ``prompt_session_inputs``' triple
+    or ``None`` for a dense call, whose ``caption`` ids are range-checked here; ``rng_seed``: the caller's seed, which
+    ``rng="torch"`` replays generators from (``TorchRngNoise``), while ``seed`` is the Philox key (``resolve_seed``); ``rng_state0``:
+    the default generator's state under ``rng="torch"`` with no seed, snapshotted once per call so that a repeated session
+    (``BeamOverflow`` retry) replays the same draws."""
+    if settings.search == "beam":
+        rng, noise_source, seed = None, None, 0
+    prompts = prompt_session_inputs(caption, caption_lengths, max_len, num_embeddings, device, rng, noise_source, no_host_read=defer_check)
+    if prompts is None:
+        check_ids(caption, num_embeddings)
+    rng_seed = seed
+    seed = 0 if rng == "torch" else resolve_seed(seed, noise_source)
+    rng_state0 = torch.get_rng_state() if (rng == "torch" and rng_seed is None) else None
+    return prompts, rng, noise_source, rng_seed, seed, rng_state0
 
 
 def check_lengths(lengths, steps):

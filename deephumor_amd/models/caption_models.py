@@ -103,19 +103,7 @@ class _CaptioningBase(nn.Module):
         the options it cannot be combined with); ``defer_check`` callers (graph capture, the pipeline) with device-resident lengths
         have done so themselves.  So are the decode settings in ``kw`` (``beam.DecodeSettings``), for every batch."""
         settings = DecodeSettings.from_kw(kw, max_len, self._hp["num_tokens"], self)
-        if settings.num_beam_groups == 1:         # (off, it is the call without the keywords)
-            kw.pop("num_beam_groups", None)
-            kw.pop("diversity_penalty", None)
-        if not settings.return_attention and not getattr(self.decoder, "_cross", False):
-            kw.pop("return_attention", None)      # (off, it is the call without the keyword -- also for the kinds whose decoders do not know it)
-        if not settings.return_logprobs:
-            kw.pop("return_logprobs", None)       # (off, it is the call without the keyword)
-        if settings.length_penalty == 0.0:
-            kw.pop("length_penalty", None)        # (the same)
-        if settings.early_stopping is None:
-            kw.pop("early_stopping", None)        # (the same)
-        if settings.sequence_bias is None:
-            kw.pop("sequence_bias", None)         # (the same: ``None`` or an empty mapping)
+        settings.call_kw(kw)                      # (a setting that is off is the call without the keyword -- also for the decoders that do not know it)
         if caption_lengths is None:
             return None
         if getattr(self.decoder, "pad_index", 0) == 1:
@@ -167,53 +155,21 @@ class _CaptioningBase(nn.Module):
         function of the lengths enters the graph cache key -- only the fact that lengths were passed, next to ``caption``'s shape:
         the captured chain treats every position ``0 .. min(P, max_len - 2)`` as mixed (all ``N * beam`` rows, the prompted beam
         step), so one graph serves every set of lengths of that shape and returns what eager returns for them."""
-        # every decode setting rides in ``kw`` and so is part of the cache key below: the graph of ``return_beams=True`` (it ends in
-        # dh_beam_finalize_beams), of ``return_attention=True`` (one dh_attn_cross_weights node per position and the gather behind the
-        # final draw), of ``return_logprobs=True`` (two nodes around every select and the back-pointer walk behind the final draw), of ``top_p < 1`` (nucleus row draws), of ``search="beam"`` (dh_beam_row_best / dh_beam_select_best nodes), of the
-        # repeat controls and of ``min_len`` / ``bad_words_ids`` (one
-        # dh_beam_history_logits / dh_beam_constrain_logits node per position that edits something; the position is a launch constant)
-        # each lives beside the plain one of the same shapes, and a replay returns clones of every field
+        # Every decode setting rides in ``kw`` and so is part of the cache key below: the graph of each one lives beside the plain one of
+        # the same shapes (other select / finalize nodes, or a node more per position), and a replay returns clones of every field.
+        # ``call_kw``: a setting that is off is the call without the keyword -- the plain graph, not a second one.  What a session
+        # would upload is uploaded HERE, in front of any capture (no host-to-device copy happens inside one): the two lists, whose
+        # hashable compiled forms replace the raw nestings in ``kw`` -- in the key, and so kept alive for as long as the graph is
+        # cached --, and the weight table the selects that rank by key read (of ones without a penalty), which the sessions then find
+        # in ``compile_length_weights``' cache and the graph's state holds (``_graph_state``)
         settings = DecodeSettings.from_kw(kw, kw.get("max_len", 25), self._hp["num_tokens"], self)
-        if not settings.return_attention:
-            kw.pop("return_attention", None)          # (False is the call without the keyword: the plain graph, not a second one)
-        if not settings.return_logprobs:
-            kw.pop("return_logprobs", None)           # (the same)
-        # ``length_penalty`` (dh_beam_select_best_norm nodes in place of dh_beam_select_best): 0.0 is the call without the keyword, any
-        # other value -- as the float the check returns -- is in the key below, and its weight table is uploaded HERE, in front of any
-        # capture (the sessions inside find it in ``compile_length_weights``' cache).  The captured nodes hold the table's raw pointer:
-        # the graph's cached state keeps the tensor (``_graph_state``), the cache alone would free it at its next eviction
-        kw.pop("length_penalty", None)
-        if settings.length_penalty != 0.0:
-            kw["length_penalty"] = settings.length_penalty
+        settings.call_kw(kw)
+        compiled = settings.compiled(inputs[0].device)
+        for name in ("bad_words_ids", "sequence_bias"):
+            if name in kw:
+                kw[name] = getattr(compiled, name)
+        if settings.length_penalty != 0.0 or settings.early_stopping is not None or settings.num_beam_groups > 1:
             compile_length_weights(settings.length_penalty, kw.get("max_len", 25), inputs[0].device)
-        # ``early_stopping`` (dh_beam_select_pool nodes, and dh_beam_finalize_pool at the end): ``None`` is the call without the keyword,
-        # ``True`` / ``False`` are in the key below; the select reads a weight table whatever the penalty is -- of ones at 0.0 --, which
-        # is uploaded here and held by the graph's state like any other
-        kw.pop("early_stopping", None)
-        if settings.early_stopping is not None:
-            kw["early_stopping"] = settings.early_stopping
-            compile_length_weights(settings.length_penalty, kw.get("max_len", 25), inputs[0].device)
-        # ``num_beam_groups`` / ``diversity_penalty`` (dh_beam_select_groups nodes): 1 is the call without the keywords; more groups --
-        # as the values the check returns -- are in the key below, so two group counts never share a graph; the select reads a weight
-        # table here too (of ones at 0.0), uploaded in front of the capture and held by the graph's state
-        kw.pop("num_beam_groups", None)
-        kw.pop("diversity_penalty", None)
-        if settings.num_beam_groups > 1:
-            kw["num_beam_groups"], kw["diversity_penalty"] = settings.num_beam_groups, settings.diversity_penalty
-            compile_length_weights(settings.length_penalty, kw.get("max_len", 25), inputs[0].device)
-        # The list is compiled HERE, in front of any capture -- no host-to-device copy happens inside one -- and the ``BadWords``
-        # replaces the raw nesting in ``kw``: it is hashable, so it is in the key below, and the captured closure keeps its two
-        # tensors alive
-        if "bad_words_ids" in kw:
-            kw["bad_words_ids"] = settings.compiled(inputs[0].device).bad_words_ids
-        # ``sequence_bias`` (one dh_beam_bias_logits node per position): the same -- ``None`` / an empty mapping is the call without the
-        # keyword, a list is compiled in front of the capture and its hashable ``SequenceBias`` is in the key below, which keeps the
-        # four tensors the captured nodes point at alive for as long as the graph is cached
-        kw.pop("sequence_bias", None)
-        if settings.sequence_bias is not None:
-            kw["sequence_bias"] = settings.compiled(inputs[0].device).sequence_bias
-        if settings.search == "sample":
-            kw.pop("search", None)                    # (the default is the call without the keyword: the plain graph, not a second one)
         if kw.get("rng") == "torch" and settings.search != "beam":      # host-generated noise (parity mode): nothing to replay
             return self.generate_batch(*inputs, caption=caption, seed=seed, caption_lengths=caption_lengths, **kw)
         if caption_lengths is not None:

@@ -15,25 +15,8 @@ from torch import nn
 
 from .. import hip
 from ._f32x_guard import f32x_guarded
-from .beam import BeamCaptions, DecodeSession, DecodeSettings, call_logits_hook, check_ids, check_lengths, classifier_must_be_finite, decode_with_overflow_retry, make_noise_source, prompt_session_inputs, resolve_seed, run_interleaved
+from .beam import BeamCaptions, DecodeSession, DecodeSettings, call_logits_hook, check_ids, check_lengths, classifier_must_be_finite, decode_with_overflow_retry, make_noise_source, run_interleaved, session_inputs
 from .encoders import _Planned
-
-
-def _later_keywords(*names):
-    """Decorator of ``LSTMDecoder.generate_batch``: the method keeps the parameter list it had (positional order, keyword-only tail
-    ending at ``repetition_penalty``), and the keyword-only controls added since -- ``names`` -- are accepted by name here and go to
-    ``self._decode_session``, the implementation, together with everything else.  A call without them is the method's own body."""
-    import functools
-
-    def deco(fn):
-        @functools.wraps(fn)
-        def generate_batch(self, *args, **kw):
-            later = {k: kw.pop(k) for k in names if k in kw}
-            if not later:
-                return fn(self, *args, **kw)
-            return self._decode_session(*args, **kw, **later)
-        return generate_batch
-    return deco
 
 
 class LSTMDecoder(_Planned, nn.Module):
@@ -190,175 +173,59 @@ class LSTMDecoder(_Planned, nn.Module):
         hs.mul_(valid[..., None])          # pad_packed_sequence zero rows (mask, not arithmetic on valid rows)
         return hs, bs, steps_out
 
-    @_later_keywords("min_len", "bad_words_ids", "search", "return_logprobs", "num_beam_groups", "diversity_penalty", "length_penalty",
-                     "early_stopping", "sequence_bias")
+    @f32x_guarded
     def generate_batch(self, image_emb, caption=None, max_len=25, temperature=1.0, beam_size=10, top_k=50,
                        eos_index=3, seed=None, img0=0, noise_source=None, logits_hook=None, streams=1, seed_tensor=None,
                        defer_check=False, early_stop_every=0, exact=False, rng=None, *, caption_lengths=None, return_beams=False, top_p=1.0,
-                       no_repeat_ngram_size=0, repetition_penalty=1.0):
+                       no_repeat_ngram_size=0, repetition_penalty=1.0, **kw):
         """Batched beam-search sampling for ``image_emb [N, 1, E]`` or ``[N, E]``.
 
-        Returns ``(tokens int64 [N, max_len] zero-padded, lengths int64 [N])``; row ``i`` equals
-        what the reference's ``generate`` returns for image ``i`` under the same random draws
-        (rnn_models.py:48-143, incl. the hidden-state indexing at :135-137).  ``streams`` > 1 decodes
-        that many image sub-batches concurrently on separate HIP streams (same captions).
-        ``early_stop_every=k`` (> 0) checks every k steps whether every image has finished (the reference's
-        ``all_ended()`` break, rnn_models.py:131) and stops decoding then -- one host sync per check, same captions.
-        ``exact=True`` draws every row through the general sampler from the start (what a batch is repeated with automatically
-        when flat logits overflow the pre-filtered samplers, see ``BeamOverflow``).
-        ``rng="torch"``: the draws consume torch CPU generators in the reference's order (``beam.TorchRngNoise``): on the fp32 path
-        ``torch.manual_seed(s); decoder.generate(emb, rng="torch")`` returns the reference's sampled caption; in a batch image ``i``
-        replays ``torch.manual_seed(seed + img0 + i)``.
-        ``caption_lengths`` (int64 / int32 ``[N]``, host or device; keyword only): a prompt of its own length per image -- row ``i``
-        is teacher-forced with ``caption[i, :caption_lengths[i]]`` (0: no prompt; the rest of the row is ignored) and equals row 0 of
-        the dense call ``generate_batch(image_emb[i:i+1], caption=caption[i:i+1, :caption_lengths[i]], img0=img0 + i, ...)``.
-        All images walk the positions together; the beam step takes every image's phase from the lengths
-        (``BeamSearchHelper.step_prompted``).  Philox noise only (``beam.prompt_session_inputs``).
-        ``return_beams=True`` (keyword only): every beam the search ends with instead of the one drawn among them -- a
-        ``beam.BeamCaptions`` whose ``best()`` is the plain call's pair, bit for bit (``dh_beam_finalize_beams`` in place of
-        ``dh_beam_finalize``; nothing else changes).
-        ``top_p`` (keyword only, a number in ``(0, 1]``): nucleus filtering beside ``top_k`` -- every row draw runs over the smallest
-        set of the row's top-k survivors, most probable first, whose probabilities reach ``top_p`` (never fewer than ``beam_size``;
-        the exact rule: ``BeamSearchHelper``).  ``1.0``, the default, is the call without the keyword: same launches, same bits.
-        Flat logits (more than 1,024 survivors) raise ``BeamOverflow`` with ``top_p < 1``.
-        ``no_repeat_ngram_size=n`` (keyword only, int ``>= 0``): no row draws a token that would complete an n-gram its own history
-        (prompt included) already holds; ``repetition_penalty`` (keyword only, finite ``> 0``): every distinct token of the row's
-        history has its logit ``x`` replaced by ``x * penalty`` if ``x < 0`` else ``x / penalty`` (CTRL).  Penalty first, ban second,
-        one launch of ``dh_beam_history_logits`` in front of every row draw (``BeamSearchHelper``); ``logits_hook`` still sees the
-        model's raw logits.  ``0`` / ``1.0``, the defaults, are the call without the keywords: same launches, same bits.  ``max_len``
-        above ``hip.MAX_HISTORY`` with a control on is a ``ValueError``.
-        ``min_len`` (keyword only, int, ``0 <= min_len < max_len``, absolute like ``max_len``: prompt tokens count): no row draws
-        ``<eos>`` at a token position ``s < min_len``.  ``bad_words_ids`` (keyword only; ``None``, a sequence of non-empty sequences of
-        token ids, or a ``beam.BadWords`` from ``beam.compile_bad_words``; one list for the batch): no row draws the last id of a
-        phrase whose other ids end its own history (prompt included, per beam row) -- a single id is banned at every position.  At
-        most ``hip.MAX_BAD_WORDS`` phrases of ``hip.MAX_BAD_LEN`` ids.  One launch of ``dh_beam_constrain_logits`` behind the history
-        edits and in front of the row draw, only at positions where there is something to ban; ``logits_hook`` still sees the raw
-        logits.  ``0`` / ``None``, the defaults, are the call without the keywords: same launches, same bits.  All validation:
-        ``beam.check_constraints``.
-        ``search`` (keyword only, ``"sample"`` or ``"beam"``; ``beam.check_search``): ``"sample"``, the default, is the call without
-        the keyword -- same launches, same bits.  ``"beam"`` is the deterministic search: every row keeps its ``beam_size`` most
-        likely tokens (after the history edits and the bans; never ``<unk>``), every image the ``beam_size`` candidates with the
-        largest cumulative log-probability, and the caption returned is the beam with the largest one -- the same on every call,
-        whatever ``seed``, ``rng`` and ``noise_source`` are (accepted, unused: no noise is generated or consumed).  ``top_k`` keeps
-        its assertion ``beam_size <= top_k`` and filters nothing; ``top_p < 1`` is a ``ValueError``.  With ``return_beams=True`` the
-        ``scores`` are cumulative model log-probabilities and ``drawn`` is 0.  Two launches per position (``dh_beam_row_best``,
-        ``dh_beam_select_best``) in place of the sampled pair (``BeamSearchHelper``).
-        ``length_penalty`` (keyword only, with ``search="beam"``; a finite number, ``abs <= 8``; ``beam.check_length_penalty``): every
-        select ranks its candidates by ``key = fp32(score * w[L])`` in place of the score -- ``L`` the columns the search has written
-        to the beam, from the image's first generated column through its own first ``<eos>``, ``w[L] = float32(float64(L) **
-        -length_penalty)`` from a host-made table --, inside the pruning; an ended beam keeps the key it was kept with.  Scores are
-        ``<= 0``: ``> 0`` favours longer captions, ``< 0`` shorter ones.  ``BeamCaptions.scores`` are the keys, slot 0 the largest.
-        ``dh_beam_select_best_norm`` in place of ``dh_beam_select_best``; ``0.0``, the default, is the call without the keyword: same
-        launches, same bits.  Non-zero with ``search="sample"``: ``ValueError``.
-        ``return_logprobs=True`` (keyword only, a plain bool; ``beam.check_return_logprobs``): one more result, last in the tuple, an
-        fp32 device tensor with the model's log-probability of every token the search wrote -- ``(tokens, lengths, logprobs [N, T])``,
-        or ``(BeamCaptions, logprobs [N, B, T])`` with ``return_beams=True`` in ``BeamCaptions`` slot order.  ``logprobs[i, (slot,) c]``
-        is ``log_softmax(x / temperature)[token at column c]`` over every real column (``<unk>`` included), ``x`` the fp32 logits row
-        that token was taken from as it stands in front of the row step: behind ``logits_hook``, the history edits and the bans, in
-        front of the top-k / nucleus / ``<unk>`` filtering -- the definition ``search="beam"`` uses for ``scores``, whose bits these are
-        there (their left-to-right fp32 sum over a live beam's own columns IS its score).  Filled from the image's first generated
-        column up to the beam's own length (``BeamCaptions.lengths``; the drawn beam's for the plain call); every other element --
-        prefix and prompt columns, anything behind the beam's own ``<eos>`` -- is exactly 0.  A dead beam (score ``-inf``) has
-        unspecified values, never NaN.  It changes no token; ``False``, the default, is the call without the keyword: same launches,
-        same bits.  On: three launches of their own (``dh_beam_pick_logprobs`` in front of and ``dh_beam_record_logprobs`` behind every
-        select, ``dh_beam_gather_logprobs`` behind the final draw; ``BeamSearchHelper``).
-        ``early_stopping`` (keyword only, with ``search="beam"``; ``None``, ``True`` or ``False``; ``beam.check_early_stopping``): the
-        finished-hypothesis pool of the usual beam search.  A candidate whose token is ``<eos>`` takes no beam slot any more: among the
-        step's first ``beam_size`` ranks it goes to the image's pool -- sorted by key, ``beam_size`` entries, entered when full only with
-        a key strictly above its worst -- and the ``beam_size`` best other candidates stay as live beams, so the beam keeps its width.
-        ``True``: an image is done as soon as its pool is full; ``False``: when it is full and no live beam kept at this step has a key
-        above the pool's worst (with ``length_penalty <= 0`` keys only fall as a beam grows and this loses nothing; with
-        ``length_penalty > 0`` it is a heuristic).  ``early_stop_every`` then has something to find.  At the end the live beams of an
-        image that is not done are offered to the pool the same way; the result's slots are the pool's: ``lengths`` each hypothesis'
-        own, its ``<eos>`` included -- the convention that cuts a finished Transformer image's last ``<eos>`` column is NOT applied
-        here --, ``scores`` the keys, ``beam_index`` the live slot or ``-1`` for an entry that came from the pool; the plain pair is
-        slot 0.  ``dh_beam_select_pool`` in place of the select and ``dh_beam_finalize_pool`` in place of the final launch; ``None``,
-        the default, is the call without the keyword: same launches, same bits.  With ``search="sample"``: ``ValueError``; with
-        ``return_attention`` / ``return_logprobs``: ``NotImplementedError`` (a pooled hypothesis has no live engine row to gather from).
-        ``num_beam_groups`` / ``diversity_penalty`` (keyword only, with ``search="beam"``; an int ``G >= 1`` that divides ``beam_size``
-        and a number ``0 < lam <= 1e6``; ``beam.check_beam_groups``): diverse beam search.  The ``beam_size`` beams are ``G`` groups of
-        ``Bg = beam_size // G`` -- engine beams ``g * Bg .. g * Bg + Bg - 1`` are group ``g`` for the whole search -- and at every
-        position the groups choose one after the other: group ``g`` ranks the candidates of its own beams by ``key - lam * count``,
-        ``count`` the times the candidate's token was taken at this position by the groups before it (an ended beam is neither
-        penalised nor counted).  The penalty shapes the choice and is never stored: ``BeamCaptions.scores`` stay model
-        log-probabilities (length-normalised under ``length_penalty``), all ``beam_size`` beams come back in score order,
-        ``beam_index // Bg`` is a beam's group (``experiments.group_best`` picks each group's best) and the plain pair is slot 0.
-        ``dh_beam_select_groups`` in place of the select, one launch per position for all groups; ``1`` / ``0.0``, the defaults, are
-        the call without the keywords: same launches, same bits.  ``G > 1`` with ``search="sample"`` or without a penalty:
-        ``ValueError``; with ``early_stopping``: ``NotImplementedError`` (a pool per group is the follow-up).
-        ``sequence_bias`` (keyword only; ``None``, a mapping ``{tuple of token ids: bias}``, a sequence of ``(phrase, bias)`` pairs, or
-        a ``beam.SequenceBias`` from ``beam.compile_sequence_bias``; one list for the batch; ``beam.check_sequence_bias``): the soft
-        counterpart of ``bad_words_ids`` -- ``bias`` is added to the logit of a phrase's last id in every row whose own history
-        (prompt included, per beam row) ends with the phrase's other ids; a single id is biased at every position.  Positive values
-        steer captions towards a token, negative ones away from it without forbidding it; every bias is finite with ``abs(bias) <=
-        1e4``.  Pairs that meet on one column are added in list order, each its own fp32 add; ``-inf`` stays ``-inf`` (a banned
-        token stays banned).  One launch of ``dh_beam_bias_logits`` behind the history edits and in front of the bans; under
-        ``search="beam"`` the scores, and with ``return_logprobs`` the log-probabilities, are those of the biased rows;
-        ``logits_hook`` still sees the raw logits.  ``None`` or an empty mapping is the call without the keyword: same launches,
-        same bits.
-        ``min_len``, ``bad_words_ids``, ``search``, ``return_logprobs``, ``num_beam_groups``, ``diversity_penalty``, ``length_penalty``, ``early_stopping`` and ``sequence_bias`` are not in the parameter list above, which ends at
-        ``repetition_penalty`` as it did: they are taken by name (``_later_keywords``) and handed to ``_decode_session``, the
-        implementation, which spells every keyword out."""
-        return self._generate_batch(image_emb, caption, max_len, temperature, beam_size, top_k, eos_index, seed, img0, noise_source,
-                                    logits_hook, streams, seed_tensor, defer_check, early_stop_every, exact, rng,
-                                    caption_lengths=caption_lengths, return_beams=return_beams, top_p=top_p,
-                                    no_repeat_ngram_size=no_repeat_ngram_size, repetition_penalty=repetition_penalty)
+        Returns ``(tokens int64 [N, max_len] zero-padded, lengths int64 [N])``; row ``i`` equals what the reference's ``generate``
+        returns for image ``i`` under the same random draws (rnn_models.py:48-143, incl. the hidden-state indexing at :135-137).
 
-    @f32x_guarded
-    def _generate_batch(self, image_emb, caption=None, max_len=25, temperature=1.0, beam_size=10, top_k=50,
-                        eos_index=3, seed=None, img0=0, noise_source=None, logits_hook=None, streams=1, seed_tensor=None,
-                        defer_check=False, early_stop_every=0, exact=False, rng=None, *, caption_lengths=None, return_beams=False, top_p=1.0,
-                        no_repeat_ngram_size=0, repetition_penalty=1.0, min_len=0, bad_words_ids=None):
-        """``generate_batch`` with its keyword-only tail up to ``bad_words_ids`` written out: this parameter list is what it was, and
-        ``_decode_batch`` behind it takes the keywords added since."""
-        return self._decode_batch(image_emb, caption, max_len, temperature, beam_size, top_k, eos_index, seed, img0, noise_source,
-                                  logits_hook, streams, seed_tensor, defer_check, early_stop_every, exact, rng,
-                                  caption_lengths=caption_lengths, return_beams=return_beams, top_p=top_p,
-                                  no_repeat_ngram_size=no_repeat_ngram_size, repetition_penalty=repetition_penalty, min_len=min_len,
-                                  bad_words_ids=bad_words_ids)
+        The engine arguments.  ``streams`` > 1 decodes that many image sub-batches concurrently on separate HIP streams (same
+        captions).  ``early_stop_every=k`` (> 0) checks every k steps whether every image has finished (the reference's
+        ``all_ended()`` break, rnn_models.py:131) -- one host sync per check, same captions.  ``exact=True`` draws every row through
+        the general sampler from the start (what a batch is repeated with automatically when flat logits overflow the pre-filtered
+        samplers, see ``BeamOverflow``).  ``rng="torch"``: the draws consume torch CPU generators in the reference's order
+        (``beam.TorchRngNoise``) -- on the fp32 path ``torch.manual_seed(s); decoder.generate(emb, rng="torch")`` returns the
+        reference's sampled caption; in a batch image ``i`` replays ``torch.manual_seed(seed + img0 + i)``.  ``caption_lengths`` (int64
+        / int32 ``[N]``, host or device): a prompt of its own length per image -- row ``i`` is teacher-forced with ``caption[i,
+        :caption_lengths[i]]`` (0: none; the rest of the row is ignored) and equals row 0 of the dense call ``generate_batch(image_emb[i:i+1],
+        caption=caption[i:i+1, :caption_lengths[i]], img0=img0 + i, ...)``; Philox noise only (``beam.prompt_session_inputs``).
 
-    @f32x_guarded
-    def _decode_batch(self, image_emb, caption=None, max_len=25, temperature=1.0, beam_size=10, top_k=50,
-                      eos_index=3, seed=None, img0=0, noise_source=None, logits_hook=None, streams=1, seed_tensor=None,
-                      defer_check=False, early_stop_every=0, exact=False, rng=None, *, caption_lengths=None, return_beams=False, top_p=1.0,
-                      no_repeat_ngram_size=0, repetition_penalty=1.0, min_len=0, bad_words_ids=None, search="sample"):
-        """``generate_batch`` with its keyword-only tail up to ``search`` written out: this parameter list is what it was, and
-        ``_decode_session`` behind it takes the keywords added since."""
+        The decode settings, keyword only: the four named above and, in ``kw``, the rest of ``beam.DecodeSettings.names()`` -- any other
+        keyword is a ``TypeError``.  Each is validated by its ``beam.check_*`` function before anything runs, and each one's default is
+        the call without the keyword: same launches, same bits.  ``BeamSearchHelper`` has the full contract of every one:
+
+        ``return_beams=True``          every beam the search ends with, a ``beam.BeamCaptions`` whose ``best()`` is the plain pair;
+        ``top_p``                      nucleus filtering beside ``top_k`` (a number in ``(0, 1]``);
+        ``no_repeat_ngram_size`` / ``repetition_penalty``   no n-gram twice in a row's history / CTRL's penalty on its tokens;
+        ``min_len`` / ``bad_words_ids``  no ``<eos>`` before ``min_len`` / no last id of a listed phrase behind its other ids;
+        ``sequence_bias``              ``{phrase: bias}``, added to the logit of a phrase's last id behind its other ids;
+        ``search="beam"``              the deterministic search: the ``beam_size`` most likely continuations, no noise, scores that
+                                       are cumulative model log-probabilities;
+        ``length_penalty``             (``search="beam"``) candidates ranked by ``score * L ** -length_penalty``;
+        ``early_stopping``             (``search="beam"``; ``True`` / ``False``) finished hypotheses go to a pool of ``beam_size``;
+        ``num_beam_groups`` / ``diversity_penalty``   (``search="beam"``) diverse groups of beams;
+        ``return_logprobs=True``       one more result, last: the model log-probability of every token written, ``[N, T]`` or
+                                       ``[N, B, T]`` behind a ``BeamCaptions``."""
         return self._decode_session(image_emb, caption, max_len, temperature, beam_size, top_k, eos_index, seed, img0, noise_source,
-                                    logits_hook, streams, seed_tensor, defer_check, early_stop_every, exact, rng,
-                                    caption_lengths=caption_lengths, return_beams=return_beams, top_p=top_p,
-                                    no_repeat_ngram_size=no_repeat_ngram_size, repetition_penalty=repetition_penalty, min_len=min_len,
-                                    bad_words_ids=bad_words_ids, search=search)
+                                    logits_hook, streams, seed_tensor, defer_check, early_stop_every, exact, rng, caption_lengths,
+                                    return_beams=return_beams, top_p=top_p, no_repeat_ngram_size=no_repeat_ngram_size,
+                                    repetition_penalty=repetition_penalty, **kw)
 
-    @f32x_guarded
-    def _decode_session(self, image_emb, caption=None, max_len=25, temperature=1.0, beam_size=10, top_k=50,
-                        eos_index=3, seed=None, img0=0, noise_source=None, logits_hook=None, streams=1, seed_tensor=None,
-                        defer_check=False, early_stop_every=0, exact=False, rng=None, *, caption_lengths=None, return_beams=False, top_p=1.0,
-                        no_repeat_ngram_size=0, repetition_penalty=1.0, min_len=0, bad_words_ids=None, search="sample",
-                        return_logprobs=False, sequence_bias=None, num_beam_groups=1, diversity_penalty=0.0, length_penalty=0.0,
-                        early_stopping=None):
-        """The implementation of ``generate_batch``, every keyword spelled out."""
-        settings = DecodeSettings.from_kw(dict(return_beams=return_beams, top_p=top_p, no_repeat_ngram_size=no_repeat_ngram_size,
-                                               repetition_penalty=repetition_penalty, min_len=min_len, bad_words_ids=bad_words_ids,
-                                               search=search, return_logprobs=return_logprobs, length_penalty=length_penalty,
-                                               early_stopping=early_stopping, num_beam_groups=num_beam_groups,
-                                               diversity_penalty=diversity_penalty, beam_size=beam_size, sequence_bias=sequence_bias),
-                                          max_len, self.num_tokens)
-        if settings.search == "beam":     # nothing is drawn: no generator is read, no noise source is asked
-            rng, noise_source, seed = None, None, 0
+    def _decode_session(self, image_emb, caption, max_len, temperature, beam_size, top_k, eos_index, seed, img0, noise_source,
+                        logits_hook, streams, seed_tensor, defer_check, early_stop_every, exact, rng, caption_lengths, **kw):
+        """The implementation of ``generate_batch``: the engine arguments by name, the decode settings in ``kw``."""
+        settings = DecodeSettings.from_call(kw, beam_size, max_len, self)
+        return_beams = settings.return_beams
         self._check_mode()
         plan = self._get_plan()
         classifier_must_be_finite(plan)
-        settings = settings.compiled(image_emb.device)                 # the phrase list uploaded once (a BadWords: as it is)
-        prompts = prompt_session_inputs(caption, caption_lengths, max_len, self.embedding.num_embeddings, image_emb.device, rng,
-                                        noise_source, no_host_read=defer_check)
-        if prompts is None:
-            check_ids(caption, self.embedding.num_embeddings)
-        rng_seed = seed
-        seed = 0 if rng == "torch" else resolve_seed(seed, noise_source)
-        # rng="torch" with seed=None draws from torch's DEFAULT generator: its state is snapshotted once per call so that a repeated
-        # session (BeamOverflow retry) replays the same draws (beam.TorchRngNoise)
-        rng_state0 = torch.get_rng_state() if (rng == "torch" and rng_seed is None) else None
+        settings = settings.compiled(image_emb.device)                 # the two lists uploaded once (compiled ones: as they are)
+        prompts, rng, noise_source, rng_seed, seed, rng_state0 = session_inputs(
+            settings, caption, caption_lengths, max_len, self.embedding.num_embeddings, image_emb.device, seed, rng, noise_source, defer_check)
         image_emb = image_emb.reshape(image_emb.shape[0], -1).to(plan["dtype"]).contiguous()
 
         def new_helper(lo, hi, exact, **kw):
@@ -442,7 +309,7 @@ class LSTMDecoder(_Planned, nn.Module):
                  temperature=1.0, beam_size=10, top_k=50, eos_index=3, **kw):
         """Single-image API of the reference (rnn_models.py:48-49): ``image_emb [1, 1, E]`` ->
         1-D int64 token tensor; with ``return_beams=True`` the image's ``BeamCaptions`` (``N = 1``, nothing squeezed).  ``top_p``,
-        ``no_repeat_ngram_size``, ``repetition_penalty``, ``min_len``, ``bad_words_ids``, ``search`` (in ``kw``): see ``generate_batch``."""
+        ``no_repeat_ngram_size``, ``repetition_penalty`` and every other decode setting (in ``kw``): see ``generate_batch``."""
         res = self.generate_batch(image_emb, caption=caption, max_len=max_len, temperature=temperature,
                                   beam_size=beam_size, top_k=top_k, eos_index=eos_index, **kw)
         return self.single_output(res, caption, max_len, beam_size)

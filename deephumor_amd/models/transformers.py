@@ -21,7 +21,7 @@ from torch import nn
 
 from .. import hip
 from ._f32x_guard import f32x_guarded
-from .beam import BeamCaptions, DecodeSession, DecodeSettings, call_logits_hook, check_ids, classifier_must_be_finite, decode_with_overflow_retry, make_noise_source, prompt_session_inputs, resolve_seed, run_interleaved
+from .beam import BeamCaptions, DecodeSession, DecodeSettings, call_logits_hook, check_ids, classifier_must_be_finite, decode_with_overflow_retry, make_noise_source, run_interleaved, session_inputs
 from .encoders import _Planned
 
 
@@ -528,7 +528,7 @@ class _IncrementalDecoder(_Planned, nn.Module):
 
     @staticmethod
     def _one(res):
-        """``generate``'s result from ``_generate_batch``'s for one image: the caption, or the ``BeamCaptions`` (N = 1) as it is; with
+        """``generate``'s result from ``generate_batch``'s for one image: the caption, or the ``BeamCaptions`` (N = 1) as it is; with
         ``return_attention=True`` the pair ``(caption, attention [len, S])``, or ``(BeamCaptions, attention [1, B, T, S])`` as it is;
         with ``return_logprobs=True`` one more element in the same way, ``logprobs [len]`` (or ``[1, B, T]`` as it is)."""
         if isinstance(res, BeamCaptions) or isinstance(res[0], BeamCaptions):
@@ -539,49 +539,21 @@ class _IncrementalDecoder(_Planned, nn.Module):
             return (toks[0, :n].squeeze(), *(e[0, :n] for e in extra))
         return toks[0, :n].squeeze()
 
-    def _generate_batch(self, start_emb, enc_out, caption, max_len, temperature, beam_size, top_k, eos_index,
-                        seed=None, img0=0, noise_source=None, logits_hook=None, streams=1, seed_tensor=None,
-                        defer_check=False, early_stop_every=0, exact=False, rng=None, caption_lengths=None, return_beams=False, top_p=1.0,
-                        no_repeat_ngram_size=0, repetition_penalty=1.0, min_len=0, bad_words_ids=None, return_attention=False,
-                        search="sample"):
-        """``_decode_session`` with the keywords up to ``search``: this parameter list is what it was."""
-        return self._decode_session(start_emb, enc_out, caption, max_len, temperature, beam_size, top_k, eos_index, seed, img0, noise_source,
-                                    logits_hook, streams, seed_tensor, defer_check, early_stop_every, exact, rng, caption_lengths,
-                                    return_beams, top_p, no_repeat_ngram_size, repetition_penalty, min_len, bad_words_ids, return_attention,
-                                    search)
-
     def _decode_session(self, start_emb, enc_out, caption, max_len, temperature, beam_size, top_k, eos_index,
                         seed=None, img0=0, noise_source=None, logits_hook=None, streams=1, seed_tensor=None,
-                        defer_check=False, early_stop_every=0, exact=False, rng=None, caption_lengths=None, return_beams=False, top_p=1.0,
-                        no_repeat_ngram_size=0, repetition_penalty=1.0, min_len=0, bad_words_ids=None, return_attention=False,
-                        search="sample", return_logprobs=False, sequence_bias=None, num_beam_groups=1, diversity_penalty=0.0,
-                        length_penalty=0.0, early_stopping=None):
-        """The implementation of ``generate_batch`` / ``generate``, every keyword spelled out."""
-        settings = DecodeSettings.from_kw(dict(return_beams=return_beams, return_attention=return_attention, top_p=top_p,
-                                               no_repeat_ngram_size=no_repeat_ngram_size, repetition_penalty=repetition_penalty,
-                                               min_len=min_len, bad_words_ids=bad_words_ids, search=search,
-                                               return_logprobs=return_logprobs, length_penalty=length_penalty,
-                                               early_stopping=early_stopping, num_beam_groups=num_beam_groups,
-                                               diversity_penalty=diversity_penalty, beam_size=beam_size, sequence_bias=sequence_bias),
-                                          max_len, self.num_tokens, self)
-        if settings.search == "beam":     # nothing is drawn: no generator is read, no noise source is asked
-            rng, noise_source, seed = None, None, 0
+                        defer_check=False, early_stop_every=0, exact=False, rng=None, caption_lengths=None, **kw):
+        """The implementation of ``generate_batch`` / ``generate``: the engine arguments by name, the decode settings in ``kw``."""
+        settings = DecodeSettings.from_call(kw, beam_size, max_len, self)
+        return_beams, return_attention = settings.return_beams, settings.return_attention
         self._check_mode()
         plan = self._get_plan()
         classifier_must_be_finite(plan)
-        settings = settings.compiled(start_emb.device)                 # the phrase list uploaded once (a BadWords: as it is)
+        settings = settings.compiled(start_emb.device)                 # the two lists uploaded once (compiled ones: as they are)
         if caption_lengths is not None and self.pad_index == 1:
             raise NotImplementedError("caption_lengths with pad_index == 1: that decoder re-runs the whole sequence per token on the "
                                       "module path (_generate_reforward), which has no per-image prompt phase")
-        prompts = prompt_session_inputs(caption, caption_lengths, max_len, self.tok_embedding.num_embeddings, start_emb.device, rng,
-                                        noise_source, no_host_read=defer_check)
-        if prompts is None:
-            check_ids(caption, self.tok_embedding.num_embeddings)
-        rng_seed = seed                   # rng="torch": the draws replay torch CPU generators (beam.TorchRngNoise)
-        seed = 0 if rng == "torch" else resolve_seed(seed, noise_source)
-        # rng="torch" with seed=None draws from torch's DEFAULT generator: its state is snapshotted once per call so that a repeated
-        # session (BeamOverflow retry) replays the same draws (beam.TorchRngNoise)
-        rng_state0 = torch.get_rng_state() if (rng == "torch" and rng_seed is None) else None
+        prompts, rng, noise_source, rng_seed, seed, rng_state0 = session_inputs(
+            settings, caption, caption_lengths, max_len, self.tok_embedding.num_embeddings, start_emb.device, seed, rng, noise_source, defer_check)
         if max_len + 1 > self.pos_embedding.num_embeddings:
             raise IndexError("index out of range in self")    # reference: pos_embedding lookup, SURVEY.md section 5
         start_emb = start_emb.to(plan["dtype"]).contiguous()
@@ -669,7 +641,7 @@ class _IncrementalDecoder(_Planned, nn.Module):
             return helper.finalize(len_bias_done=0, full_len=max_len, pad_index=self.pad_index, defer_check=defer_check,
                                    beams=return_beams, pos=pos, attn_w=attn_w)
 
-        def run(exact):                   # (flat logits: see LSTMDecoder._generate_batch)
+        def run(exact):                   # (flat logits: see decode_with_overflow_retry)
             return run_interleaved(lambda lo, hi: session(lo, hi, exact), n_img, streams)
         return decode_with_overflow_retry(run, exact).public(return_beams)
 

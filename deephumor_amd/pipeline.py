@@ -56,13 +56,10 @@ class CaptionPipeline:
         if settings.return_attention:
             raise NotImplementedError("return_attention: CaptionPipeline hands batches over through pinned (tokens, lengths) / BeamCaptions "
                                       "slots that carry no float payload; call model.generate_batch(..., return_attention=True)")
-        gen_kw.pop("return_attention", None)         # (False: the pipeline without the keyword)
         if settings.return_logprobs:
             raise NotImplementedError("return_logprobs: CaptionPipeline hands batches over through pinned (tokens, lengths) / BeamCaptions "
                                       "slots that carry no float payload; call model.generate_batch(..., return_logprobs=True)")
-        gen_kw.pop("return_logprobs", None)          # (the same)
-        if settings.sequence_bias is None:
-            gen_kw.pop("sequence_bias", None)        # (``None`` / an empty mapping: the same; a list is compiled once, by the first batch)
+        settings.call_kw(gen_kw)                     # (a setting that is off: the pipeline without the keyword)
         self.model, self.gen_kw, self.overlap, self.preprocess = model, gen_kw, overlap, preprocess
         self.dev = next(model.parameters()).device
         if overlap:

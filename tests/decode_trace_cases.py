@@ -20,6 +20,19 @@ the ordered entry-point names of the SECOND call (the first builds the plans):
     j_a j_b  a and b through ``generate_batch_graphed``                 the second replay's outputs
     k_b k_b_beams  ``CaptionPipeline``, two batches of 3, b / b + beams outputs
     l        single-image ``generate``, b                               outputs
+
+Golden G25 (``tests/golden/g25_decode_trace_search_<kind>.npz``, ``search_cases``) holds the settings behind ``search`` the same way --
+``BEAM`` is ``search="beam"``, ``GROUPS`` that with ``beam_size=4, num_beam_groups=2, diversity_penalty=0.5``:
+
+    beam beams_logprobs length      ``BEAM``; + ``return_beams`` and ``return_logprobs``; + ``length_penalty=1.0``   launches + outputs
+    stop_true stop_false            ``BEAM`` + ``early_stopping``                                                   launches + outputs
+    stop_pool stop_full             ``stop_true`` + ``return_beams`` and a bias towards ``<eos>``: some / only pool entries  launches + outputs
+    groups groups_length groups_beams  ``GROUPS``; + ``length_penalty=1.0``; + ``return_beams``                      launches + outputs
+    bias_logprobs                   ``search="sample"``, ``sequence_bias``, ``return_logprobs``                     launches + outputs
+    bias_prompts                    b + ``sequence_bias`` behind the 0 / 2 / 4 prompts                              launches + outputs
+    graphed_length                  ``BEAM`` + ``length_penalty=1.0`` through ``generate_batch_graphed``            the second replay's outputs
+    pipe_groups pipe_groups_beams   ``CaptionPipeline``, ``GROUPS`` / + ``return_beams``                            outputs
+    one                             single-image ``generate``, ``BEAM``                                             outputs
 """
 import functools
 
@@ -37,8 +50,19 @@ PROMPTS = torch.tensor([[17, 230, 45, 7], [8, 9, 8, 11], [300, 301, 302, 303]])
 PROMPT_LENGTHS = torch.tensor([0, 2, 4])
 
 
+BEAM = dict(search="beam")
+GROUPS = dict(search="beam", beam_size=4, num_beam_groups=2, diversity_penalty=0.5)
+BIAS = {(17,): -2.0, (230, 45): 3.0, (8,): 1.5, (300, 8): -1.0}
+EOS_BIAS = {(3,): 6.0}               # towards <eos>: the finished-hypothesis pool takes entries
+EOS_FIRST = {(3,): 12.0}             # every row's best candidate is <eos>: behind ``min_len`` the pool is full within two positions
+
+
 def fixture_name(kind):
     return f"g24_decode_trace_{kind}.npz"
+
+
+def search_fixture_name(kind):
+    return f"g25_decode_trace_search_{kind}.npz"
 
 
 @functools.lru_cache(maxsize=2)
@@ -52,18 +76,18 @@ def build(kind, tag, pad_index=0):
 
 
 def fields(res):
-    """Any public result as ``{name: tensor}``."""
+    """Any public result as ``{name: tensor}``: a caption alone, a ``BeamCaptions``, or a tuple that begins with either (or with the
+    ``tokens`` of the plain pair) and goes on with ``lengths``, ``attention`` (one dimension more than ``tokens``) and ``logprobs``."""
     if torch.is_tensor(res):                           # generate: the caption
         return {"tokens": res}
     if hasattr(res, "_fields"):                        # a BeamCaptions
         return dict(zip(res._fields, res))
-    if hasattr(res[0], "_fields"):                     # (BeamCaptions, attention)
-        return dict(fields(res[0]), attention=res[1])
-    if len(res) == 3:
-        return dict(zip(("tokens", "lengths", "attention"), res))
-    if res[1].is_floating_point():                     # generate with return_attention: (caption, its map)
-        return dict(zip(("tokens", "attention"), res))
-    return dict(zip(("tokens", "lengths"), res))
+    out = fields(res[0])
+    for t in res[1:]:
+        name = "lengths" if not t.is_floating_point() else "attention" if t.dim() > out["tokens"].dim() else "logprobs"
+        assert name not in out, (name, [tuple(x.shape) for x in res[1:]])
+        out[name] = t
+    return out
 
 
 def to_numpy(res):
@@ -104,11 +128,11 @@ def second(call):
         return to_numpy(call())
 
 
-def pipeline(model, images, **extra):
+def pipeline(model, images, controls=CONTROLS, **extra):
     """Two batches of three host images through ``CaptionPipeline``, seeds 1 and 2; every field of both results."""
     from deephumor_amd.pipeline import CaptionPipeline
-    kw = {k: v for k, v in KW.items() if k != "seed"}
-    pipe = CaptionPipeline(model, **kw, **CONTROLS, **extra)
+    kw = {k: v for k, v in {**KW, **controls, **extra}.items() if k != "seed"}
+    pipe = CaptionPipeline(model, **kw)
     out = {}
     for i, res in enumerate(pipe.run([(images[:3],), (images[1:],)], seeds=[1, 2])):
         out.update((f"batch{i}_{k}", v) for k, v in to_numpy(res).items())
@@ -120,7 +144,7 @@ def _images():
     return synth_images(4, seed=0)
 
 
-def _cases(kind, tag):
+def _cases(kind, tag, search=False):
     """Thunks only: nothing touches the GPU (or builds an image) until one is called."""
     three = lambda: _images()[:3].cuda()
     model = lambda pad_index=0: build(kind, tag, pad_index)
@@ -128,8 +152,10 @@ def _cases(kind, tag):
     def batch(pad_index=0, caption=None, **kw):
         def call():
             cap = {} if caption is None else {"caption": caption.cuda()}
-            return model(pad_index).generate_batch(three(), **KW, **cap, **kw)
+            return model(pad_index).generate_batch(three(), **{**KW, **cap, **kw})
         return lambda: traced(call)
+    if search:
+        return _search_cases(model, three, batch)
     out = {"a": batch(), "b": batch(**CONTROLS), "c": batch(return_beams=True)}
     if kind == "CaptioningTransformer":
         out["d"] = batch(return_attention=True)
@@ -147,6 +173,32 @@ def _cases(kind, tag):
     return out
 
 
+def _search_cases(model, three, batch):
+    """The second table (golden G25): the settings behind ``search``."""
+    out = {"beam": batch(**BEAM),
+           "beams_logprobs": batch(**BEAM, return_beams=True, return_logprobs=True),
+           "length": batch(**BEAM, length_penalty=1.0),
+           "stop_true": batch(**BEAM, early_stopping=True),
+           "stop_false": batch(**BEAM, early_stopping=False),
+           "stop_pool": batch(**BEAM, early_stopping=True, return_beams=True, sequence_bias=EOS_BIAS),
+           "stop_full": batch(**BEAM, early_stopping=True, return_beams=True, sequence_bias=EOS_FIRST, min_len=3),
+           "groups": batch(**GROUPS),
+           "groups_length": batch(**GROUPS, length_penalty=1.0),
+           "groups_beams": batch(**GROUPS, return_beams=True),
+           "bias_logprobs": batch(search="sample", sequence_bias=BIAS, return_logprobs=True),
+           "bias_prompts": batch(caption=PROMPTS, caption_lengths=PROMPT_LENGTHS, **CONTROLS, sequence_bias=BIAS)}
+    out["graphed_length"] = lambda: second(lambda: model().generate_batch_graphed(three(), **KW, **BEAM, length_penalty=1.0))
+    out["pipe_groups"] = lambda: pipeline(model(), _images(), controls=GROUPS)
+    out["pipe_groups_beams"] = lambda: pipeline(model(), _images(), controls=GROUPS, return_beams=True)
+    out["one"] = lambda: second(lambda: model().generate(_images()[:1].cuda(), **KW, **BEAM))
+    return out
+
+
 def cases(kind):
     """``{"<dtype>/<case>": thunk}`` in running order; ``thunk()`` runs the case on the GPU and returns ``{field: numpy array}``."""
     return {f"{tag}/{name}": thunk for tag in DTYPES for name, thunk in _cases(kind, tag).items()}
+
+
+def search_cases(kind):
+    """``cases`` for golden G25."""
+    return {f"{tag}/{name}": thunk for tag in DTYPES for name, thunk in _cases(kind, tag, search=True).items()}

@@ -16,6 +16,12 @@ def meta():
         return json.load(f)
 
 
+# ``dataclasses.fields(beam.DecodeSettings)``, in order: one declared field per decode setting
+DECODE_FIELDS = ["return_beams", "return_attention", "top_p", "no_repeat_ngram_size", "repetition_penalty", "min_len", "bad_words_ids",
+                 "num_tokens", "search", "return_logprobs", "length_penalty", "early_stopping", "num_beam_groups", "diversity_penalty",
+                 "sequence_bias"]
+
+
 def golden(name):
     return np.load(os.path.join(GOLDEN, name))
 

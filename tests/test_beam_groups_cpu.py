@@ -16,7 +16,7 @@ import torch
 import beam_groups_ref as GR
 import beam_search_ref as R
 import length_penalty_ref as LP
-from helpers import KINDS, synthetic_sd
+from helpers import DECODE_FIELDS, KINDS, synthetic_sd
 
 from deephumor_amd import _abi, _build, hip
 from deephumor_amd.models import beam
@@ -268,7 +268,7 @@ def test_check_beam_groups():
 
 def test_the_record_key_hash_and_pickle():
     names = [f.name for f in dataclasses.fields(DecodeSettings)]
-    assert "num_beam_groups" not in names and "diversity_penalty" not in names and names[-1] == "search"
+    assert names == DECODE_FIELDS
     mk = lambda **kw: DecodeSettings.from_kw(dict(search="beam", **kw), 25, 100)
     plain, one, two, three = mk(), mk(num_beam_groups=1, diversity_penalty=0.0), mk(num_beam_groups=2, diversity_penalty=0.5), \
         mk(num_beam_groups=3, diversity_penalty=0.5)
@@ -276,19 +276,20 @@ def test_the_record_key_hash_and_pickle():
     assert len({plain, two, three, mk(num_beam_groups=2, diversity_penalty=0.75)}) == 4
     assert len({hash(plain), hash(two), hash(three)}) == 3
     assert DecodeSettings().num_beam_groups == 1 and DecodeSettings().diversity_penalty == 0.0
-    # the key of a record without groups is what it was; with groups ONE element in front
-    assert len(plain._key()) == 11 and plain._key()[-4:] == (None, 0.0, False, "beam")
-    assert len(two._key()) == 12 and two._key()[0] == (2, 0.5) and two._key()[1:] == plain._key()
+    tail = lambda s: (s.early_stopping, s.length_penalty, s.return_logprobs, s.search)
+    assert tail(plain) == (None, 0.0, False, "beam") and (plain.num_beam_groups, plain.diversity_penalty) == (1, 0.0)
+    assert (two.num_beam_groups, two.diversity_penalty) == (2, 0.5) and dataclasses.replace(two, num_beam_groups=1, diversity_penalty=0.0) == plain
     both = mk(num_beam_groups=3, diversity_penalty=2, length_penalty=1.5, min_len=2)
-    assert both._key()[0] == (3, 2.0) and both._key()[-4:] == (None, 1.5, False, "beam")
+    assert (both.num_beam_groups, both.diversity_penalty) == (3, 2.0) and tail(both) == (None, 1.5, False, "beam")
     for clone in (copy.copy(both), copy.deepcopy(both), pickle.loads(pickle.dumps(both)), both.compiled("cpu"), dataclasses.replace(both, min_len=2)):
         assert clone == both and hash(clone) == hash(both) and clone.num_beam_groups == 3 and clone.diversity_penalty == 2.0
-        assert clone.length_penalty == 1.5
-    assert dataclasses.replace(both, search="beam") == mk(min_len=2)             # a plain string drops what rides on it
-    s = pickle.loads(pickle.dumps(two.search))
-    assert s == "beam" and s.num_beam_groups == 2 and s.diversity_penalty == 0.5 and s.length_penalty == 0.0 and s.early_stopping is None
+        assert clone.length_penalty == 1.5 and clone.min_len == 2 and type(clone.search) is str
+    same = dataclasses.replace(both, search="beam")                              # every setting is a field of its own: all stay
+    assert same == both and same.length_penalty == 1.5 and same.num_beam_groups == 3 and same.diversity_penalty == 2.0
+    s = pickle.loads(pickle.dumps(two))
+    assert s.search == "beam" and s.num_beam_groups == 2 and s.diversity_penalty == 0.5 and s.length_penalty == 0.0 and s.early_stopping is None
     back = DecodeSettings.from_kw(dict(search=two.search), 25, 100)              # the keywords alone set them
-    assert back.num_beam_groups == 1 and type(back.search) is str
+    assert back.num_beam_groups == 1 and type(back.search) is str and type(two.search) is str and back == plain
     with pytest.raises(dataclasses.FrozenInstanceError):
         two.num_beam_groups = 1
     kw = dict(search="beam", num_beam_groups=2, diversity_penalty=1.0)
@@ -424,10 +425,8 @@ def test_keywords_ride_in_kw_and_the_pinned_lists_stay():
         ps = inspect.signature(fn).parameters
         assert "num_beam_groups" not in ps and "diversity_penalty" not in ps, fn
         assert any(q.kind is inspect.Parameter.VAR_KEYWORD for q in ps.values()), fn
-    for cls in (LSTMDecoder, _IncrementalDecoder):
-        assert list(inspect.signature(cls._decode_session).parameters)[-4:] == ["num_beam_groups", "diversity_penalty", "length_penalty",
-                                                                                 "early_stopping"]
-    assert list(inspect.signature(LSTMDecoder.generate_batch).parameters)[-1] == "repetition_penalty"
+    # (the signatures of every public callable, and the keyword on its way to DecodeSettings.from_kw: test_decode_settings_cpu)
+    assert [p.name for p in inspect.signature(LSTMDecoder.generate_batch).parameters.values() if p.kind is not p.VAR_KEYWORD][-1] == "repetition_penalty"
     with pytest.raises(TypeError, match="num_beam_groups"):                    # ... and takes the keyword by name
         LSTMDecoder(50).generate_batch(torch.zeros(1, 256), search="beam", num_beam_groups=2.5, diversity_penalty=1.0)
     with pytest.raises(ValueError, match="must divide beam_size"):

@@ -296,3 +296,106 @@ def test_session_result_cat_and_public(beams, deferred, attention):
         assert type(out) is tuple and len(out) == len(want)
         for got, w in zip(out, want):
             assert got is w or (torch.is_tensor(w) and torch.equal(got, w))
+
+
+# ---- the public callables and the record's field list ---------------------------------------------------------------------------------
+KW, ONLY, VARARGS = "POSITIONAL_OR_KEYWORD", "KEYWORD_ONLY", "VAR_POSITIONAL"
+GEN = [("caption", KW, None), ("max_len", KW, 25), ("temperature", KW, 1.0), ("beam_size", KW, 10), ("top_k", KW, 50), ("eos_index", KW, 3)]
+LENGTHS = [("caption_lengths", ONLY, None)]
+GRAPHED = [("self", KW, None), ("inputs", VARARGS, None), ("seed", ONLY, None), ("caption", ONLY, None), ("caption_lengths", ONLY, None)]
+ENGINE = [("seed", KW, None), ("img0", KW, 0), ("noise_source", KW, None), ("logits_hook", KW, None), ("streams", KW, 1), ("seed_tensor", KW, None),
+          ("defer_check", KW, False), ("early_stop_every", KW, 0), ("exact", KW, False), ("rng", KW, None)]
+MODEL_KINDS = {"CaptioningLSTM": ["images"], "CaptioningLSTMWithLabels": ["images", "labels"], "CaptioningTransformerBase": ["images"],
+               "CaptioningTransformer": ["images"], "CaptioningTransformerWithLabels": ["images", "labels"]}
+DECODER_KINDS = {"LSTMDecoder": ["image_emb"], "TransformerDecoder": ["start_emb", "enc_out"], "SelfAttentionTransformerDecoder": ["start_emb"]}
+# every setting, in the record's order, with the value that switches it off and one that switches it on
+SETTINGS = [("return_beams", False, True), ("return_attention", False, True), ("top_p", 1.0, 0.8), ("no_repeat_ngram_size", 0, 2),
+            ("repetition_penalty", 1.0, 1.3), ("min_len", 0, 3), ("bad_words_ids", None, [[7]]), ("search", "sample", "beam"),
+            ("return_logprobs", False, True), ("length_penalty", 0.0, 1.0), ("early_stopping", None, True), ("num_beam_groups", 1, 2),
+            ("diversity_penalty", 0.0, 0.5), ("sequence_bias", None, {(7,): 1.0})]
+
+
+def named(fn):
+    """``fn``'s parameters but its ``**kw``: ``(name, kind, default or None)``."""
+    empty = inspect.Parameter.empty
+    return [(p.name, p.kind.name, None if p.default is empty else p.default) for p in inspect.signature(fn).parameters.values()
+            if p.kind is not inspect.Parameter.VAR_KEYWORD]
+
+
+def public_callables():
+    """``{(class name, method name): the named parameters it has had since before the settings moved into ``kw``}``."""
+    me = [("self", KW, None)]
+    out = {}
+    for kind, inputs in MODEL_KINDS.items():
+        one = [(n[:-1], KW, None) for n in inputs]                     # images -> image, labels -> label
+        out[kind, "generate_batch"] = me + [(n, KW, None) for n in inputs] + GEN + LENGTHS
+        out[kind, "generate"] = me + one + GEN
+        out[kind, "decode"] = me + [("encoded", KW, None)] + GEN + LENGTHS
+        out[kind, "generate_batch_graphed"] = GRAPHED
+    for kind, inputs in DECODER_KINDS.items():
+        out[kind, "generate_batch"] = me + [(n, KW, None) for n in inputs] + GEN + LENGTHS
+        out[kind, "generate"] = me + [(n, KW, None) for n in inputs] + GEN
+    out["LSTMDecoder", "generate_batch"] = (me + [("image_emb", KW, None)] + GEN + ENGINE + LENGTHS + [
+        ("return_beams", ONLY, False), ("top_p", ONLY, 1.0), ("no_repeat_ngram_size", ONLY, 0), ("repetition_penalty", ONLY, 1.0)])
+    return out
+
+
+def test_the_record_declares_one_field_per_setting():
+    import dataclasses
+    names = [f.name for f in dataclasses.fields(DecodeSettings)]
+    assert names == ["return_beams", "return_attention", "top_p", "no_repeat_ngram_size", "repetition_penalty", "min_len", "bad_words_ids",
+                     "num_tokens", "search", "return_logprobs", "length_penalty", "early_stopping", "num_beam_groups", "diversity_penalty",
+                     "sequence_bias"]
+    assert list(DecodeSettings.names()) == [n for n in names if n != "num_tokens"] == [s[0] for s in SETTINGS]
+    off = DecodeSettings()
+    assert [getattr(off, name) for name, _, _ in SETTINGS] == [default for _, default, _ in SETTINGS] and off.num_tokens is None
+    assert off == DecodeSettings.from_kw({}, 25, 100) and off == DecodeSettings.from_kw({name: default for name, default, _ in SETTINGS}, 25, 100)
+
+
+@pytest.mark.parametrize("cls,method", list(public_callables()), ids=lambda v: v)
+def test_public_signature_and_every_setting_by_keyword(cls, method, monkeypatch):
+    """The named parameters are what they were (name, position, kind, default); every setting is taken by keyword and reaches
+    ``DecodeSettings.from_kw`` -- before anything else runs --; a keyword nobody knows is a ``TypeError``."""
+    import deephumor_amd.models as M
+    from deephumor_amd.models import rnn_models, transformers
+    owner = getattr(M, cls, None) or getattr(rnn_models, cls, None) or getattr(transformers, cls)
+    assert named(getattr(owner, method)) == public_callables()[cls, method]
+    assert any(p.kind is inspect.Parameter.VAR_KEYWORD for p in inspect.signature(getattr(owner, method)).parameters.values())
+
+    obj = owner(50, n_layers=1) if "Transformer" in cls else owner(50)
+    obj.eval()
+    inputs = {"images": torch.zeros(1, 3, 224, 224), "labels": torch.zeros(1, 2, dtype=torch.long), "image_emb": torch.zeros(1, 256),
+              "start_emb": torch.zeros(1, 512), "enc_out": torch.zeros(1, 49, 512)}
+    args = [inputs[n] for n in {**MODEL_KINDS, **DECODER_KINDS}[cls]]
+    if method == "decode":
+        args = [tuple(inputs[n] for n in DECODER_KINDS[type(obj.decoder).__name__])]
+
+    class Reached(Exception):
+        pass
+    seen = []
+
+    def from_kw(kw, *a, **k):
+        seen.append(dict(kw))
+        raise Reached
+    with monkeypatch.context() as mp:
+        mp.setattr(DecodeSettings, "from_kw", from_kw)
+        attention = not (cls == "LSTMDecoder" or (method == "decode" and "LSTM" in cls))      # (a decoder without maps does not know the keyword at all)
+        for name, _, on in SETTINGS:
+            if name == "return_attention" and not attention:
+                continue
+            with pytest.raises(Reached):
+                getattr(obj, method)(*args, **{name: on})
+            assert seen[-1][name] == on, name
+        everything = {name: on for name, _, on in SETTINGS if attention or name != "return_attention"}
+        with pytest.raises(Reached):
+            getattr(obj, method)(*args, **everything)
+        assert {k: seen[-1][k] for k in everything} == everything
+    if cls in DECODER_KINDS or method == "decode":                     # (the models hand ``kw`` on: their decoder refuses the name)
+        with pytest.raises(TypeError, match="unexpected keyword.*no_such_keyword"):
+            getattr(obj, method)(*args, no_such_keyword=1)
+        with pytest.raises(TypeError, match="unexpected keyword.*no_such_keyword"):
+            getattr(obj, method)(*args, search="beam", sequence_bias=None, no_such_keyword=1)
+    elif method != "generate_batch_graphed":                           # (that one meets its decoder inside the warm-up run, on a GPU)
+        obj.encode = lambda *a: tuple(inputs[n] for n in DECODER_KINDS[type(obj.decoder).__name__])
+        with pytest.raises(TypeError, match="unexpected keyword.*no_such_keyword"):
+            getattr(obj, method)(*args, no_such_keyword=1)

@@ -16,7 +16,7 @@ import torch
 import beam_search_ref as R
 import early_stopping_ref as ES
 import length_penalty_ref as LP
-from helpers import KINDS, synthetic_sd
+from helpers import DECODE_FIELDS, KINDS, synthetic_sd
 
 from deephumor_amd import _abi, _build, hip
 from deephumor_amd.models import beam
@@ -257,22 +257,25 @@ def test_check_early_stopping():
 
 def test_the_record_key_hash_and_pickle():
     names = [f.name for f in dataclasses.fields(DecodeSettings)]
-    assert "early_stopping" not in names and names[-1] == "search"
+    assert names == DECODE_FIELDS
     plain, none = DecodeSettings.from_kw(dict(search="beam"), 25, 100), DecodeSettings.from_kw(dict(search="beam", early_stopping=None), 25, 100)
     on, off = (DecodeSettings.from_kw(dict(search="beam", early_stopping=v), 25, 100) for v in (True, False))
     assert plain == none and hash(plain) == hash(none) and type(none.search) is str and none.early_stopping is None
     assert len({plain, on, off}) == 3 and on.early_stopping is True and off.early_stopping is False and DecodeSettings().early_stopping is None
-    assert on._key()[-4] is True and off._key()[-4] is False and plain._key()[-4] is None
-    assert on._key()[-3:] == (0.0, False, "beam") and len(on._key()) == len(plain._key()) == 11
+    tail = lambda s: (s.early_stopping, s.length_penalty, s.return_logprobs, s.search)
+    assert tail(on) == (True, 0.0, False, "beam") and tail(off) == (False, 0.0, False, "beam") and tail(plain) == (None, 0.0, False, "beam")
+    assert dataclasses.replace(on, early_stopping=None) == plain == dataclasses.replace(off, early_stopping=None)
     both = DecodeSettings.from_kw(dict(search="beam", early_stopping=False, length_penalty=1.5, min_len=2), 25, 100)
-    assert both._key()[-4:] == (False, 1.5, False, "beam") and both.length_penalty == 1.5
+    assert tail(both) == (False, 1.5, False, "beam") and both.length_penalty == 1.5
     for clone in (copy.copy(both), copy.deepcopy(both), pickle.loads(pickle.dumps(both)), both.compiled("cpu"), dataclasses.replace(both, min_len=2)):
         assert clone == both and hash(clone) == hash(both) and clone.early_stopping is False and clone.length_penalty == 1.5
-    assert dataclasses.replace(both, search="beam") == DecodeSettings.from_kw(dict(search="beam", min_len=2), 25, 100)
-    s = pickle.loads(pickle.dumps(on.search))
-    assert s == "beam" and s.early_stopping is True and s.length_penalty == 0.0
+        assert clone.min_len == 2 and type(clone.search) is str
+    same = dataclasses.replace(both, search="beam")                              # every setting is a field of its own: all stay
+    assert same == both and same.early_stopping is False and same.length_penalty == 1.5
+    s = pickle.loads(pickle.dumps(on))
+    assert s.search == "beam" and s.early_stopping is True and s.length_penalty == 0.0
     back = DecodeSettings.from_kw(dict(search=on.search), 25, 100)              # the keyword alone sets it
-    assert back.early_stopping is None and type(back.search) is str
+    assert back.early_stopping is None and type(back.search) is str and type(on.search) is str and back == plain
     with pytest.raises(dataclasses.FrozenInstanceError):
         on.early_stopping = None
     kw = dict(search="beam", early_stopping=True)
@@ -413,13 +416,9 @@ def test_keyword_rides_in_kw_and_the_pinned_lists_stay():
     for fn in fns:
         ps = inspect.signature(fn).parameters
         assert "early_stopping" not in ps and any(q.kind is inspect.Parameter.VAR_KEYWORD for q in ps.values()), fn
-    assert list(inspect.signature(LSTMDecoder._generate_batch).parameters)[-1] == "bad_words_ids"
-    assert list(inspect.signature(LSTMDecoder._decode_batch).parameters)[-1] == "search"
-    assert list(inspect.signature(_IncrementalDecoder._generate_batch).parameters)[-1] == "search"
-    assert list(inspect.signature(LSTMDecoder.generate_batch).parameters)[-1] == "repetition_penalty"
-    assert list(inspect.signature(LSTMDecoder._decode_session).parameters)[-2:] == ["length_penalty", "early_stopping"]
-    assert list(inspect.signature(_IncrementalDecoder._decode_session).parameters)[-2:] == ["length_penalty", "early_stopping"]
-    assert [f.name for f in dataclasses.fields(DecodeSettings)][-2:] == ["num_tokens", "search"]
+    # (the signatures of every public callable, and the keyword on its way to DecodeSettings.from_kw: test_decode_settings_cpu)
+    assert [p.name for p in inspect.signature(LSTMDecoder.generate_batch).parameters.values() if p.kind is not p.VAR_KEYWORD][-1] == "repetition_penalty"
+    assert [f.name for f in dataclasses.fields(DecodeSettings)] == DECODE_FIELDS
     with pytest.raises(TypeError, match="early_stopping"):                     # ... and takes the keyword by name
         LSTMDecoder(50).generate_batch(torch.zeros(1, 256), search="beam", early_stopping=1)
 

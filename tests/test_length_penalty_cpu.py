@@ -13,7 +13,7 @@ import torch
 
 import beam_search_ref as R
 import length_penalty_ref as LP
-from helpers import KINDS, synthetic_sd
+from helpers import DECODE_FIELDS, KINDS, synthetic_sd
 
 from deephumor_amd import _abi, _build, hip
 from deephumor_amd.models import beam
@@ -61,7 +61,7 @@ def test_the_engine_table_is_the_restatement_table():
 # ---- the settings record -----------------------------------------------------------------------------------------------------------
 def test_settings_carry_it_outside_the_field_list():
     names = [f.name for f in DecodeSettings.__dataclass_fields__.values()]
-    assert "length_penalty" not in names and names[-2:] == ["search", "return_logprobs"]
+    assert names == DECODE_FIELDS
     plain = DecodeSettings.from_kw({}, 25, 100)
     off = DecodeSettings.from_kw(dict(length_penalty=0.0), 25, 100)
     off_beam, beam_plain = DecodeSettings.from_kw(dict(search="beam", length_penalty=0), 25, 100), DecodeSettings.from_kw(dict(search="beam"), 25, 100)
@@ -71,9 +71,9 @@ def test_settings_carry_it_outside_the_field_list():
     assert on != beam_plain and on != plain and len({plain, off, beam_plain, off_beam, on}) == 3
     assert on == DecodeSettings.from_kw(dict(search="beam", length_penalty=1), 8, 10)
     assert on != DecodeSettings.from_kw(dict(search="beam", length_penalty=2.0), 25, 100)
-    assert on.search == "beam" and on._key()[-1] == "beam" and on._key()[-3] == 1.0 and plain._key()[-3] == 0.0
+    assert on.search == "beam" and type(on.search) is str and on.length_penalty == 1.0 and plain.length_penalty == 0.0
     lp_on = DecodeSettings.from_kw(dict(search="beam", length_penalty=1.0, return_logprobs=True), 25, 100)
-    assert lp_on._key()[:-2] == on._key()[:-2] and lp_on != on
+    assert dataclasses.replace(lp_on, return_logprobs=False) == on and lp_on != on
     with pytest.raises(dataclasses.FrozenInstanceError):
         on.length_penalty = 0.0
     # it survives compiled() and replace() of another field
@@ -470,10 +470,8 @@ def test_keyword_rides_in_kw_and_the_pinned_lists_stay():
     for fn in fns:
         ps = inspect.signature(fn).parameters
         assert "length_penalty" not in ps and any(q.kind is inspect.Parameter.VAR_KEYWORD for q in ps.values()), fn
-    assert list(inspect.signature(LSTMDecoder._generate_batch).parameters)[-1] == "bad_words_ids"
-    assert list(inspect.signature(LSTMDecoder._decode_batch).parameters)[-1] == "search"
-    assert list(inspect.signature(_IncrementalDecoder._generate_batch).parameters)[-1] == "search"
-    assert list(inspect.signature(LSTMDecoder.generate_batch).parameters)[-1] == "repetition_penalty"
+    # (the signatures of every public callable, and the keyword on its way to DecodeSettings.from_kw: test_decode_settings_cpu)
+    assert [p.name for p in inspect.signature(LSTMDecoder.generate_batch).parameters.values() if p.kind is not p.VAR_KEYWORD][-1] == "repetition_penalty"
     with pytest.raises(ValueError, match="length_penalty"):                  # ... and takes the keyword by name
         LSTMDecoder(50).generate_batch(torch.zeros(1, 256), search="beam", length_penalty=float("nan"))
 
@@ -620,18 +618,19 @@ def test_the_cache_evicts_the_least_recently_used_table():
     assert beam.held_length_weights(0.0, "cpu") == () and len(beam.held_length_weights(3.0, "cpu")) == 1
 
 
-def test_the_carrier_on_search_copies_pickles_and_takes_the_penalty_from_the_keyword_alone():
+def test_the_record_copies_pickles_and_takes_the_penalty_from_the_keyword_alone():
     import copy
     import pickle
     on = DecodeSettings.from_kw(dict(search="beam", length_penalty=1.5, min_len=2), 25, 100)
-    for clone in (copy.copy(on), copy.deepcopy(on), pickle.loads(pickle.dumps(on))):
+    for clone in (copy.copy(on), copy.deepcopy(on), pickle.loads(pickle.dumps(on)), on.compiled("cpu"), dataclasses.replace(on, min_len=2)):
         assert clone == on and clone.length_penalty == 1.5 and clone.search == "beam" and hash(clone) == hash(on)
+        assert clone.min_len == 2 and type(clone.search) is str
     s = pickle.loads(pickle.dumps(on.search))
-    assert s == "beam" and s.length_penalty == 1.5 and type(s) is type(on.search)
-    # replace(search=<a plain string>) is the record without the penalty
-    plain = dataclasses.replace(on, search="beam")
-    assert plain.length_penalty == 0.0 and plain == DecodeSettings.from_kw(dict(search="beam", min_len=2), 25, 100)
-    # a carrier handed back in as `search` brings no penalty with it: the keyword alone sets one
+    assert s == "beam" and type(s) is str and type(on.search) is str
+    # the penalty is a field of its own: replace(search=...) keeps it
+    same = dataclasses.replace(on, search="beam")
+    assert same.length_penalty == 1.5 and same == on and same != DecodeSettings.from_kw(dict(search="beam", min_len=2), 25, 100)
+    # a record's `search` handed back in brings no penalty with it: the keyword alone sets one
     back = DecodeSettings.from_kw(dict(search=on.search), 25, 100)
     assert back.length_penalty == 0.0 and type(back.search) is str and back == DecodeSettings.from_kw(dict(search="beam"), 25, 100)
     both = DecodeSettings.from_kw(dict(search=on.search, length_penalty=0.5), 25, 100)

@@ -1,6 +1,7 @@
 """``return_logprobs`` on the CPU: the validation, the settings record, the result layouts, the helper's launch order, the C-ABI
 additions, the refusals -- and the two restatements of ``tests/logprobs_ref.py`` against each other: the slab tables walked backwards
 (``gather(record(...))``, what the kernels do) and the rows carried forwards (``track``) on random searches."""
+import dataclasses
 import inspect
 import os
 import re
@@ -9,7 +10,7 @@ import pytest
 import torch
 
 import logprobs_ref as R
-from helpers import synthetic_sd
+from helpers import DECODE_FIELDS, synthetic_sd
 
 from deephumor_amd import _abi, _build, hip
 from deephumor_amd.models import beam
@@ -49,7 +50,7 @@ def test_check_return_logprobs():
 # ---- the settings record -----------------------------------------------------------------------------------------------------------
 def test_settings_carry_it_last():
     names = [f.name for f in DecodeSettings.__dataclass_fields__.values()]
-    assert names[-2:] == ["search", "return_logprobs"] and names[:9] == [
+    assert names == DECODE_FIELDS and names[9] == "return_logprobs" and names[:9] == [
         "return_beams", "return_attention", "top_p", "no_repeat_ngram_size", "repetition_penalty", "min_len", "bad_words_ids", "num_tokens",
         "search"]
     plain = DecodeSettings.from_kw({}, 25, 1000)
@@ -58,7 +59,7 @@ def test_settings_carry_it_last():
     assert plain.return_logprobs is False and DecodeSettings().return_logprobs is False and on.return_logprobs is True
     assert plain == off and hash(plain) == hash(off) and on != plain and len({plain, off, on}) == 2
     assert on == DecodeSettings.from_kw(dict(return_logprobs=True), 8, 10) and hash(on) == hash(DecodeSettings.from_kw(dict(return_logprobs=True), 8))
-    assert on._key()[-1] == "sample" and plain._key()[:-2] == on._key()[:-2]
+    assert on.search == "sample" and type(on.search) is str and dataclasses.replace(on, return_logprobs=False) == plain
     with pytest.raises(AttributeError):
         on.return_logprobs = False
     kw = dict(return_logprobs=True, top_p=0.5)

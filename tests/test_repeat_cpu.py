@@ -145,13 +145,13 @@ def test_bad_values_fail_before_the_encoder(kind):
 
 def test_keyword_only_and_positional_prefixes():
     import deephumor_amd.models as M
-    from deephumor_amd.models.beam import BeamSearchHelper
+    from deephumor_amd.models.beam import BeamSearchHelper, DecodeSettings
     from deephumor_amd.models.rnn_models import LSTMDecoder
-    from deephumor_amd.models.transformers import SelfAttentionTransformerDecoder, TransformerDecoder, _IncrementalDecoder
+    from deephumor_amd.models.transformers import SelfAttentionTransformerDecoder, TransformerDecoder
     for name, default in (("no_repeat_ngram_size", 0), ("repetition_penalty", 1.0)):
         p = inspect.signature(LSTMDecoder.generate_batch).parameters[name]
         assert p.kind is inspect.Parameter.KEYWORD_ONLY and p.default == default
-        assert inspect.signature(_IncrementalDecoder._generate_batch).parameters[name].default == default
+        assert getattr(DecodeSettings(), name) == default        # (the signatures and the keyword's way down: test_decode_settings_cpu)
         # everywhere else the keywords ride in **kw: they cannot be passed by position
         fns = [getattr(getattr(M, kind), fn) for kind in KINDS for fn in ("generate_batch", "decode", "generate", "generate_batch_graphed")]
         fns += [TransformerDecoder.generate_batch, SelfAttentionTransformerDecoder.generate_batch, LSTMDecoder.generate]
@@ -165,7 +165,7 @@ def test_keyword_only_and_positional_prefixes():
     assert names[:19] == ["self", "image_emb", "caption", "max_len", "temperature", "beam_size", "top_k", "eos_index", "seed", "img0",
                           "noise_source", "logits_hook", "streams", "seed_tensor", "defer_check", "early_stop_every", "exact", "rng",
                           "caption_lengths"]
-    assert names[19:] == ["return_beams", "top_p", "no_repeat_ngram_size", "repetition_penalty"]
+    assert names[19:] == ["return_beams", "top_p", "no_repeat_ngram_size", "repetition_penalty", "kw"]
     names = list(inspect.signature(BeamSearchHelper.__init__).parameters)
     assert names[1:7] == ["temperature", "beam_size", "top_k", "unk_index", "eos_index", "device"]
     assert names[names.index("top_p") + 1:] == ["no_repeat_ngram_size", "repetition_penalty"]

@@ -6,7 +6,10 @@ tensor, bit for bit, of the decode layer's routes -- ``generate_batch`` with and
 Needs the GPU, not the reference: the fixture is what THIS tree does, recorded in front of a change to the Python decode layer that
 must move no launch and no bit.  Every case is run twice here and must repeat itself before it is written.
 
-    python tools/make_decode_trace_golden.py [kind ...]
+    python tools/make_decode_trace_golden.py [--search] [kind ...]
+
+``--search``: golden G25 (``g25_decode_trace_search_<kind>.npz``, ``decode_trace_cases.search_cases``) -- the settings behind
+``search``: beam search, log-probabilities, the length penalty, the pool, the groups and the biases.
 """
 import os
 import sys
@@ -23,16 +26,18 @@ OUT = os.path.join(ROOT, "tests", "golden")
 
 
 def main():
-    for kind in (sys.argv[1:] or dt.KINDS):
+    args = [a for a in sys.argv[1:] if a != "--search"]
+    table, fixture = (dt.search_cases, dt.search_fixture_name) if "--search" in sys.argv else (dt.cases, dt.fixture_name)
+    for kind in (args or dt.KINDS):
         fix = {}
-        for key, thunk in dt.cases(kind).items():
+        for key, thunk in table(kind).items():
             got, again = thunk(), thunk()
             assert got.keys() == again.keys(), key
             for name, arr in got.items():
                 assert arr.dtype == again[name].dtype and np.array_equal(arr, again[name], equal_nan=arr.dtype.kind == "f"), (key, name)
                 fix[f"{key}/{name}"] = arr
             print(kind, key, {k: tuple(v.shape) for k, v in got.items()}, flush=True)
-        path = os.path.join(OUT, dt.fixture_name(kind))
+        path = os.path.join(OUT, fixture(kind))
         np.savez_compressed(path, **fix)
         print(path, os.path.getsize(path), "bytes", flush=True)
 
