@@ -218,6 +218,7 @@ def round16_keep_nonzero(x, out_dtype):
 def maxpool3x3s2_nhwc(x):
     _dev(x)
     n, h, w, c = x.shape
+    assert x.is_contiguous()
     out = torch.empty((n, (h - 1) // 2 + 1, (w - 1) // 2 + 1, c), dtype=x.dtype, device=x.device)
     _launch("dh_maxpool3x3s2_nhwc", _ptr(x), _ptr(out), n, h, w, c, _dt(x), _stream())
     return out
@@ -227,6 +228,7 @@ def avgpool_nhwc(x):
     """x [N, H, W, C] channels-last -> [N, C]"""
     _dev(x)
     n, h, w, c = x.shape
+    assert x.is_contiguous()
     out = torch.empty((n, c), dtype=x.dtype, device=x.device)
     _launch("dh_avgpool_nhwc", _ptr(x), _ptr(out), n, h * w, c, _dt(x), _stream())
     return out
@@ -235,6 +237,7 @@ def avgpool_nhwc(x):
 def maxpool3x3s2(x):
     _dev(x)
     n, c, h, w = x.shape
+    assert x.is_contiguous()
     out = torch.empty((n, c, (h - 1) // 2 + 1, (w - 1) // 2 + 1), dtype=x.dtype, device=x.device)
     _launch("dh_maxpool3x3s2", _ptr(x), _ptr(out), n, c, h, w, _dt(x), _stream())
     return out
@@ -244,6 +247,7 @@ def avgpool_rows(x):
     """x [N, C, H, W] -> [N, C]"""
     _dev(x)
     n, c, h, w = x.shape
+    assert x.is_contiguous()
     out = torch.empty((n, c), dtype=x.dtype, device=x.device)
     _launch("dh_avgpool_rows", _ptr(x), _ptr(out), n * c, h * w, _dt(x), _stream())
     return out
@@ -253,6 +257,7 @@ def nchw_to_rows(x):
     """x [N, C, H, W] -> [N, H*W, C]"""
     _dev(x)
     n, c, h, w = x.shape
+    assert x.is_contiguous()
     out = torch.empty((n, h * w, c), dtype=x.dtype, device=x.device)
     _launch("dh_nchw_to_rows", _ptr(x), _ptr(out), n, c, h * w, _dt(x), _stream())
     return out
@@ -364,6 +369,7 @@ def nchw_to_nhwc_f32(x, cp=4):
 def maxpool3x3s2_nhwc_f32(x):
     _dev(x)
     n, h, w, c = x.shape
+    assert x.dtype == torch.float32 and x.is_contiguous()
     y = torch.empty((n, (h + 2 - 3) // 2 + 1, (w + 2 - 3) // 2 + 1, c), dtype=torch.float32, device=x.device)
     _launch("dh_maxpool3x3s2_nhwc_f32", _ptr(x), _ptr(y), n, h, w, c, _stream())
     return y
@@ -373,6 +379,7 @@ def avgpool_nhwc_f32(x):
     """x [N, H, W, C] fp32 -> [N, C]."""
     _dev(x)
     n, h, w, c = x.shape
+    assert x.dtype == torch.float32 and x.is_contiguous()
     y = torch.empty((n, c), dtype=torch.float32, device=x.device)
     _launch("dh_avgpool_nhwc_f32", _ptr(x), _ptr(y), n, h * w, c, _stream())
     return y
@@ -671,6 +678,11 @@ def pack_stem_weight(w, dtype):
 def embed_rows(tok_emb, pos_emb, start_emb, tokens, x, rows, rows_per_img, row_mult, pos, scale):
     _dev(tok_emb, pos_emb, start_emb, tokens, x)
     d = tok_emb.shape[1]
+    # the library takes no row strides but the token table's: every embedding and the output are whole [*, d] rows of one type
+    assert tok_emb.is_contiguous() and pos_emb.is_contiguous() and pos_emb.shape[1] == d and pos_emb.dtype == tok_emb.dtype
+    assert start_emb is None or (start_emb.is_contiguous() and start_emb.shape[1] == d and start_emb.dtype == tok_emb.dtype)
+    assert x.is_contiguous() and x.dim() == 2 and x.shape[1] == d and x.shape[0] >= rows and x.dtype == tok_emb.dtype
+    assert tokens is None or (tokens.dtype == torch.int32 and tokens.dim() == 2 and tokens.stride(1) == 1)
     _launch("dh_embed_rows", _ptr(tok_emb), _ptr(pos_emb), _ptr(start_emb), _ptr(tokens),
                                 tokens.stride(0) if tokens is not None else 0, _ptr(x), rows, rows_per_img,
                                 row_mult, pos, d, float(scale), _dt(tok_emb), _stream())
@@ -681,7 +693,11 @@ def add_layernorm(x, y, gamma, beta, out=None, eps=1e-5):
     _dev(x, y, gamma, beta)
     rows, d = x.shape
     if out is None:
-        out = torch.empty_like(x)
+        out = torch.empty((rows, d), dtype=x.dtype, device=x.device)
+    # the library takes no row stride: x, y and out are whole [rows, d] rows of one type, gamma and beta fp32 [d]
+    assert x.is_contiguous() and (y is None or (y.is_contiguous() and y.shape == x.shape and y.dtype == x.dtype))
+    assert out.is_contiguous() and out.shape == x.shape and out.dtype == x.dtype
+    assert all(p.dtype == torch.float32 and p.is_contiguous() and p.shape == (d,) for p in (gamma, beta))
     _launch("dh_add_layernorm", _ptr(x), _ptr(y), _ptr(gamma), _ptr(beta), _ptr(out), rows, d, float(eps),
                                    _dt(x), _stream())
     return out
@@ -744,6 +760,7 @@ def enc_key_mask(enc_out):
     """enc_out [rows, D] -> uint8 [rows]"""
     _dev(enc_out)
     rows, d = enc_out.shape
+    assert enc_out.is_contiguous()
     out = torch.empty((rows,), dtype=torch.uint8, device=enc_out.device)
     _launch("dh_enc_key_mask", _ptr(enc_out), _ptr(out), rows, d, _dt(enc_out), _stream())
     return out
