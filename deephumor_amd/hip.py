@@ -169,6 +169,15 @@ def _dt(t):
 # ------------------------------------------------------------------------------------------------
 # thin tensor-level wrappers (shape checks live here; the library only sees pointers and sizes)
 # ------------------------------------------------------------------------------------------------
+def _out(out, shape, dtype, device):
+    """``out`` as given (shape, dtype and contiguity asserted) or a fresh tensor."""
+    if out is None:
+        return torch.empty(shape, dtype=dtype, device=device)
+    _dev(out)
+    assert tuple(out.shape) == tuple(shape) and out.dtype == dtype and out.is_contiguous(), (tuple(out.shape), out.dtype, shape, dtype)
+    return out
+
+
 def conv2d_bn_act(x, w, scale, shift, residual=None, relu=True, stride=1, pad=0, out=None):
     _dev(x, w, scale, shift, residual)
     n, cin, h, wd = x.shape
@@ -183,14 +192,14 @@ def conv2d_bn_act(x, w, scale, shift, residual=None, relu=True, stride=1, pad=0,
     return out
 
 
-def stem_conv_nhwc(x, w, scale, shift, stride=2, pad=3, relu=True, out_dtype=torch.bfloat16):
+def stem_conv_nhwc(x, w, scale, shift, stride=2, pad=3, relu=True, out_dtype=torch.bfloat16, out=None):
     """x NCHW fp32 image, w fp32 [Cout,Cin,KS,KS] -> channels-last bf16 / fp16 [N,Ho,Wo,Cout]."""
     _dev(x, w, scale, shift)
     n, cin, h, wd = x.shape
     cout, _, ks, _ = w.shape
     assert x.dtype == torch.float32 and w.dtype == torch.float32 and x.is_contiguous() and w.is_contiguous()
     ho, wo = (h + 2 * pad - ks) // stride + 1, (wd + 2 * pad - ks) // stride + 1
-    out = torch.empty((n, ho, wo, cout), dtype=out_dtype, device=x.device)
+    out = _out(out, (n, ho, wo, cout), out_dtype, x.device)
     _launch("dh_stem_conv_nhwc", _ptr(x), _ptr(w), _ptr(scale), _ptr(shift), _ptr(out), n, cin, h, wd, cout, ks,
             stride, pad, int(relu), _dt(out), _stream())
     return out
@@ -494,27 +503,27 @@ def attn_cross_prefill_packed(q, kp, vt, keymask, n_img, n_pos, s, d, n_heads, s
     return out
 
 
-def conv2d_nhwc_bn_act(x, w, scale, shift, residual=None, relu=True, stride=1, pad=0):
+def conv2d_nhwc_bn_act(x, w, scale, shift, residual=None, relu=True, stride=1, pad=0, out=None):
     """Channels-last bf16 convolution: x [N,H,W,Cin], w [Cout,KS,KS,Cin] -> [N,Ho,Wo,Cout]."""
     _dev(x, w, scale, shift, residual)
     n, h, wd, cin = x.shape
     cout, ks, ks2, cin2 = w.shape
     assert cin == cin2 and ks == ks2 and x.is_contiguous() and w.is_contiguous()
     ho, wo = (h + 2 * pad - ks) // stride + 1, (wd + 2 * pad - ks) // stride + 1
-    out = torch.empty((n, ho, wo, cout), dtype=x.dtype, device=x.device)
+    out = _out(out, (n, ho, wo, cout), x.dtype, x.device)
     _launch("dh_conv2d_nhwc_bn_act", _ptr(x), _ptr(w), _ptr(scale), _ptr(shift), _ptr(residual), _ptr(out),
             n, h, wd, cin, cout, ks, stride, pad, int(relu), _dt(x), _stream(), tag=f"{ks}x{ks}")
     return out
 
 
-def conv2d_nhwc_bn_relu_maxpool(x, w, scale, shift, stride=2, pad=3):
+def conv2d_nhwc_bn_relu_maxpool(x, w, scale, shift, stride=2, pad=3, out=None):
     """The ResNet stem in one launch: x [N,H,W,Cin] 16-bit (Cin % 8 == 0), w [Cout,KS,KS,Cin] -> pooled [N,Ho/2,Wo/2,Cout]."""
     _dev(x, w, scale, shift)
     n, h, wd, cin = x.shape
     cout, ks, _, cin2 = w.shape
     assert cin == cin2 and x.is_contiguous() and w.is_contiguous()
     ho, wo = (h + 2 * pad - ks) // stride + 1, (wd + 2 * pad - ks) // stride + 1
-    out = torch.empty((n, ho // 2, wo // 2, cout), dtype=x.dtype, device=x.device)
+    out = _out(out, (n, ho // 2, wo // 2, cout), x.dtype, x.device)
     _launch("dh_conv2d_nhwc_bn_relu_maxpool", _ptr(x), _ptr(w), _ptr(scale), _ptr(shift), _ptr(out), n, h, wd, cin, cout, ks,
             stride, pad, _dt(x), _stream())
     return out
@@ -1250,14 +1259,14 @@ def transformer_decode_position(model, scratch, start_emb, tokens, src, n_img, r
             group_max.stride(0) if group_max is not None else 0, _stream())
 
 
-def conv1x1_dual_nhwc(y, x, w_cat, shift, stride, relu=True):
+def conv1x1_dual_nhwc(y, x, w_cat, shift, stride, relu=True, out=None):
     """relu(y (*) W3' + x[strided] (*) Wd' + shift): conv3 + downsample of a stage's first bottleneck as one GEMM
     (bf16, NHWC; ``w_cat`` [Cout, C1 + C2] has the BatchNorm scales folded in)."""
     _dev(y, x, w_cat, shift)
     n, ho, wo, c1 = y.shape
     _, h, w_, c2 = x.shape
     cout = w_cat.shape[0]
-    out = torch.empty((n, ho, wo, cout), dtype=y.dtype, device=y.device)
+    out = _out(out, (n, ho, wo, cout), y.dtype, y.device)
     _launch("dh_conv1x1_dual_nhwc", _ptr(y), _ptr(x), _ptr(w_cat), _ptr(shift), _ptr(out), n, ho, wo, c1, h, w_, c2, stride,
             cout, int(relu), _dt(y), _stream())
     return out
