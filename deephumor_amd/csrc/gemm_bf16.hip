@@ -1460,9 +1460,28 @@ __global__ __launch_bounds__(256) void lse_combine_kernel(const float* __restric
     }
 }
 
+int dh_f32x_vocab_lse(const float* A, int lda, const void* w_planes, int Kp, const float* bias, const int64_t* targets, float* group_max,
+                      float* group_sum, float* target_logit, int gm_ld, int M, int V, int K, hipStream_t s);      // (gemm_f32x.hip)
+
 extern "C" int dh_vocab_logprob(const void* A, int lda, const void* W, int ldw, const float* bias, const int64_t* targets,
                                 float* logp, float* group_max, float* group_sum, float* target_logit, int gm_ld, int M, int V,
                                 int K, int dtype, void* stream) {
+    if (dtype == DH_F32) {
+        // fp32 hidden states x the dh_split_f32x planes [2][V][ldw] of the classifier weight: the f32x tile in its log-sum-exp mode
+        // (gemm_f32x.hip), then the same combine
+        DH_REQUIRE(A && W && targets && logp && group_max && group_sum && target_logit && M > 0 && V > 0 && K > 0);
+        DH_REQUIRE(gm_ld >= 2 * dh_cdiv(V, 128) && (K % 64) == 0 && K >= 128 && (lda % 4) == 0 && (ldw % 32) == 0 && lda >= K && ldw >= K);
+        DH_REQUIRE(((uintptr_t)A % 16) == 0 && ((uintptr_t)W % 16) == 0 && (long long)dh_cdiv(M, 128) * dh_cdiv(V, 128) < (1ll << 31));
+        dh_prof_set_tag("logprob");
+        dh_prof_set_dims(M, V, K);
+        DhProfScope prof("dh_linear_f32x", 2.0 * M * V * K, 4.0 * ((double)M * K + (double)V * K), stream);
+        const int rc = dh_f32x_vocab_lse((const float*)A, lda, W, ldw, bias, targets, group_max, group_sum, target_logit, gm_ld, M, V, K,
+                                         (hipStream_t)stream);
+        if (rc != DH_OK) return rc;
+        hipLaunchKernelGGL(lse_combine_kernel, dim3(dh_cdiv(M, 4)), dim3(256), 0, (hipStream_t)stream, group_max, group_sum, gm_ld,
+                           2 * dh_cdiv(V, 128), target_logit, targets, V, logp, M);
+        DH_LAUNCH_CHECK();
+    }
     if (!DH_IS_16BIT(dtype)) return DH_ERR_UNSUPPORTED;
     DH_REQUIRE(A && W && targets && logp && group_max && group_sum && target_logit && M > 0 && V > 0 && K > 0);
     DH_REQUIRE(gm_ld >= 2 * dh_cdiv(V, 128) && (K % 64) == 0 && K >= 128 && (lda % 8) == 0 && (ldw % 8) == 0 && lda >= K && ldw >= K);

@@ -37,6 +37,7 @@ struct F32xParams {
     int tiles_m, tiles_n, n_fast;                      // n_fast: consecutive workgroups walk the N tiles of one M tile (small weights)
     unsigned* range_flag;                              // sticky per-stream word: an activation outside the fp16 range was split (see below)
     int diag;
+    const int64_t* targets; float* gmax; float* gsum; float* tgt_logit; int gmax_ld;      // MODE 3 (log-sum-exp partials instead of C)
 };
 
 // Range guard of the ACTIVATIONS: the weights' range is checked when a plan is built, but an activation with |x| >= 65504
@@ -117,8 +118,55 @@ __device__ __forceinline__ void epilogue(const F32xParams& p, const dh_f32x4 (&a
     }
 }
 
+// MODE 3 (teacher-forced scoring, dh_vocab_logprob(DH_F32)): no C.  A wave's 64 x 64 quarter of the 128 x 128 tile is one 64-column group
+// g = n / 64 of 64 rows: per (row, group) the maximum of the logits main + 2^-11 * correction + bias over the group's real columns
+// n < N and the sum of exp(logit - maximum) -- the partials lse_combine_kernel (gemm_bf16.hip) folds in group order -- plus the
+// target's logit from the wave whose group holds it.  A row's 16 logits of this lane in (j, r) order, then the four lanes of the row
+// by two shuffles: one order for every M and every place of the row in the batch, no atomics.
+template <int TM, int TN>
+__device__ __forceinline__ void lse_epilogue(const F32xParams& p, const dh_f32x4 (&acc)[TN][TM], const dh_f32x4 (&cor)[TN][TM], int mw, int nw,
+                                             int l15, int lq) {
+    static_assert(TN == 4, "a wave owns one 64-column group");
+    float bi[TN][4];
+#pragma unroll
+    for (int j = 0; j < TN; ++j)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) bi[j][r] = p.bias ? p.bias[min(nw + 16 * j + 4 * lq + r, p.N - 1)] : 0.f;
+#pragma unroll
+    for (int i = 0; i < TM; ++i) {
+        const int m = mw + 16 * i + l15;
+        const int64_t tcol = m < p.M ? p.targets[m] - (int64_t)nw : -1;
+        float v[TN][4];
+        float mxv = -INFINITY;
+#pragma unroll
+        for (int j = 0; j < TN; ++j)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const int c = 16 * j + 4 * lq + r;
+                v[j][r] = nw + c < p.N ? fmaf(cor[j][i][r], kLoInv, acc[j][i][r]) + bi[j][r] : -INFINITY;
+                mxv = fmaxf(mxv, v[j][r]);
+                if (tcol == c) p.tgt_logit[m] = v[j][r];
+            }
+        mxv = fmaxf(mxv, __shfl_xor(mxv, 16, 64));
+        mxv = fmaxf(mxv, __shfl_xor(mxv, 32, 64));
+        float se = 0.f;
+        if (mxv > -INFINITY) {
+#pragma unroll
+            for (int j = 0; j < TN; ++j)
+#pragma unroll
+                for (int r = 0; r < 4; ++r) se += expf(v[j][r] - mxv);       // exp(-inf) = 0 for columns past N
+        }
+        se += __shfl_xor(se, 16, 64);
+        se += __shfl_xor(se, 32, 64);
+        if (lq == 0 && m < p.M) {
+            p.gmax[(size_t)m * p.gmax_ld + (nw >> 6)] = mxv;
+            p.gsum[(size_t)m * p.gmax_ld + (nw >> 6)] = se;
+        }
+    }
+}
+
 // MODE 0: dense A; 1: convolution with Cin % 32 == 0 (a 32-k slab lies inside one filter tap: the tap is wave-uniform);
-// 2: convolution, any Cin % 4 == 0 (the stem: per-lane tap decode)
+// 2: convolution, any Cin % 4 == 0 (the stem: per-lane tap decode); 3: dense A, lse_epilogue (128 x 128 only)
 // Tiles: 128 x 128 (the large layers), 128 x 64 (Cout = 64: stage 1 and the stem), 64 x 64 (the decode-position linears, whose
 // 1,280 x 512 outputs are 40 tiles of 128 x 128 on 256 CUs).  Four waves, 2 x 2 over the tile.
 template <int MODE, int BM, int BN>
@@ -155,7 +203,7 @@ __global__ __launch_bounds__(256, BM * BN >= 128 * 128 ? 2 : 3) void gemm_f32x_k
         a_ok[it] = m < p.M;
         const int mm = a_ok[it] ? m : 0;
         a_ih0[it] = a_iw0[it] = 0;
-        if (MODE == 0) {
+        if (MODE == 0 || MODE == 3) {
             a_ptr[it] = p.A + (size_t)mm * p.lda + a_kc * 4;
         } else {
             const int hw = p.Ho * p.Wo, n = mm / hw, r = mm - n * hw, oh = r / p.Wo, ow = r - oh * p.Wo;
@@ -169,7 +217,7 @@ __global__ __launch_bounds__(256, BM * BN >= 128 * 128 ? 2 : 3) void gemm_f32x_k
 #pragma unroll
         for (int it = 0; it < A_IT; ++it) {
             const float* src = nullptr;
-            if (MODE == 0) {
+            if (MODE == 0 || MODE == 3) {
                 if (a_ok[it] && k0 + a_kc * 4 < p.K) src = a_ptr[it] + k0;
             } else if (MODE == 1) {
                 if (a_ok[it] && (unsigned)(a_ih0[it] + st_kh) < (unsigned)p.H && (unsigned)(a_iw0[it] + st_kw) < (unsigned)p.Wd)
@@ -277,7 +325,8 @@ __global__ __launch_bounds__(256, BM * BN >= 128 * 128 ? 2 : 3) void gemm_f32x_k
     }
 
     report(p, amax);
-    epilogue<TM, TN>(p, acc, cor, m0 + wm0, n0 + wn0, l15, lq);
+    if constexpr (MODE == 3) lse_epilogue<TM, TN>(p, acc, cor, m0 + wm0, n0 + wn0, l15, lq);
+    else epilogue<TM, TN>(p, acc, cor, m0 + wm0, n0 + wn0, l15, lq);
 }
 
 __device__ uint4 dh_f32x_zero_page[2];              // zero-initialised: source of chunks outside M / K
@@ -525,6 +574,22 @@ extern "C" int dh_linear_f32x(const float* A, int lda, const void* w_planes, int
     dh_prof_set_dims(M, N, K);
     DhProfScope prof("dh_linear_f32x", 2.0 * M * N * K, 4.0 * ((double)M * K + (double)N * K + (double)M * N), stream);
     return launch(p, 0, (hipStream_t)stream);
+}
+
+// The classifier of dh_vocab_logprob(DH_F32) (gemm_bf16.hip, which validates the arguments and then runs lse_combine_kernel): the
+// 128 x 128 tile in MODE 3 for EVERY M -- a row's partials then do not depend on the batch it stands in.
+int dh_f32x_vocab_lse(const float* A, int lda, const void* w_planes, int Kp, const float* bias, const int64_t* targets, float* group_max,
+                      float* group_sum, float* target_logit, int gm_ld, int M, int V, int K, hipStream_t s) {
+    F32xParams p{};
+    p.A = A; p.lda = lda; p.Wp = (const uint16_t*)w_planes; p.Kp = Kp; p.plane = (size_t)V * Kp; p.bias = bias;
+    p.targets = targets; p.gmax = group_max; p.gsum = group_sum; p.tgt_logit = target_logit; p.gmax_ld = gm_ld;
+    p.M = M; p.N = V; p.K = K;
+    p.range_flag = range_flag_of(s);
+    if (!p.range_flag) return DH_ERR_LAUNCH;
+    p.n_fast = (double)V * Kp * 4.0 <= 4.0 * 1048576.0;
+    p.tiles_m = dh_cdiv(M, 128); p.tiles_n = dh_cdiv(V, 128);
+    hipLaunchKernelGGL((gemm_f32x_kernel<3, 128, 128>), dim3((unsigned)(p.tiles_m * p.tiles_n)), dim3(256), 0, s, p);
+    return hipGetLastError() == hipSuccess ? DH_OK : DH_ERR_LAUNCH;
 }
 
 extern "C" int dh_conv2d_nhwc_f32x(const float* x, const void* w_planes, int Kp, const float* scale, const float* shift, const float* residual,

@@ -4,9 +4,14 @@ The corpus has 300 template images and 900,000 captions (README.md:26,37): the R
 depends on the template only, so it is computed ONCE per distinct template and gathered per caption;
 the decoders then run their teacher-forced ``forward`` (same incremental engine as ``generate``) and the
 perplexity kernels score every caption (call shape of trainer.py:63-81)."""
+from typing import NamedTuple, Optional
+
 import torch
 
 from .. import hip
+from ..data import SPECIAL_TOKENS
+from ..models._f32x_guard import f32x_guarded
+from ..models.beam import check_ids, check_return_attention
 from .metrics import sequence_perplexity, sequence_perplexity_from_hidden
 
 
@@ -56,3 +61,160 @@ def score_captions(model, template_images, template_index, captions, lengths, la
             logits = logits[:, :tgt.shape[1]].contiguous()
             out.append(sequence_perplexity(logits, tgt.contiguous(), lengths[lo:hi], pad_index))
         return torch.cat(out)
+
+
+class CaptionScores(NamedTuple):
+    """What ``explain_captions`` returns for ``n`` captions of ``L`` positions.  Device tensors:
+
+    ``logprobs`` fp32 ``[n, L]``      ``log_softmax(logits[i, p])[captions[i, p]]``, exactly 0.0 where ``captions[i, p]`` is the pad;
+    ``perplexity`` fp32 ``[n]``       ``exp(-sum_p logprobs[i, p] / lengths[i])`` (``dh_seq_perplexity``), ``score_captions``' value;
+    ``attention`` fp32 ``[n, L, S]``  or None: where position ``p`` looked -- the head-mean encoder-attention softmax of the last
+                                      decoder layer over the ``S`` image patches; every real row sums to 1, pad rows are exactly 0."""
+    logprobs: torch.Tensor
+    perplexity: torch.Tensor
+    attention: Optional[torch.Tensor] = None
+
+    def map(self, fn):
+        """``CaptionScores`` of ``fn(field)`` for every field that is there (``clone``, ``cpu`` ...)."""
+        return CaptionScores(*(None if t is None else fn(t) for t in self))
+
+    @staticmethod
+    def cat(parts):
+        """The captions of several results, in order."""
+        parts = list(parts)
+        return CaptionScores(*(None if ts[0] is None else torch.cat(ts, 0) for ts in zip(*parts)))
+
+
+def _check_explain_args(model, template_images, template_index, captions, lengths, batch_size, pad_index, return_attention):
+    check_return_attention(return_attention, model)
+    if isinstance(batch_size, bool) or not isinstance(batch_size, int) or batch_size < 1:
+        raise ValueError(f"batch_size must be an int >= 1, got {batch_size!r}")
+    if isinstance(pad_index, bool) or not isinstance(pad_index, int):
+        raise TypeError(f"pad_index must be an int, not {type(pad_index).__name__}")
+    if not torch.is_tensor(captions) or captions.dim() != 2 or captions.dtype != torch.int64 or captions.shape[0] < 1 or captions.shape[1] < 1:
+        raise ValueError("captions must be an int64 tensor [n, L] with n >= 1 and L >= 1 (tokens + <eos>, padded with pad_index)")
+    n = captions.shape[0]
+    lengths = torch.as_tensor(lengths)
+    if tuple(lengths.shape) != (n,) or lengths.dtype.is_floating_point or lengths.dtype == torch.bool:
+        raise ValueError(f"lengths must be an integer tensor of shape [{n}] (one per caption), got {tuple(lengths.shape)} {lengths.dtype}")
+    if int(lengths.min()) < 1:
+        raise ValueError("lengths must be >= 1 (a caption holds at least its <eos>)")
+    template_index = torch.as_tensor(template_index)
+    if tuple(template_index.shape) != (n,) or template_index.dtype.is_floating_point or template_index.dtype == torch.bool:
+        raise ValueError(f"template_index must be an integer tensor of shape [{n}] (one per caption), got {tuple(template_index.shape)}")
+    check_ids(template_index, template_images.shape[0])
+    check_ids(captions, model.decoder.classifier.out_features)                # (nn.Embedding's IndexError)
+    return template_index.long(), lengths.long()
+
+
+def explain_captions(model, template_images, template_index, captions, lengths, labels=None, batch_size=256, pad_index=0,
+                     return_attention=False):
+    """``score_captions`` with the per-token values kept: for GIVEN captions (a corpus meme, a candidate being ranked) every token's
+    model log-probability and, with ``return_attention=True``, the image map of every position -- what ``generate_batch(...,
+    return_logprobs=True, return_attention=True)`` returns for the captions it writes.  Inputs and position convention are
+    ``score_captions``': output position ``p`` predicts ``captions[:, p]``, position 0 is the image slot.  -> ``CaptionScores``.
+
+    Routes of the log-probs, per batch of ``batch_size`` captions:
+      16-bit model        ``score_captions``' launches (hidden states -> ``dh_vocab_logprob`` -> ``dh_seq_perplexity``): ``perplexity`` is
+                          ``score_captions``' bit for bit;
+      fp32, ``f32_split``  hidden states -> ``dh_vocab_logprob(DH_F32)`` on the plan's split classifier planes: no ``[rows, V]`` logits in
+                          memory.  The stream's overflow word is read once per batch; a flagged batch (an activation outside the fp16
+                          range) is repeated on the logits route with the option off, as ``f32x_guarded`` does;
+      anything else       (option off, classifier width outside ``K % 64 == 0, K >= 128``, ``pad_index == 1``) the logits route:
+                          ``forward`` then ``dh_token_logprob`` -- ``score_captions``' fp32 launches.
+    A caption's values do not depend on ``batch_size`` or on the captions next to it.
+
+    ``return_attention`` (a plain bool): only the kinds with encoder attention have maps (``TypeError`` otherwise, ``NotImplementedError``
+    for a ``pad_index == 1`` decoder -- ``check_return_attention``).  ``S`` is the encoder's patch count, 49 at 224 x 224: the zero rows
+    the reference pads the encoder output with are masked keys of weight exactly 0 and are not returned (a ``pad_index >= 2`` decoder
+    masks nothing: once ``L`` exceeds the patch count its padded rows are real keys and ``S`` grows to ``L``).  Arguments are validated
+    before the encoder runs."""
+    template_index, lengths = _check_explain_args(model, template_images, template_index, captions, lengths, batch_size, pad_index,
+                                                  return_attention)
+    enc = model.encoder
+    dec = model.decoder
+    lstm = hasattr(dec, "lstm")
+    with torch.no_grad():
+        feats = enc(template_images, labels) if labels is not None else enc(template_images)
+        spatial = None
+        if isinstance(feats, tuple):
+            feats, spatial = feats
+        dev = feats.device
+        width = dec.classifier.in_features
+        fused_ok = width % 64 == 0 and width >= 128                              # dh_vocab_logprob's contract
+        parts = []
+        for lo in range(0, captions.shape[0], batch_size):
+            hi = min(lo + batch_size, captions.shape[0])
+            idx = template_index[lo:hi].to(dev)
+            emb = feats.index_select(0, idx)
+            sp = None if spatial is None else spatial.index_select(0, idx)
+            tgt = captions[lo:hi].to(dev).contiguous()
+            inp = tgt[:, :-1]
+            bs, l = tgt.shape
+            lens = lengths[lo:hi].to(dev)
+
+            def hidden_route(split=False):
+                attn = None
+                if lstm:
+                    hidden, _, _ = dec.hidden_states(emb, inp, None)
+                elif return_attention:
+                    hidden, attn = dec._forward(inp, sp, emb, num_positions=l, return_hidden=True, return_attention=True)
+                else:
+                    hidden = dec._forward(inp, sp, emb, num_positions=l, return_hidden=True)
+                plan = dec._get_plan()
+                hidden = hidden[:, :l].contiguous()
+                w_x = plan["cls_w_x"] if split else None
+                logp = hip.vocab_logprob(hidden.reshape(bs * l, width), plan["cls_w"], plan["cls_b"], tgt.reshape(-1), w_x=w_x)
+                return logp.view(bs, l), attn
+
+            def logits_route():
+                attn = None
+                if return_attention:
+                    logits, attn = f32x_guarded(lambda d: d._forward(inp, sp, emb, num_positions=l, return_attention=True))(dec)
+                elif spatial is not None:
+                    logits = dec(inp, enc_out=sp, start_emb=emb, num_positions=l)
+                elif lstm:
+                    logits = dec(emb, inp, None)
+                else:
+                    logits = dec(inp, start_emb=emb)
+                logits = logits[:, :l].contiguous()
+                return hip.token_logprob(logits.reshape(bs * l, -1), tgt.reshape(-1)).view(bs, l), attn
+
+            if feats.dtype in hip.HALF_DTYPES and fused_ok:
+                logp, attn = hidden_route()
+            elif (feats.dtype == torch.float32 and fused_ok and hip.option("f32_split") and getattr(dec, "pad_index", 0) != 1
+                  and not torch.cuda.is_current_stream_capturing() and "cls_w_x" in dec._get_plan()):
+                logp, attn = hidden_route(split=True)
+                with torch.cuda.device(dev):
+                    over = hip.f32x_take_overflow(dev)
+                if over:                                                         # an activation left the fp16 range: exact kernels
+                    with hip.option_scope(f32_split=0):
+                        logp, attn = logits_route()
+            else:
+                logp, attn = logits_route()
+            pad = tgt == pad_index
+            pp = hip.seq_perplexity(logp, tgt, lens, pad_index)
+            if attn is not None:
+                attn = attn[:, :l].masked_fill(pad[..., None], 0.0)
+            parts.append(CaptionScores(logp.masked_fill(pad, 0.0), pp, attn))
+        return CaptionScores.cat(parts)
+
+
+def token_scores(captions, scores, vocab):
+    """The readable form of ``explain_captions``' log-probs, as ``beams_to_texts`` is for beams: for every caption a list of
+    ``(token text, log-prob)`` up to and including its ``<eos>`` (the whole row without one; the pad never appears -- a row ends at its
+    first pad).  ``scores``: the ``CaptionScores`` or its ``logprobs [n, L]``."""
+    lp = scores.logprobs if isinstance(scores, CaptionScores) else scores
+    toks, lp = captions.detach().cpu().tolist(), lp.detach().cpu().tolist()
+    eos, pad = vocab.stoi[SPECIAL_TOKENS['EOS']], vocab.stoi[SPECIAL_TOKENS['PAD']]
+    out = []
+    for row, vals in zip(toks, lp):
+        items = []
+        for tok, v in zip(row, vals):
+            if tok == pad:
+                break
+            items.append((vocab.itos[tok], v))
+            if tok == eos:
+                break
+        out.append(items)
+    return out

@@ -887,9 +887,32 @@ def vocab_logits_wreg(a, w_packed, bias_padded, v, logits, group_max):
             logits.stride(0) if logits is not None else 0, _ptr(group_max), group_max.stride(0), m, v, k, _dt(a), _stream())
 
 
-def vocab_logprob(a, w, bias, targets):
+def vocab_logprob(a, w, bias, targets, w_x=None):
     """bf16 a [M,K], w [V,K], int64 targets [M] -> fp32 log_softmax(a @ w.T + bias)[targets] [M]; the [M,V] logits are
-    never written (per-group log-sum-exp partials in the classifier GEMM's epilogue)."""
+    never written (per-group log-sum-exp partials in the classifier GEMM's epilogue).  Targets outside ``[0, V)`` give 0.0.
+
+    fp32 ``a`` with ``w_x = split_f32x(w)`` (``[2, V, Kp]`` fp16; ``w`` itself is then not read and may be None): the same on the
+    split-operand tile of ``linear_f32x`` in its log-sum-exp mode -- fp32-class values, one kernel for every ``M`` (a row's value does
+    not depend on the batch), and an activation with ``|x| >= 65504`` sets the stream's overflow word (``f32x_take_overflow``).  Both
+    forms take ``K % 64 == 0 and K >= 128``; the fp32 form also a row stride of ``a`` that is a multiple of 4 floats and 16-byte
+    aligned rows (else ``a`` is copied)."""
+    if a.dtype == torch.float32:
+        if w_x is None:
+            raise RuntimeError("vocab_logprob: fp32 hidden states need w_x = split_f32x(w) (the fused classifier runs on the 16-bit "
+                               "matrix cores); without the planes use linear() and token_logprob()")
+        _dev(a, w_x, bias, targets)
+        m, k = a.shape
+        two, v, kp = w_x.shape
+        assert two == 2 and w_x.dtype == torch.float16 and w_x.is_contiguous() and kp == (k + 31) // 32 * 32 and a.stride(1) == 1
+        if a.stride(0) % 4 or a.data_ptr() % 16:
+            a = a.contiguous()
+        ng = n_groups(v)
+        scratch = torch.empty((2, m, ng), dtype=torch.float32, device=a.device)
+        tgt = torch.empty((m,), dtype=torch.float32, device=a.device)
+        logp = torch.empty((m,), dtype=torch.float32, device=a.device)
+        _launch("dh_vocab_logprob", _ptr(a), a.stride(0), _ptr(w_x), kp, _ptr(bias), _ptr(targets.contiguous()), _ptr(logp),
+                _ptr(scratch[0]), _ptr(scratch[1]), _ptr(tgt), ng, m, v, k, F32, _stream())
+        return logp
     _dev(a, w, bias, targets)
     m, k = a.shape
     v = w.shape[0]

@@ -21,7 +21,7 @@ from torch import nn
 
 from .. import hip
 from ._f32x_guard import f32x_guarded
-from .beam import BeamCaptions, DecodeSession, DecodeSettings, call_logits_hook, check_ids, classifier_must_be_finite, decode_with_overflow_retry, make_noise_source, run_interleaved, session_inputs
+from .beam import BeamCaptions, DecodeSession, DecodeSettings, call_logits_hook, check_ids, check_return_attention, classifier_must_be_finite, decode_with_overflow_retry, make_noise_source, run_interleaved, session_inputs
 from .encoders import _Planned
 
 
@@ -356,8 +356,15 @@ class _IncrementalDecoder(_Planned, nn.Module):
                                         attn_w=attn_w, attn_layer=len(self.layers) - 1)
         return x_out if x_out is not None else sc["x"]
 
-    def _forward(self, x, enc_out, start_emb, num_positions=None, return_hidden=False):
+    def _forward(self, x, enc_out, start_emb, num_positions=None, return_hidden=False, return_attention=False):
+        """``return_attention`` (internal; ``experiments.explain_captions``): the pair ``(result, attention)`` -- fp32
+        ``[bs, seq, S]``, the last layer's head-mean encoder-attention softmax of every teacher-forced position, from one
+        ``dh_attn_cross_weights`` launch behind that layer's ``fc_q`` (position by position: ``_decode_position``'s ``attn_w``)."""
         check_ids(x, self.tok_embedding.num_embeddings)                               # (nn.Embedding's IndexError)
+        if return_attention:
+            check_return_attention(True, self)
+            if start_emb is None or enc_out is None:
+                raise TypeError("return_attention needs the start embedding and the encoder output")
         if start_emb is None or self.pad_index == 1:
             return self._forward_modules(x, enc_out, start_emb, return_hidden=return_hidden)
         self._check_mode()
@@ -374,18 +381,22 @@ class _IncrementalDecoder(_Planned, nn.Module):
         ncopy = min(x.shape[1], tokens.shape[1])
         tokens[:, :ncopy] = x[:, :ncopy].to(torch.int32)
         if self._prefill_ok(plan, seq):
-            return self._forward_prefill(plan, tokens, enc_out, start_emb.to(plan["dtype"]).contiguous(), bs, seq, return_hidden)
+            return self._forward_prefill(plan, tokens, enc_out, start_emb.to(plan["dtype"]).contiguous(), bs, seq, return_hidden,
+                                         return_attention)
         helper_src = (torch.arange(bs, dtype=torch.int32, device=dev))[:, None].expand(bs, seq).contiguous()
         run = self._Run(self, plan, bs, 1, seq, enc_out, dev)
         hs = torch.empty((bs, seq, self.hid_dim), device=dev, dtype=plan["dtype"])
         xt = torch.empty((bs, self.hid_dim), device=dev, dtype=plan["dtype"])
+        attn_w = torch.empty((seq, bs, run.s), device=dev, dtype=torch.float32) if return_attention else None
         for t in range(seq):
-            self._decode_position(plan, run, t, bs, 1, 1, tokens, helper_src, start_emb.to(plan["dtype"]).contiguous(), x_out=xt)
+            self._decode_position(plan, run, t, bs, 1, 1, tokens, helper_src, start_emb.to(plan["dtype"]).contiguous(), x_out=xt,
+                                  attn_w=attn_w)
             hs[:, t, :].copy_(xt)
+        attn = (attn_w.permute(1, 0, 2).contiguous(),) if return_attention else ()
         if return_hidden:
-            return hs
+            return (hs,) + attn if attn else hs
         out = hip.linear(hs.view(bs * seq, self.hid_dim), plan["cls_w"], plan["cls_b"], out_dtype=torch.float32, tag="vocab", w_x=plan.get("cls_w_x"))
-        return out.view(bs, seq, -1)
+        return (out.view(bs, seq, -1),) + attn if attn else out.view(bs, seq, -1)
 
     def _forward_modules(self, x, enc_out, start_emb=None, return_hidden=False):
         """The reference's own formulation of ``forward`` on the module-API layers: pad ``x`` / ``enc_out`` to a common length
@@ -458,7 +469,7 @@ class _IncrementalDecoder(_Planned, nn.Module):
         limit = 56 if plan["dtype"] in hip.HALF_DTYPES else 40
         return self.hid_dim == 64 * self.n_heads and seq <= limit
 
-    def _forward_prefill(self, plan, tokens, enc_out, start_emb, bs, seq, return_hidden=False):
+    def _forward_prefill(self, plan, tokens, enc_out, start_emb, bs, seq, return_hidden=False, return_attention=False):
         """Teacher-forced forward in prefill form: rows are sequence-major (row n*seq + t); per layer one QKV GEMM
         over all bs*seq rows, one causal self-attention launch, projection + residual LayerNorm, (cross-attention in
         chunks of positions), FFN -- ~12 launches per layer instead of ~11 per layer AND position."""
@@ -469,9 +480,16 @@ class _IncrementalDecoder(_Planned, nn.Module):
         if enc_out is not None:
             flat, s_enc, keymask = self._enc_for_cross(enc_out.to(dt), seq)            # transformers.py:450-452, 480-481
         packed_ok = dt in hip.HALF_DTYPES and 0 < s_enc <= 64
+        last = plan["layers"][-1]
+        attn = []                                          # return_attention: [bs, seq, s_enc] fp32 of the last layer
 
         def cross(q, L):
             kv = hip.linear(flat, L["wkv"], L["bkv"], tag="enc_kv", w_x=L.get("wkv_x"))
+            if return_attention and L is last:
+                # the side launch of generate_batch(return_attention=True), all positions of an image at once: q rows n * seq + t (natural
+                # layout on every chain) against the unpacked K; seq <= 56 rows per image.  The attention output below is not touched.
+                w = torch.empty((bs, seq, s_enc), dtype=torch.float32, device=q.device)
+                attn.append(hip.attn_cross_weights(q, kv, keymask, w, bs, seq, 1, s_enc, d, nh, L["ea_scale"]))
             if packed_ok:                                  # matrix-core cross-attention, 16 positions per launch
                 # (dperm: the head-dim slot order of the decode chain's fused fc_q + attention launch, so that teacher-forced
                 # logits and incremental decoding sum in the same order)
@@ -505,9 +523,9 @@ class _IncrementalDecoder(_Planned, nn.Module):
                 pend = L["ln3"]
             x = hip.add_layernorm(x, None, pend[0], pend[1], eps=pend[2])
             if return_hidden:
-                return x.view(bs, seq, d)
+                return (x.view(bs, seq, d), attn[0]) if return_attention else x.view(bs, seq, d)
             out = hip.linear(x, plan["cls_w"], plan["cls_b"], out_dtype=torch.float32, tag="vocab", w_x=plan.get("cls_w_x"))
-            return out.view(bs, seq, -1)
+            return (out.view(bs, seq, -1), attn[0]) if return_attention else out.view(bs, seq, -1)
         for L in plan["layers"]:
             qkv = hip.linear(x, L["wqkv"], L["bqkv"], tag="qkv", w_x=L.get("wqkv_x"))
             att = hip.attn_self_prefill(qkv, tokens, bs, seq, d, nh, L["sa_scale"], self.pad_index)
@@ -522,9 +540,9 @@ class _IncrementalDecoder(_Planned, nn.Module):
             o = hip.linear(ff, L["w2"], L["b2"], tag="ffn", w_x=L.get("w2_x"))
             x = hip.add_layernorm(x, o, L["ln3"][0], L["ln3"][1], eps=L["ln3"][2])
         if return_hidden:
-            return x.view(bs, seq, d)
+            return (x.view(bs, seq, d), attn[0]) if return_attention else x.view(bs, seq, d)
         out = hip.linear(x, plan["cls_w"], plan["cls_b"], out_dtype=torch.float32, tag="vocab", w_x=plan.get("cls_w_x"))
-        return out.view(bs, seq, -1)
+        return (out.view(bs, seq, -1), attn[0]) if return_attention else out.view(bs, seq, -1)
 
     @staticmethod
     def _one(res):

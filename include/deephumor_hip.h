@@ -464,7 +464,12 @@ int dh_beam_row_sample_exact(const float* logits, int ldl, int V, int rows, int 
 
 /* Teacher-forced scoring without materialising the logits (bf16): logp[m] = log_softmax(A[m,:] W^T + bias)[targets[m]]
  * (metrics.py:4-9 via F.cross_entropy).  group_max / group_sum [M, gm_ld >= 2*ceil(V/128)] and target_logit [M] are
- * scratch.  targets outside [0, V) give logp = 0.  K % 64 == 0, K >= 128. */
+ * scratch.  targets outside [0, V) give logp = 0.  K % 64 == 0, K >= 128.
+ * dtype == DH_F32: A is fp32 [M, lda] (lda % 4 == 0, 16-byte aligned) and W holds the dh_split_f32x planes of the classifier weight,
+ * [2][V][ldw] fp16 with ldw = Kp (a multiple of 32, >= K); bias fp32; everything else as above, K % 64 == 0 and K >= 128 too.  The
+ * f32x tile (dh_linear_f32x) in a log-sum-exp mode: fp32-class values, no logits written, ONE kernel for every M -- a row's result
+ * does not depend on M or on its place in the batch -- fixed reduction order, no float atomics.  An activation with |x| >= 65504
+ * sets the stream's sticky overflow word (dh_f32x_take_overflow) like every other f32x kernel. */
 int dh_vocab_logprob(const void* A, int lda, const void* W, int ldw, const float* bias, const int64_t* targets, float* logp,
                      float* group_max, float* group_sum, float* target_logit, int gm_ld, int M, int V, int K, int dtype,
                      void* stream);
