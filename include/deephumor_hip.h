@@ -939,7 +939,8 @@ int dh_lstm_layer_fused(const void* x_rows, int ldx, int x_div, const void* emb,
 /* The same step with the gate weights stationary in registers (decode shapes: E + Hh = 768 or 1024, E % 64 == 0, Hh % 32 == 0):
  * a workgroup owns 128 gate rows x 80 activation rows, its waves load their weight fragments straight from L2 out of
  * w_packed = dh_pack_mfma_fragments(w_il [4 Hh, E + Hh]); only the activation block crosses LDS.  Same arguments and results
- * (bit-identical) as dh_lstm_layer_fused. */
+ * (bit-identical) as dh_lstm_layer_fused; the outputs are stored 16 bytes per lane: h_next, c_next and h_out 16-byte aligned,
+ * ld_out % 8 == 0. */
 int dh_lstm_layer_wreg_supported(int E, int Hh);
 int dh_lstm_layer_wreg(const void* x_rows, int ldx, int x_div, const void* emb, const int32_t* tokens, int tok_ld,
                        int tok_pos, const void* h_prev, const float* c_prev, const int32_t* hparent, void* h_next,
