@@ -668,20 +668,16 @@ extern "C" int dh_attn_self_prefill(const void* qkv, const int32_t* tokens, int 
     DH_LAUNCH_CHECK();
 }
 
-// Cross-attention for sequence-major prefill rows (row n * n_pos + t): the decode kernels take at most
-// DH_BEAM_MAX_BEAMS query rows per image and launch, so the positions go in chunks of that many.
+// Cross-attention for sequence-major prefill rows (row n * n_pos + t): ONE launch of the decode kernels, whose blockIdx.z row
+// blocks (DH_ATTN_ROW) take the positions DH_ATTN_RPB at a time.  n_pos is any row count per image: a caller whose image serves
+// several sequences (experiments.score_pairs: n_pos = captions x positions) passes them all.
 extern "C" int dh_attn_cross_prefill(const void* q, int ldq, const void* kv, const uint8_t* keymask, void* out, int n_img,
                                      int n_pos, int S, int D, int n_heads, float scale, int dtype, void* stream) {
     DH_REQUIRE(q && kv && keymask && out && n_img > 0 && n_pos > 0 && S > 0 && n_heads > 0 && D % n_heads == 0);
-    DH_REQUIRE(((D / n_heads) % 8) == 0 && ldq >= D);
+    DH_REQUIRE(((D / n_heads) % 8) == 0 && ldq >= D && dh_cdiv(n_pos, DH_ATTN_RPB) <= 65535 && n_heads <= 65535);
     const size_t esz = dtype == DH_F32 ? 4 : 2;
     DhProfScope prof("dh_attn_cross_prefill", 4.0 * n_img * n_pos * S * D, (double)esz * n_img * (S * 2.0 * D + n_pos * 2.0 * D), stream);
-    for (int t0 = 0; t0 < n_pos; t0 += DH_ATTN_RPB) {
-        const int cnt = n_pos - t0 < DH_ATTN_RPB ? n_pos - t0 : DH_ATTN_RPB;
-        const char* qc = (const char*)q + (size_t)t0 * ldq * esz;
-        char* oc = (char*)out + (size_t)t0 * D * esz;
-        DH_DISPATCH_T(dtype, launch_cross<T>(qc, ldq, kv, keymask, oc, n_img, cnt, S, D, n_heads, scale, (hipStream_t)stream, n_pos));
-    }
+    DH_DISPATCH_T(dtype, launch_cross<T>(q, ldq, kv, keymask, out, n_img, n_pos, S, D, n_heads, scale, (hipStream_t)stream, n_pos));
     DH_LAUNCH_CHECK();
 }
 
@@ -831,8 +827,9 @@ __global__ __launch_bounds__(256) void attn_cross_mfma_kernel(const T* __restric
             kf[j][kk] = *reinterpret_cast<const uint4*>(kb + min(16 * j + l15, S - 1) * 64 + 32 * kk + 8 * lq);
             vf[j][kk] = *reinterpret_cast<const uint4*>(vb + (16 * j + l15) * 64 + 32 * kk + 8 * lq);
         }
-    const bool live = l15 < rows_per_img;
-    const size_t qrow = (size_t)img * row_si + (live ? l15 : 0);
+    const int r0 = (int)blockIdx.y * 16;                           // row block of the image (prefill: 16 positions; decode: 0)
+    const bool live = r0 + l15 < rows_per_img;
+    const size_t qrow = (size_t)img * row_si + r0 + (live ? l15 : 0);
 #pragma unroll
     for (int kk = 0; kk < 2; ++kk) {
         const uint16_t* qp = reinterpret_cast<const uint16_t*>(q) + qrow * ldq + h * 64;
@@ -850,12 +847,12 @@ __global__ __launch_bounds__(256) void attn_cross_mfma_kernel(const T* __restric
     cross_core<T>(kf, vf, qf, kbits, S, scale, live, orow, lq);
 }
 
-// q [n_img * row_si rows, ldq] (image i's rows start at row i * row_si; rows_per_img <= 16 of them are used), out likewise
-// [.., D]; kp / vt from dh_attn_cross_pack.
+// q [n_img * row_si rows, ldq] (image i's rows start at row i * row_si; rows_per_img of them are used, 16 per blockIdx.y), out
+// likewise [.., D]; kp / vt from dh_attn_cross_pack.
 static int launch_cross_packed(const void* q, int ldq, const void* kp, const void* vt, const uint8_t* keymask, void* out, int n_img,
                                int rows_per_img, int row_si, int S, int D, int n_heads, float scale, int dperm, int dtype, hipStream_t s) {
     const int waves = n_img * n_heads;
-    DH_DISPATCH_16(dtype, hipLaunchKernelGGL(attn_cross_mfma_kernel<T>, dim3(dh_cdiv(waves, 4)), dim3(256), 0, s, (const T*)q, ldq,
+    DH_DISPATCH_16(dtype, hipLaunchKernelGGL(attn_cross_mfma_kernel<T>, dim3(dh_cdiv(waves, 4), dh_cdiv(rows_per_img, 16)), dim3(256), 0, s, (const T*)q, ldq,
                                              (const T*)kp, (const T*)vt, keymask, (T*)out, n_img, rows_per_img, row_si, S, D, n_heads, scale, dperm));
     return DH_OK;
 }
@@ -881,13 +878,10 @@ extern "C" int dh_attn_cross_prefill_packed(const void* q, int ldq, const void* 
     DH_REQUIRE(q && kp && vt && keymask && out && n_img > 0 && n_pos > 0 && S > 0 && S <= 64 && n_heads > 0 && D == 64 * n_heads);
     DH_REQUIRE(ldq >= D && (ldq % 8) == 0 && ((uintptr_t)q % 16) == 0 && ((uintptr_t)out % 8) == 0);
     DhProfScope prof("dh_attn_cross_prefill", 4.0 * n_img * n_pos * S * D, 2.0 * n_img * (S * 2.0 * D + n_pos * 2.0 * D), stream);
-    for (int t0 = 0; t0 < n_pos; t0 += 16) {           // 16 query rows per MFMA tile: the positions go in chunks of 16
-        const int cnt = n_pos - t0 < 16 ? n_pos - t0 : 16;
-        const char* qc = (const char*)q + (size_t)t0 * ldq * 2;
-        char* oc = (char*)out + (size_t)t0 * D * 2;
-        const int rc = launch_cross_packed(qc, ldq, kp, vt, keymask, oc, n_img, cnt, n_pos, S, D, n_heads, scale, dperm, dtype, (hipStream_t)stream);
-        if (rc != DH_OK) return rc;
-    }
+    DH_REQUIRE(dh_cdiv(n_pos, 16) <= 65535);
+    // 16 query rows per MFMA tile: the positions go in blocks of 16 along blockIdx.y, all in one launch
+    const int rc = launch_cross_packed(q, ldq, kp, vt, keymask, out, n_img, n_pos, n_pos, S, D, n_heads, scale, dperm, dtype, (hipStream_t)stream);
+    if (rc != DH_OK) return rc;
     DH_LAUNCH_CHECK();
 }
 

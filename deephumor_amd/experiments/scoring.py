@@ -85,8 +85,12 @@ class CaptionScores(NamedTuple):
         return CaptionScores(*(None if ts[0] is None else torch.cat(ts, 0) for ts in zip(*parts)))
 
 
-def _check_explain_args(model, template_images, template_index, captions, lengths, batch_size, pad_index, return_attention):
+def _check_explain_args(model, template_images, template_index, captions, lengths, batch_size, pad_index, return_attention, pairs=False):
+    """The argument rules of ``explain_captions``.  ``pairs`` (``score_pairs``): there is no ``template_index`` -- every caption meets
+    every template -- and at least one template is asked for instead; -> ``(None, lengths)``."""
     check_return_attention(return_attention, model)
+    if pairs and (not torch.is_tensor(template_images) or template_images.dim() < 1 or template_images.shape[0] < 1):
+        raise ValueError("template_images must be a tensor [T, ...] with T >= 1 templates")
     if isinstance(batch_size, bool) or not isinstance(batch_size, int) or batch_size < 1:
         raise ValueError(f"batch_size must be an int >= 1, got {batch_size!r}")
     if isinstance(pad_index, bool) or not isinstance(pad_index, int):
@@ -99,6 +103,9 @@ def _check_explain_args(model, template_images, template_index, captions, length
         raise ValueError(f"lengths must be an integer tensor of shape [{n}] (one per caption), got {tuple(lengths.shape)} {lengths.dtype}")
     if int(lengths.min()) < 1:
         raise ValueError("lengths must be >= 1 (a caption holds at least its <eos>)")
+    if pairs:
+        check_ids(captions, model.decoder.classifier.out_features)
+        return None, lengths.long()
     template_index = torch.as_tensor(template_index)
     if tuple(template_index.shape) != (n,) or template_index.dtype.is_floating_point or template_index.dtype == torch.bool:
         raise ValueError(f"template_index must be an integer tensor of shape [{n}] (one per caption), got {tuple(template_index.shape)}")
@@ -133,15 +140,12 @@ def explain_captions(model, template_images, template_index, captions, lengths, 
                                                   return_attention)
     enc = model.encoder
     dec = model.decoder
-    lstm = hasattr(dec, "lstm")
     with torch.no_grad():
         feats = enc(template_images, labels) if labels is not None else enc(template_images)
         spatial = None
         if isinstance(feats, tuple):
             feats, spatial = feats
         dev = feats.device
-        width = dec.classifier.in_features
-        fused_ok = width % 64 == 0 and width >= 128                              # dh_vocab_logprob's contract
         parts = []
         for lo in range(0, captions.shape[0], batch_size):
             hi = min(lo + batch_size, captions.shape[0])
@@ -149,55 +153,146 @@ def explain_captions(model, template_images, template_index, captions, lengths, 
             emb = feats.index_select(0, idx)
             sp = None if spatial is None else spatial.index_select(0, idx)
             tgt = captions[lo:hi].to(dev).contiguous()
-            inp = tgt[:, :-1]
-            bs, l = tgt.shape
             lens = lengths[lo:hi].to(dev)
-
-            def hidden_route(split=False):
-                attn = None
-                if lstm:
-                    hidden, _, _ = dec.hidden_states(emb, inp, None)
-                elif return_attention:
-                    hidden, attn = dec._forward(inp, sp, emb, num_positions=l, return_hidden=True, return_attention=True)
-                else:
-                    hidden = dec._forward(inp, sp, emb, num_positions=l, return_hidden=True)
-                plan = dec._get_plan()
-                hidden = hidden[:, :l].contiguous()
-                w_x = plan["cls_w_x"] if split else None
-                logp = hip.vocab_logprob(hidden.reshape(bs * l, width), plan["cls_w"], plan["cls_b"], tgt.reshape(-1), w_x=w_x)
-                return logp.view(bs, l), attn
-
-            def logits_route():
-                attn = None
-                if return_attention:
-                    logits, attn = f32x_guarded(lambda d: d._forward(inp, sp, emb, num_positions=l, return_attention=True))(dec)
-                elif spatial is not None:
-                    logits = dec(inp, enc_out=sp, start_emb=emb, num_positions=l)
-                elif lstm:
-                    logits = dec(emb, inp, None)
-                else:
-                    logits = dec(inp, start_emb=emb)
-                logits = logits[:, :l].contiguous()
-                return hip.token_logprob(logits.reshape(bs * l, -1), tgt.reshape(-1)).view(bs, l), attn
-
-            if feats.dtype in hip.HALF_DTYPES and fused_ok:
-                logp, attn = hidden_route()
-            elif (feats.dtype == torch.float32 and fused_ok and hip.option("f32_split") and getattr(dec, "pad_index", 0) != 1
-                  and not torch.cuda.is_current_stream_capturing() and "cls_w_x" in dec._get_plan()):
-                logp, attn = hidden_route(split=True)
-                with torch.cuda.device(dev):
-                    over = hip.f32x_take_overflow(dev)
-                if over:                                                         # an activation left the fp16 range: exact kernels
-                    with hip.option_scope(f32_split=0):
-                        logp, attn = logits_route()
-            else:
-                logp, attn = logits_route()
+            logp, attn = _pass_logprobs(dec, emb, sp, tgt, return_attention)
             pad = tgt == pad_index
             pp = hip.seq_perplexity(logp, tgt, lens, pad_index)
             if attn is not None:
-                attn = attn[:, :l].masked_fill(pad[..., None], 0.0)
+                attn = attn[:, :tgt.shape[1]].masked_fill(pad[..., None], 0.0)
             parts.append(CaptionScores(logp.masked_fill(pad, 0.0), pp, attn))
         return CaptionScores.cat(parts)
+
+
+def _pass_logprobs(dec, emb, sp, tgt, return_attention=False, share=1):
+    """One decoder pass of ``explain_captions`` / ``score_pairs``, the one statement of their routes (``explain_captions``' docstring):
+    start embeddings ``emb [bs, D]``, captions ``tgt`` int64 ``[bs, l]`` on the device -> ``(log-probs fp32 [bs, l], pads not yet
+    zeroed; attention [bs, >= l, S] or None)``.  ``sp``: the spatial features of the two cross-attention kinds, ``[bs, S, D]`` -- or,
+    with ``share > 1`` (``score_pairs``' template-major passes), ``[bs / share, S, D]``: image ``j`` serves sequences
+    ``j * share .. (j + 1) * share - 1`` (``TransformerDecoder._forward``'s ``enc_share``)."""
+    lstm = hasattr(dec, "lstm")
+    dev = emb.device
+    inp = tgt[:, :-1]
+    bs, l = tgt.shape
+    width = dec.classifier.in_features
+    fused_ok = width % 64 == 0 and width >= 128                                  # dh_vocab_logprob's contract
+    kw = dict(enc_share=share) if share > 1 else {}
+
+    def hidden_route(split=False):
+        attn = None
+        if lstm:
+            hidden, _, _ = dec.hidden_states(emb, inp, None)
+        elif return_attention:
+            hidden, attn = dec._forward(inp, sp, emb, num_positions=l, return_hidden=True, return_attention=True, **kw)
+        else:
+            hidden = dec._forward(inp, sp, emb, num_positions=l, return_hidden=True, **kw)
+        plan = dec._get_plan()
+        hidden = hidden[:, :l].contiguous()
+        w_x = plan["cls_w_x"] if split else None
+        logp = hip.vocab_logprob(hidden.reshape(bs * l, width), plan["cls_w"], plan["cls_b"], tgt.reshape(-1), w_x=w_x)
+        return logp.view(bs, l), attn
+
+    def logits_route():
+        attn = None
+        if return_attention:
+            logits, attn = f32x_guarded(lambda d: d._forward(inp, sp, emb, num_positions=l, return_attention=True, **kw))(dec)
+        elif kw:
+            logits = f32x_guarded(lambda d: d._forward(inp, sp, emb, num_positions=l, **kw))(dec)
+        elif sp is not None:
+            logits = dec(inp, enc_out=sp, start_emb=emb, num_positions=l)
+        elif lstm:
+            logits = dec(emb, inp, None)
+        else:
+            logits = dec(inp, start_emb=emb)
+        logits = logits[:, :l].contiguous()
+        return hip.token_logprob(logits.reshape(bs * l, -1), tgt.reshape(-1)).view(bs, l), attn
+
+    if emb.dtype in hip.HALF_DTYPES and fused_ok:
+        return hidden_route()
+    if (emb.dtype == torch.float32 and fused_ok and hip.option("f32_split") and getattr(dec, "pad_index", 0) != 1
+            and not torch.cuda.is_current_stream_capturing() and "cls_w_x" in dec._get_plan()):
+        logp, attn = hidden_route(split=True)
+        with torch.cuda.device(dev):
+            over = hip.f32x_take_overflow(dev)
+        if over:                                                                 # an activation left the fp16 range: exact kernels
+            with hip.option_scope(f32_split=0):
+                logp, attn = logits_route()
+        return logp, attn
+    return logits_route()
+
+
+class PairScores(NamedTuple):
+    """What ``score_pairs`` returns for ``n`` captions and ``T`` templates.  Device tensors:
+
+    ``logprob`` fp32 ``[n, T]``     ``log p(caption i | template t)``: the fp64 sum of the pair's per-token fp32 log-probs
+                                    (``explain_captions``' ``logprobs`` row; pads contribute exactly 0), rounded once;
+    ``perplexity`` fp32 ``[n, T]``  the pair's ``dh_seq_perplexity`` value, ``explain_captions``' bit for bit."""
+    logprob: torch.Tensor
+    perplexity: torch.Tensor
+
+    def map(self, fn):
+        """``PairScores`` of ``fn(field)`` (``clone``, ``cpu`` ...)."""
+        return PairScores(*(fn(t) for t in self))
+
+    @staticmethod
+    def cat(parts):
+        """The captions of several results over the same templates, in order."""
+        return PairScores(*(torch.cat(ts, 0) for ts in zip(*list(parts))))
+
+
+# Private switch between the two ways a cross-attention decoder gets a pass's template features (same bits either way):
+# True   one K|V projection and one packed layout per template of the pass, shared by its captions (``_forward``'s ``enc_share``);
+# False  the features gathered per pair, as ``explain_captions`` does.
+# The route kept is the one ``tools/time_pairs.py`` measured faster (profiles/pairs/timing.txt); the tests reach the other through here.
+_SHARE_TEMPLATE_KEYS = True
+
+
+def score_pairs(model, template_images, captions, lengths, labels=None, batch_size=256, pad_index=0):
+    """Every caption under every template: ``log p(caption i | template t)`` for ``captions`` int64 ``[n, L]`` and ``template_images``
+    ``[T, 3, H, W]`` -> ``PairScores`` (``logprob``, ``perplexity``, fp32 ``[n, T]`` each).  Inputs and position convention are
+    ``score_captions``' (``lengths [n]``, ``labels [T, l]`` for the label models; position ``p`` predicts ``captions[:, p]``, position 0
+    is the image slot) without a ``template_index``.  ``rank_templates`` / ``rank_captions`` read the matrix.
+
+    The encoder sees each template once.  The decoder runs in passes of at most ``batch_size`` (caption, template) sequences, laid out
+    template-major -- sequence ``t' * n_c + c`` for the ``n_c`` captions and the templates of the pass --, so the rows of one template
+    are contiguous and the two cross-attention kinds project and pack a template's keys once for all its captions.  Encoded features
+    are gathered per pass: apart from the two ``[n, T]`` results, memory is that of one pass.  The routes of the log-probs are
+    ``explain_captions``', per pass (one helper states them for both); a pair's two values are those of ``explain_captions`` on that
+    single pair and do not depend on ``batch_size``, ``n``, ``T`` or the pairs that share its pass.  Arguments are validated before the
+    encoder runs."""
+    _, lengths = _check_explain_args(model, template_images, None, captions, lengths, batch_size, pad_index, False, pairs=True)
+    enc = model.encoder
+    dec = model.decoder
+    with torch.no_grad():
+        feats = enc(template_images, labels) if labels is not None else enc(template_images)
+        spatial = None
+        if isinstance(feats, tuple):
+            feats, spatial = feats
+        dev = feats.device
+        (n, l), t_all = captions.shape, feats.shape[0]
+        caps, lens = captions.to(dev).contiguous(), lengths.to(dev)
+        out = PairScores(torch.empty((n, t_all), dtype=torch.float32, device=dev), torch.empty((n, t_all), dtype=torch.float32, device=dev))
+        for lo in range(0, n, batch_size):
+            hi = min(lo + batch_size, n)
+            nc = hi - lo
+            per = min(max(1, batch_size // nc), t_all)                           # templates of a pass
+            # template-major: sequence t' * nc + c.  The captions' side of a pass is the same for every pass of the chunk (a shorter
+            # last pass takes a prefix of it)
+            tgt_all, lens_all = caps[lo:hi].repeat(per, 1), lens[lo:hi].repeat(per)
+            pad_all = tgt_all == pad_index
+            for t0 in range(0, t_all, per):
+                t1 = min(t0 + per, t_all)
+                rows = (t1 - t0) * nc
+                tgt = tgt_all[:rows]
+                idx = torch.arange(t0, t1, device=dev).repeat_interleave(nc)
+                emb = feats.index_select(0, idx)
+                share = nc if _SHARE_TEMPLATE_KEYS and spatial is not None else 1
+                sp = None if spatial is None else spatial[t0:t1] if share > 1 else spatial.index_select(0, idx)
+                logp, _ = _pass_logprobs(dec, emb, sp, tgt, share=share)
+                pp = hip.seq_perplexity(logp, tgt, lens_all[:rows], pad_index)
+                total = logp.masked_fill(pad_all[:rows], 0.0).sum(-1, dtype=torch.float64).float()
+                out.logprob[lo:hi, t0:t1] = total.view(t1 - t0, nc).t()
+                out.perplexity[lo:hi, t0:t1] = pp.view(t1 - t0, nc).t()
+        return out
 
 
 def token_scores(captions, scores, vocab):

@@ -356,11 +356,19 @@ class _IncrementalDecoder(_Planned, nn.Module):
                                         attn_w=attn_w, attn_layer=len(self.layers) - 1)
         return x_out if x_out is not None else sc["x"]
 
-    def _forward(self, x, enc_out, start_emb, num_positions=None, return_hidden=False, return_attention=False):
+    def _forward(self, x, enc_out, start_emb, num_positions=None, return_hidden=False, return_attention=False, enc_share=1):
         """``return_attention`` (internal; ``experiments.explain_captions``): the pair ``(result, attention)`` -- fp32
         ``[bs, seq, S]``, the last layer's head-mean encoder-attention softmax of every teacher-forced position, from one
-        ``dh_attn_cross_weights`` launch behind that layer's ``fc_q`` (position by position: ``_decode_position``'s ``attn_w``)."""
+        ``dh_attn_cross_weights`` launch behind that layer's ``fc_q`` (position by position: ``_decode_position``'s ``attn_w``).
+        ``enc_share`` (internal; ``experiments.score_pairs``): ``enc_out`` holds ``bs / enc_share`` images and image ``j`` serves the
+        sequences ``j * enc_share .. (j + 1) * enc_share - 1``.  The prefill form then projects and packs each image's keys ONCE and
+        its cross-attention launches take ``enc_share * seq`` query rows per image; every other form gets the images repeated."""
         check_ids(x, self.tok_embedding.num_embeddings)                               # (nn.Embedding's IndexError)
+        if enc_share > 1:
+            if enc_out is None or enc_out.shape[0] * enc_share != x.shape[0]:
+                raise ValueError(f"enc_share = {enc_share}: enc_out must hold {x.shape[0]} / {enc_share} images")
+            if return_attention or start_emb is None or self.pad_index == 1:
+                enc_out, enc_share = enc_out.repeat_interleave(enc_share, 0), 1
         if return_attention:
             check_return_attention(True, self)
             if start_emb is None or enc_out is None:
@@ -382,7 +390,9 @@ class _IncrementalDecoder(_Planned, nn.Module):
         tokens[:, :ncopy] = x[:, :ncopy].to(torch.int32)
         if self._prefill_ok(plan, seq):
             return self._forward_prefill(plan, tokens, enc_out, start_emb.to(plan["dtype"]).contiguous(), bs, seq, return_hidden,
-                                         return_attention)
+                                         return_attention, enc_share)
+        if enc_share > 1:
+            enc_out = enc_out.repeat_interleave(enc_share, 0)
         helper_src = (torch.arange(bs, dtype=torch.int32, device=dev))[:, None].expand(bs, seq).contiguous()
         run = self._Run(self, plan, bs, 1, seq, enc_out, dev)
         hs = torch.empty((bs, seq, self.hid_dim), device=dev, dtype=plan["dtype"])
@@ -469,11 +479,14 @@ class _IncrementalDecoder(_Planned, nn.Module):
         limit = 56 if plan["dtype"] in hip.HALF_DTYPES else 40
         return self.hid_dim == 64 * self.n_heads and seq <= limit
 
-    def _forward_prefill(self, plan, tokens, enc_out, start_emb, bs, seq, return_hidden=False, return_attention=False):
+    def _forward_prefill(self, plan, tokens, enc_out, start_emb, bs, seq, return_hidden=False, return_attention=False, enc_share=1):
         """Teacher-forced forward in prefill form: rows are sequence-major (row n*seq + t); per layer one QKV GEMM
-        over all bs*seq rows, one causal self-attention launch, projection + residual LayerNorm, (cross-attention in
-        chunks of positions), FFN -- ~12 launches per layer instead of ~11 per layer AND position."""
+        over all bs*seq rows, one causal self-attention launch, projection + residual LayerNorm, (one cross-attention
+        launch over all positions), FFN -- ~11 launches per layer instead of ~11 per layer AND position.
+        ``enc_share`` (``_forward``): ``enc_out`` holds ``bs / enc_share`` images; the rows of image ``j`` are the contiguous
+        ``enc_share * seq`` rows from ``j * enc_share * seq`` on, which is all the cross-attention kernels need to know."""
         d, nh, dt = self.hid_dim, self.n_heads, plan["dtype"]
+        n_img, n_rows = bs // enc_share, enc_share * seq      # cross-attention: images and the query rows each of them serves
         x = hip.embed_prefill(plan["tok"], plan["pos"], start_emb, tokens, bs, seq, plan["scale"])
         kv = keymask = None
         s_enc = 0
@@ -490,13 +503,13 @@ class _IncrementalDecoder(_Planned, nn.Module):
                 # layout on every chain) against the unpacked K; seq <= 56 rows per image.  The attention output below is not touched.
                 w = torch.empty((bs, seq, s_enc), dtype=torch.float32, device=q.device)
                 attn.append(hip.attn_cross_weights(q, kv, keymask, w, bs, seq, 1, s_enc, d, nh, L["ea_scale"]))
-            if packed_ok:                                  # matrix-core cross-attention, 16 positions per launch
+            if packed_ok:                                  # matrix-core cross-attention, 16 positions per workgroup row block
                 # (dperm: the head-dim slot order of the decode chain's fused fc_q + attention launch, so that teacher-forced
                 # logits and incremental decoding sum in the same order)
                 dperm = "wq_f" in L
-                kp, vt = hip.attn_cross_pack(kv, bs, s_enc, d, nh, dperm=dperm)
-                return hip.attn_cross_prefill_packed(q, kp, vt, keymask, bs, seq, s_enc, d, nh, L["ea_scale"], dperm=dperm)
-            return hip.attn_cross_prefill(q, kv, keymask, bs, seq, s_enc, d, nh, L["ea_scale"])
+                kp, vt = hip.attn_cross_pack(kv, n_img, s_enc, d, nh, dperm=dperm)
+                return hip.attn_cross_prefill_packed(q, kp, vt, keymask, n_img, n_rows, s_enc, d, nh, L["ea_scale"], dperm=dperm)
+            return hip.attn_cross_prefill(q, kv, keymask, n_img, n_rows, s_enc, d, nh, L["ea_scale"])
 
         if "w1_f" in plan["layers"][0]:
             # 16-bit dtypes: the deferred-LayerNorm chain of dh_transformer_decode_position (csrc/runtime.hip), all positions

@@ -375,7 +375,7 @@ int dh_attn_cross_weights(const void* q, int ldq, const void* kv, const uint8_t*
  * attention launch needed; kept as the product's default so that every 16-bit summation order -- and token -- stays what it was);
  * _decode_packed / _prefill_packed take the same flag and then read q in that slot order (prefill and decode agree bit for bit).  One wave then
  * handles one (image, head) straight from HBM: no LDS, no barrier, one memory round trip.  _prefill_packed: every
- * position of image n (rows n*n_pos + t), in chunks of 16 positions. */
+ * position of image n (rows n*n_pos + t) in ONE launch, 16 positions per row block of the grid; n_pos is any row count an image serves. */
 int dh_attn_cross_pack(const void* kv, void* kp, void* vt, int n_img, int S, int D, int n_heads, int dperm, int dtype, void* stream);
 
 int dh_attn_cross_decode_packed(const void* q, int ldq, const void* kp, const void* vt, const uint8_t* keymask, void* out,
