@@ -3,10 +3,12 @@ perplexity metric on the HIP kernels, corpus scoring with per-template encoder c
 text <-> token helpers.  The Trainer / tensorboard harness is out of scope."""
 from .metrics import perplexity, sequence_perplexity
 from .scoring import CaptionScores, PairScores, explain_captions, score_captions, score_pairs, token_scores
+from .occlusion import OcclusionScores, occlusion_maps
 from .ranking import CaptionRanks, TemplateRanks, rank_captions, rank_templates, template_accuracy
 from .inference import attention_to_heatmaps, bad_words_to_ids, beam_logprob_scores, beams_to_texts, group_best, prompts_to_batch, rank_beams, sequence_bias_from_words, text_to_seq, seq_to_text, split_caption
 
 __all__ = ["perplexity", "sequence_perplexity", "score_captions", "text_to_seq", "seq_to_text", "split_caption", "prompts_to_batch",
            "beams_to_texts", "rank_beams", "bad_words_to_ids", "attention_to_heatmaps", "beam_logprob_scores", "group_best",
            "sequence_bias_from_words", "explain_captions", "CaptionScores", "token_scores", "score_pairs", "PairScores",
-           "rank_templates", "rank_captions", "template_accuracy", "TemplateRanks", "CaptionRanks"]
+           "rank_templates", "rank_captions", "template_accuracy", "TemplateRanks", "CaptionRanks",
+           "occlusion_maps", "OcclusionScores"]

@@ -190,7 +190,10 @@ def attention_to_heatmaps(attention, size=(224, 224), grid=(7, 7)):
     image patches in row-major order; keys beyond them -- the padded rows of a ``pad_index >= 2`` decoder -- are dropped) ->
     fp32 ``[..., H, W]`` by bilinear upsampling (``align_corners=False``: every patch spreads over its own ``H / 7 x W / 7`` cell and
     blends into its neighbours; for whole multiples of the grid the upsampled map has the patch map's mean).  A row that is all
-    zero -- a column past the caption's length -- stays all zero.  Post-processing for display, on the tensor's own device."""
+    zero -- a column past the caption's length -- stays all zero.  Post-processing for display, on the tensor's own device.
+    ``occlusion_maps``' ``drop [n, R]`` is such a tensor too (``R`` regions in row-major order): ``attention_to_heatmaps(drop,
+    grid=(7, 7))`` for ``level="patch"`` at 224 x 224, ``grid=`` the call's own grid for ``level="pixel"`` -- the values are log-prob
+    differences of either sign then, not weights, and are upsampled as they are."""
     gh, gw = grid
     if attention.shape[-1] < gh * gw:
         raise ValueError(f"attention has {attention.shape[-1]} keys, fewer than the {gh} x {gw} grid")

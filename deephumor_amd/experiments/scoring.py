@@ -163,12 +163,13 @@ def explain_captions(model, template_images, template_index, captions, lengths, 
         return CaptionScores.cat(parts)
 
 
-def _pass_logprobs(dec, emb, sp, tgt, return_attention=False, share=1):
+def _pass_logprobs(dec, emb, sp, tgt, return_attention=False, share=1, hide=None):
     """One decoder pass of ``explain_captions`` / ``score_pairs``, the one statement of their routes (``explain_captions``' docstring):
     start embeddings ``emb [bs, D]``, captions ``tgt`` int64 ``[bs, l]`` on the device -> ``(log-probs fp32 [bs, l], pads not yet
     zeroed; attention [bs, >= l, S] or None)``.  ``sp``: the spatial features of the two cross-attention kinds, ``[bs, S, D]`` -- or,
     with ``share > 1`` (``score_pairs``' template-major passes), ``[bs / share, S, D]``: image ``j`` serves sequences
-    ``j * share .. (j + 1) * share - 1`` (``TransformerDecoder._forward``'s ``enc_share``)."""
+    ``j * share .. (j + 1) * share - 1`` (``TransformerDecoder._forward``'s ``enc_share``).  ``hide`` (``occlusion_maps``): uint8
+    ``[bs / share, S]`` -- ``sp`` then holds the base images whose variants the pass scores (``_forward``'s ``enc_hide``)."""
     lstm = hasattr(dec, "lstm")
     dev = emb.device
     inp = tgt[:, :-1]
@@ -176,6 +177,8 @@ def _pass_logprobs(dec, emb, sp, tgt, return_attention=False, share=1):
     width = dec.classifier.in_features
     fused_ok = width % 64 == 0 and width >= 128                                  # dh_vocab_logprob's contract
     kw = dict(enc_share=share) if share > 1 else {}
+    if hide is not None:
+        kw["enc_hide"] = hide
 
     def hidden_route(split=False):
         attn = None
@@ -267,32 +270,70 @@ def score_pairs(model, template_images, captions, lengths, labels=None, batch_si
         spatial = None
         if isinstance(feats, tuple):
             feats, spatial = feats
-        dev = feats.device
-        (n, l), t_all = captions.shape, feats.shape[0]
-        caps, lens = captions.to(dev).contiguous(), lengths.to(dev)
-        out = PairScores(torch.empty((n, t_all), dtype=torch.float32, device=dev), torch.empty((n, t_all), dtype=torch.float32, device=dev))
-        for lo in range(0, n, batch_size):
-            hi = min(lo + batch_size, n)
-            nc = hi - lo
-            per = min(max(1, batch_size // nc), t_all)                           # templates of a pass
-            # template-major: sequence t' * nc + c.  The captions' side of a pass is the same for every pass of the chunk (a shorter
-            # last pass takes a prefix of it)
-            tgt_all, lens_all = caps[lo:hi].repeat(per, 1), lens[lo:hi].repeat(per)
-            pad_all = tgt_all == pad_index
-            for t0 in range(0, t_all, per):
-                t1 = min(t0 + per, t_all)
-                rows = (t1 - t0) * nc
-                tgt = tgt_all[:rows]
-                idx = torch.arange(t0, t1, device=dev).repeat_interleave(nc)
-                emb = feats.index_select(0, idx)
-                share = nc if _SHARE_TEMPLATE_KEYS and spatial is not None else 1
+        logprob, perplexity, _, _ = _score_feature_pairs(dec, feats, spatial, captions, lengths, batch_size, pad_index)
+        return PairScores(logprob, perplexity)
+
+
+# Private switch between the two ways ``occlusion_maps(level="patch")`` gives a pass the keys of a template's variants (same bits either
+# way: a hidden row is a masked key of weight exactly 0):
+# False  the variants' features with their rows zeroed, projected and packed per variant (``enc_share`` alone);
+# True   one K|V projection and one packed layout for the template, copied on the device for the variants of the pass, the hidden rows
+#        ORed onto the key mask (``_forward``'s ``enc_hide``).
+# The route kept is the one ``tools/time_occlusion.py`` measured faster (profiles/occlusion/timing.txt: the copies and the mask algebra
+# cost more than the 16 x smaller projection and pack save); the tests reach the other through here.
+_COPY_VARIANT_KEYS = False
+
+
+def _score_feature_pairs(dec, feats, spatial, captions, lengths, batch_size, pad_index, hide=None, detail=False, copy_keys=True):
+    """``score_pairs`` behind the encoder: every caption of ``captions [n, L]`` under every row of the encoded features ``feats [T, D]``
+    (``spatial [T, S, D]`` or None) in template-major passes of at most ``batch_size`` sequences -> ``(logprob fp32 [n, T], perplexity
+    fp32 [n, T], sums, rows)``.  ``detail``: ``sums`` fp64 ``[n, T]``, the sums ``logprob`` rounds, and ``rows`` fp32 ``[n, T, L]``, the
+    per-token log-probs with exact zeros at pads (None, None otherwise).
+    ``hide`` (``occlusion_maps``, cross-attention kinds): uint8 ``[T, S]`` and ``spatial [1, S, D]`` -- the ``T`` feature rows are
+    variants of ONE image, variant ``t`` being its spatial features with the rows flagged in ``hide[t]`` set to exactly 0.
+    ``copy_keys=False``: the caller knows a variant without an unmasked key (its softmax is uniform and shows the zeroed rows' K|V),
+    which only the zeroed features themselves get right."""
+    dev = feats.device
+    (n, l), t_all = captions.shape, feats.shape[0]
+    caps, lens = captions.to(dev).contiguous(), lengths.to(dev)
+    logprob = torch.empty((n, t_all), dtype=torch.float32, device=dev)
+    perplexity = torch.empty((n, t_all), dtype=torch.float32, device=dev)
+    sums = torch.empty((n, t_all), dtype=torch.float64, device=dev) if detail else None
+    rows_out = torch.empty((n, t_all, l), dtype=torch.float32, device=dev) if detail else None
+    for lo in range(0, n, batch_size):
+        hi = min(lo + batch_size, n)
+        nc = hi - lo
+        per = min(max(1, batch_size // nc), t_all)                               # templates of a pass
+        # template-major: sequence t' * nc + c.  The captions' side of a pass is the same for every pass of the chunk (a shorter
+        # last pass takes a prefix of it)
+        tgt_all, lens_all = caps[lo:hi].repeat(per, 1), lens[lo:hi].repeat(per)
+        pad_all = tgt_all == pad_index
+        for t0 in range(0, t_all, per):
+            t1 = min(t0 + per, t_all)
+            rows = (t1 - t0) * nc
+            tgt = tgt_all[:rows]
+            idx = torch.arange(t0, t1, device=dev).repeat_interleave(nc)
+            emb = feats.index_select(0, idx)
+            share = nc if _SHARE_TEMPLATE_KEYS and spatial is not None else 1
+            if hide is not None:
+                if _COPY_VARIANT_KEYS and copy_keys:
+                    sp, flags = spatial, hide[t0:t1] if share > 1 else hide.index_select(0, idx)
+                else:
+                    sp, flags = spatial.expand(t1 - t0, -1, -1).masked_fill(hide[t0:t1].bool().unsqueeze(-1), 0.0), None
+                    sp = sp if share > 1 else sp.repeat_interleave(nc, 0)
+                logp, _ = _pass_logprobs(dec, emb, sp, tgt, share=share, hide=flags)
+            else:
                 sp = None if spatial is None else spatial[t0:t1] if share > 1 else spatial.index_select(0, idx)
                 logp, _ = _pass_logprobs(dec, emb, sp, tgt, share=share)
-                pp = hip.seq_perplexity(logp, tgt, lens_all[:rows], pad_index)
-                total = logp.masked_fill(pad_all[:rows], 0.0).sum(-1, dtype=torch.float64).float()
-                out.logprob[lo:hi, t0:t1] = total.view(t1 - t0, nc).t()
-                out.perplexity[lo:hi, t0:t1] = pp.view(t1 - t0, nc).t()
-        return out
+            pp = hip.seq_perplexity(logp, tgt, lens_all[:rows], pad_index)
+            zeroed = logp.masked_fill(pad_all[:rows], 0.0)
+            total = zeroed.sum(-1, dtype=torch.float64)
+            logprob[lo:hi, t0:t1] = total.float().view(t1 - t0, nc).t()
+            perplexity[lo:hi, t0:t1] = pp.view(t1 - t0, nc).t()
+            if detail:
+                sums[lo:hi, t0:t1] = total.view(t1 - t0, nc).t()
+                rows_out[lo:hi, t0:t1] = zeroed.view(t1 - t0, nc, l).transpose(0, 1)
+    return logprob, perplexity, sums, rows_out
 
 
 def token_scores(captions, scores, vocab):

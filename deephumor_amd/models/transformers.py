@@ -356,16 +356,29 @@ class _IncrementalDecoder(_Planned, nn.Module):
                                         attn_w=attn_w, attn_layer=len(self.layers) - 1)
         return x_out if x_out is not None else sc["x"]
 
-    def _forward(self, x, enc_out, start_emb, num_positions=None, return_hidden=False, return_attention=False, enc_share=1):
+    def _forward(self, x, enc_out, start_emb, num_positions=None, return_hidden=False, return_attention=False, enc_share=1,
+                 enc_hide=None):
         """``return_attention`` (internal; ``experiments.explain_captions``): the pair ``(result, attention)`` -- fp32
         ``[bs, seq, S]``, the last layer's head-mean encoder-attention softmax of every teacher-forced position, from one
         ``dh_attn_cross_weights`` launch behind that layer's ``fc_q`` (position by position: ``_decode_position``'s ``attn_w``).
         ``enc_share`` (internal; ``experiments.score_pairs``): ``enc_out`` holds ``bs / enc_share`` images and image ``j`` serves the
         sequences ``j * enc_share .. (j + 1) * enc_share - 1``.  The prefill form then projects and packs each image's keys ONCE and
-        its cross-attention launches take ``enc_share * seq`` query rows per image; every other form gets the images repeated."""
+        its cross-attention launches take ``enc_share * seq`` query rows per image; every other form gets the images repeated.
+        ``enc_hide`` (internal; ``experiments.occlusion_maps``): uint8 ``[n_img, S]`` -- the ``n_img`` images are VARIANTS of the
+        ``n_base`` images of ``enc_out`` (``n_img % n_base == 0``): image ``j`` is base image ``j // (n_img / n_base)`` with the rows
+        flagged in ``enc_hide[j]`` set to zero, i.e. masked keys (``_enc_for_cross``).  A masked key has weight exactly 0, so the prefill
+        form of a ``pad_index == 0`` decoder projects and packs each BASE image once, copies the result for its variants and ORs the
+        flags onto the key mask -- the same bits as the zeroed rows give; every other form gets the zeroed rows themselves."""
         check_ids(x, self.tok_embedding.num_embeddings)                               # (nn.Embedding's IndexError)
+        if enc_hide is not None:
+            n_img = x.shape[0] // max(enc_share, 1)
+            if (enc_out is None or enc_hide.dtype != torch.uint8 or enc_hide.dim() != 2 or enc_hide.shape[0] != n_img
+                    or n_img * enc_share != x.shape[0] or n_img % enc_out.shape[0] or enc_hide.shape[1] != enc_out.shape[1]):
+                raise ValueError(f"enc_hide must be uint8 [{n_img}, S] flags for variants of the images of enc_out")
+            if return_attention or start_emb is None or self.pad_index != 0:
+                enc_out, enc_hide = self._hide_rows(enc_out, enc_hide), None
         if enc_share > 1:
-            if enc_out is None or enc_out.shape[0] * enc_share != x.shape[0]:
+            if enc_out is None or (enc_out.shape[0] if enc_hide is None else enc_hide.shape[0]) * enc_share != x.shape[0]:
                 raise ValueError(f"enc_share = {enc_share}: enc_out must hold {x.shape[0]} / {enc_share} images")
             if return_attention or start_emb is None or self.pad_index == 1:
                 enc_out, enc_share = enc_out.repeat_interleave(enc_share, 0), 1
@@ -390,7 +403,9 @@ class _IncrementalDecoder(_Planned, nn.Module):
         tokens[:, :ncopy] = x[:, :ncopy].to(torch.int32)
         if self._prefill_ok(plan, seq):
             return self._forward_prefill(plan, tokens, enc_out, start_emb.to(plan["dtype"]).contiguous(), bs, seq, return_hidden,
-                                         return_attention, enc_share)
+                                         return_attention, enc_share, enc_hide)
+        if enc_hide is not None:
+            enc_out = self._hide_rows(enc_out, enc_hide)
         if enc_share > 1:
             enc_out = enc_out.repeat_interleave(enc_share, 0)
         helper_src = (torch.arange(bs, dtype=torch.int32, device=dev))[:, None].expand(bs, seq).contiguous()
@@ -407,6 +422,12 @@ class _IncrementalDecoder(_Planned, nn.Module):
             return (hs,) + attn if attn else hs
         out = hip.linear(hs.view(bs * seq, self.hid_dim), plan["cls_w"], plan["cls_b"], out_dtype=torch.float32, tag="vocab", w_x=plan.get("cls_w_x"))
         return (out.view(bs, seq, -1),) + attn if attn else out.view(bs, seq, -1)
+
+    @staticmethod
+    def _hide_rows(enc_out, enc_hide):
+        """The variants ``enc_hide`` (``_forward``) describes, as features: ``[n_img, S, D]`` with the flagged rows exactly 0."""
+        rep = enc_hide.shape[0] // enc_out.shape[0]
+        return enc_out.repeat_interleave(rep, 0).masked_fill(enc_hide.bool().unsqueeze(-1), 0.0)
 
     def _forward_modules(self, x, enc_out, start_emb=None, return_hidden=False):
         """The reference's own formulation of ``forward`` on the module-API layers: pad ``x`` / ``enc_out`` to a common length
@@ -479,12 +500,15 @@ class _IncrementalDecoder(_Planned, nn.Module):
         limit = 56 if plan["dtype"] in hip.HALF_DTYPES else 40
         return self.hid_dim == 64 * self.n_heads and seq <= limit
 
-    def _forward_prefill(self, plan, tokens, enc_out, start_emb, bs, seq, return_hidden=False, return_attention=False, enc_share=1):
+    def _forward_prefill(self, plan, tokens, enc_out, start_emb, bs, seq, return_hidden=False, return_attention=False, enc_share=1,
+                         enc_hide=None):
         """Teacher-forced forward in prefill form: rows are sequence-major (row n*seq + t); per layer one QKV GEMM
         over all bs*seq rows, one causal self-attention launch, projection + residual LayerNorm, (one cross-attention
         launch over all positions), FFN -- ~11 launches per layer instead of ~11 per layer AND position.
         ``enc_share`` (``_forward``): ``enc_out`` holds ``bs / enc_share`` images; the rows of image ``j`` are the contiguous
-        ``enc_share * seq`` rows from ``j * enc_share * seq`` on, which is all the cross-attention kernels need to know."""
+        ``enc_share * seq`` rows from ``j * enc_share * seq`` on, which is all the cross-attention kernels need to know.
+        ``enc_hide`` (``_forward``; ``pad_index == 0``, no ``return_attention``): ``enc_out`` holds the base images; their K|V (and its
+        packed layout) are computed once and copied per variant, the flags join the key mask."""
         d, nh, dt = self.hid_dim, self.n_heads, plan["dtype"]
         n_img, n_rows = bs // enc_share, enc_share * seq      # cross-attention: images and the query rows each of them serves
         x = hip.embed_prefill(plan["tok"], plan["pos"], start_emb, tokens, bs, seq, plan["scale"])
@@ -492,6 +516,10 @@ class _IncrementalDecoder(_Planned, nn.Module):
         s_enc = 0
         if enc_out is not None:
             flat, s_enc, keymask = self._enc_for_cross(enc_out.to(dt), seq)            # transformers.py:450-452, 480-481
+        n_base = rep = 0
+        if enc_hide is not None:
+            n_base, rep = enc_out.shape[0], n_img // enc_out.shape[0]
+            keymask = (keymask.view(n_base, 1, s_enc) | enc_hide.view(n_base, rep, s_enc)).reshape(-1).contiguous()
         packed_ok = dt in hip.HALF_DTYPES and 0 < s_enc <= 64
         last = plan["layers"][-1]
         attn = []                                          # return_attention: [bs, seq, s_enc] fp32 of the last layer
@@ -507,8 +535,12 @@ class _IncrementalDecoder(_Planned, nn.Module):
                 # (dperm: the head-dim slot order of the decode chain's fused fc_q + attention launch, so that teacher-forced
                 # logits and incremental decoding sum in the same order)
                 dperm = "wq_f" in L
-                kp, vt = hip.attn_cross_pack(kv, n_img, s_enc, d, nh, dperm=dperm)
+                kp, vt = hip.attn_cross_pack(kv, n_base or n_img, s_enc, d, nh, dperm=dperm)
+                if rep > 1:
+                    kp, vt = kp.repeat_interleave(rep, 0), vt.repeat_interleave(rep, 0)
                 return hip.attn_cross_prefill_packed(q, kp, vt, keymask, n_img, n_rows, s_enc, d, nh, L["ea_scale"], dperm=dperm)
+            if rep > 1:
+                kv = kv.view(n_base, s_enc * 2 * d).repeat_interleave(rep, 0).view(n_img * s_enc, 2 * d)
             return hip.attn_cross_prefill(q, kv, keymask, n_img, n_rows, s_enc, d, nh, L["ea_scale"])
 
         if "w1_f" in plan["layers"][0]:
