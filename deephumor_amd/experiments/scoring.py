@@ -163,6 +163,27 @@ def explain_captions(model, template_images, template_index, captions, lengths, 
         return CaptionScores.cat(parts)
 
 
+def _pass_logits(dec, emb, sp, tgt, return_attention=False, **kw):
+    """The forward call of the logits route (``_pass_logprobs``, ``token_alternatives``): the decoder's own teacher-forced fp32 logits of
+    the captions ``tgt`` int64 ``[bs, l]`` -> ``(logits [bs, l, V], attention [bs, >= l, S] or None)``.  Position ``p`` predicts
+    ``tgt[:, p]``.  ``kw``: ``_forward``'s ``enc_share`` / ``enc_hide``.  The rows are the classifier's own output, not a copy: their
+    stride may exceed ``V`` (``hip.linear`` pads large 16-bit logits rows to whole 64-column groups)."""
+    inp = tgt[:, :-1]
+    l = tgt.shape[1]
+    attn = None
+    if return_attention:
+        logits, attn = f32x_guarded(lambda d: d._forward(inp, sp, emb, num_positions=l, return_attention=True, **kw))(dec)
+    elif kw:
+        logits = f32x_guarded(lambda d: d._forward(inp, sp, emb, num_positions=l, **kw))(dec)
+    elif sp is not None:
+        logits = dec(inp, enc_out=sp, start_emb=emb, num_positions=l)
+    elif hasattr(dec, "lstm"):
+        logits = dec(emb, inp, None)
+    else:
+        logits = dec(inp, start_emb=emb)
+    return logits[:, :l], attn
+
+
 def _pass_logprobs(dec, emb, sp, tgt, return_attention=False, share=1, hide=None):
     """One decoder pass of ``explain_captions`` / ``score_pairs``, the one statement of their routes (``explain_captions``' docstring):
     start embeddings ``emb [bs, D]``, captions ``tgt`` int64 ``[bs, l]`` on the device -> ``(log-probs fp32 [bs, l], pads not yet
@@ -195,18 +216,8 @@ def _pass_logprobs(dec, emb, sp, tgt, return_attention=False, share=1, hide=None
         return logp.view(bs, l), attn
 
     def logits_route():
-        attn = None
-        if return_attention:
-            logits, attn = f32x_guarded(lambda d: d._forward(inp, sp, emb, num_positions=l, return_attention=True, **kw))(dec)
-        elif kw:
-            logits = f32x_guarded(lambda d: d._forward(inp, sp, emb, num_positions=l, **kw))(dec)
-        elif sp is not None:
-            logits = dec(inp, enc_out=sp, start_emb=emb, num_positions=l)
-        elif lstm:
-            logits = dec(emb, inp, None)
-        else:
-            logits = dec(inp, start_emb=emb)
-        logits = logits[:, :l].contiguous()
+        logits, attn = _pass_logits(dec, emb, sp, tgt, return_attention, **kw)
+        logits = logits.contiguous()
         return hip.token_logprob(logits.reshape(bs * l, -1), tgt.reshape(-1)).view(bs, l), attn
 
     if emb.dtype in hip.HALF_DTYPES and fused_ok:
