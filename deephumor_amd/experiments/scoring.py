@@ -163,12 +163,14 @@ def explain_captions(model, template_images, template_index, captions, lengths, 
         return CaptionScores.cat(parts)
 
 
-def _pass_logits(dec, emb, sp, tgt, return_attention=False, **kw):
+def _pass_logits(dec, emb, sp, tgt, return_attention=False, inp=None, **kw):
     """The forward call of the logits route (``_pass_logprobs``, ``token_alternatives``): the decoder's own teacher-forced fp32 logits of
     the captions ``tgt`` int64 ``[bs, l]`` -> ``(logits [bs, l, V], attention [bs, >= l, S] or None)``.  Position ``p`` predicts
-    ``tgt[:, p]``.  ``kw``: ``_forward``'s ``enc_share`` / ``enc_hide``.  The rows are the classifier's own output, not a copy: their
-    stride may exceed ``V`` (``hip.linear`` pads large 16-bit logits rows to whole 64-column groups)."""
-    inp = tgt[:, :-1]
+    ``tgt[:, p]``.  ``inp`` (``text_occlusion``): int64 ``[bs, l - 1]`` decoder inputs that differ from ``tgt[:, :-1]``.  ``kw``:
+    ``_forward``'s ``enc_share`` / ``enc_hide``.  The rows are the classifier's own output, not a copy: their stride may exceed ``V``
+    (``hip.linear`` pads large 16-bit logits rows to whole 64-column groups)."""
+    if inp is None:
+        inp = tgt[:, :-1]
     l = tgt.shape[1]
     attn = None
     if return_attention:
@@ -184,16 +186,18 @@ def _pass_logits(dec, emb, sp, tgt, return_attention=False, **kw):
     return logits[:, :l], attn
 
 
-def _pass_logprobs(dec, emb, sp, tgt, return_attention=False, share=1, hide=None):
+def _pass_logprobs(dec, emb, sp, tgt, return_attention=False, share=1, hide=None, inp=None):
     """One decoder pass of ``explain_captions`` / ``score_pairs``, the one statement of their routes (``explain_captions``' docstring):
     start embeddings ``emb [bs, D]``, captions ``tgt`` int64 ``[bs, l]`` on the device -> ``(log-probs fp32 [bs, l], pads not yet
     zeroed; attention [bs, >= l, S] or None)``.  ``sp``: the spatial features of the two cross-attention kinds, ``[bs, S, D]`` -- or,
     with ``share > 1`` (``score_pairs``' template-major passes), ``[bs / share, S, D]``: image ``j`` serves sequences
     ``j * share .. (j + 1) * share - 1`` (``TransformerDecoder._forward``'s ``enc_share``).  ``hide`` (``occlusion_maps``): uint8
-    ``[bs / share, S]`` -- ``sp`` then holds the base images whose variants the pass scores (``_forward``'s ``enc_hide``)."""
+    ``[bs / share, S]`` -- ``sp`` then holds the base images whose variants the pass scores (``_forward``'s ``enc_hide``).  ``inp``
+    (``text_occlusion``): int64 ``[bs, l - 1]`` -- what the decoder is fed when that is not ``tgt[:, :-1]``; the targets stay ``tgt``."""
     lstm = hasattr(dec, "lstm")
     dev = emb.device
-    inp = tgt[:, :-1]
+    if inp is None:
+        inp = tgt[:, :-1]
     bs, l = tgt.shape
     width = dec.classifier.in_features
     fused_ok = width % 64 == 0 and width >= 128                                  # dh_vocab_logprob's contract
@@ -216,7 +220,7 @@ def _pass_logprobs(dec, emb, sp, tgt, return_attention=False, share=1, hide=None
         return logp.view(bs, l), attn
 
     def logits_route():
-        logits, attn = _pass_logits(dec, emb, sp, tgt, return_attention, **kw)
+        logits, attn = _pass_logits(dec, emb, sp, tgt, return_attention, inp=inp, **kw)
         logits = logits.contiguous()
         return hip.token_logprob(logits.reshape(bs * l, -1), tgt.reshape(-1)).view(bs, l), attn
 
