@@ -14,9 +14,13 @@
 
 // order-preserving float -> uint key (larger float <=> larger key; -0.0 and +0.0 share ONE key, as they compare equal in the
 // reference's `logits < threshold` (beam.py:34): with distinct keys a row whose k-th largest logit is a zero dropped the zeros of the
-// other sign that torch keeps as ties -- found by tools/fuzz_sampler.py on quantised logits)
+// other sign that torch keeps as ties -- found by tools/fuzz_sampler.py on quantised logits).  A NaN of EITHER sign gets the largest
+// key, as torch.topk ranks it (beam.py:32): it is then always among a row's survivors and the row flags DH_BEAM_ERR_NONFINITE where
+// the reference's torch.multinomial raises -- with the plain bit trick a NaN whose sign bit is set ordered below -inf, fell out of
+// the top-k and the row was drawn without a flag.
 __device__ __forceinline__ uint32_t f2key(float f) {
     uint32_t u = __float_as_uint(f);
+    if ((u & 0x7FFFFFFFu) > 0x7F800000u) return 0xFFFFFFFFu;
     if (u == 0x80000000u) u = 0u;
     return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
 }
@@ -231,7 +235,10 @@ __global__ __launch_bounds__(256) void beam_row_sample_kernel(
     }
     __syncthreads();
     if (tid == 0) {
-        if (n < beam) atomicOr(err, DH_BEAM_ERR_TOO_FEW);
+        // fewer positive-probability tokens than beams: a survivor at -inf (a threshold of -inf keeps them all) is a dead pick too
+        int n_live = 0;
+        for (int b = 0; b < beam; ++b) n_live += picks[b] >= 0 && val_b[picks[b]] > -INFINITY;
+        if (n_live < beam) atomicOr(err, DH_BEAM_ERR_TOO_FEW);
         // log_softmax over the gathered (un-tempered) logits of the picks (beam.py:79)
         float mx = -INFINITY;
         for (int b = 0; b < beam; ++b) if (picks[b] >= 0) mx = fmaxf(mx, val_b[picks[b]]);
@@ -362,8 +369,10 @@ __device__ __attribute__((noinline)) void row_overflow(const float* __restrict__
     }
     if (tid == 0) {                                    // log_softmax over the gathered (un-tempered) logits of the picks (beam.py:79)
         float mx = -INFINITY;
+        int n_live = 0;                                  // (more than CAP survivors, yet fewer than `beam` above -inf: dead picks)
 #pragma unroll 1
-        for (int b = 0; b < beam; ++b) mx = fmaxf(mx, row[picks[b]]);
+        for (int b = 0; b < beam; ++b) { mx = fmaxf(mx, row[picks[b]]); n_live += row[picks[b]] > -INFINITY; }
+        if (n_live < beam) atomicOr(err, DH_BEAM_ERR_TOO_FEW);
         float se = 0.f;
 #pragma unroll 1
         for (int b = 0; b < beam; ++b) se += expf(row[picks[b]] - mx);
@@ -507,9 +516,11 @@ __device__ __forceinline__ void row_tail(const RowLds& L, int rc, int ldl, int r
     __syncthreads();
     if (tid < 64) {
         // log_softmax over the gathered (un-tempered) logits of the picks (beam.py:79): lane b owns pick b
-        if (tid == 0 && n < beam) atomicOr(err, DH_BEAM_ERR_TOO_FEW);
         const int pi = tid < beam ? picks[tid] : -1;
         const float lv = pi >= 0 ? val_a[pi] : -INFINITY;
+        // fewer positive-probability tokens than beams: a survivor at -inf (a threshold of -inf keeps them all) is a dead pick too
+        const int n_live = __popcll(__ballot(lv > -INFINITY));
+        if (tid == 0 && n_live < beam) atomicOr(err, DH_BEAM_ERR_TOO_FEW);
         const float mx = wave_max(lv);
         const float se = wave_sum(pi >= 0 ? expf(lv - mx) : 0.f);
         const float lse = logf(se);
